@@ -4,9 +4,12 @@
 A "step" is one model time step (advance + scatter + remesh) of the BASELINE.json metric
 workload: the 4096×4096 periodic Cartesian box, 1 particle per cell, constant winds (10,10),
 bench06 physics (configs.box4096), slab-partitioned over the N GPUs (strong scaling).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, conditions the clocks, warms up, times the K
+steps and prints the headline; --full adds the CPU baseline, the secondary measurements, the
+per-launch spread, the ring's phase diagnosis and the state check.  --dump-outputs DIR writes what
+the timed steps computed (State and particles, float64 .npy).
 
-    python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -120,6 +123,31 @@ def measured_traffic(args, world):
     return None, None, None
 
 
+DUMP_NODES = 1 << 19     # nodes --dump-outputs writes at most: (3 + 5) float64 per node = 32 MB
+
+
+def dump_outputs(model, out_dir, dist=None):
+    """what the timed path computed in its last step, as a caller of it receives the model: the node State and the particle state,
+    one row per node (global index i + Nx j), every node up to DUMP_NODES, above that a fixed, seeded sample of the nodes (sorted).
+    Collective over the ranks of a slab run; rank 0 writes."""
+    Nx, Ny = int(model.grid.stats.Nx), int(model.grid.stats.Ny)
+    n = Nx * Ny
+    idx = np.arange(n) if n <= DUMP_NODES else np.sort(np.random.default_rng(12345).choice(n, DUMP_NODES, replace=False))
+    lo, hi = Nx * model.j0, Nx * model.j1
+    sel = idx[(idx >= lo) & (idx < hi)] - lo
+    s = model.get_state()                                   # completes the last step (picles_sync)
+    z = model.backend.get_particles()[0]
+    part = (s.reshape(-1, 3, order="F")[sel], z.reshape(-1, 5, order="F")[sel])
+    parts = [part]
+    if dist is not None:
+        parts = [None] * model.world
+        dist.all_gather_object(parts, part)
+    if model.rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "state.npy"), np.concatenate([p[0] for p in parts]).astype(np.float64))
+        np.save(os.path.join(out_dir, "particles.npy"), np.concatenate([p[1] for p in parts]).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -160,6 +188,14 @@ def main():
                          "PICLES_CCL_LIB names — the rehearsal of the N > 1 launch path on one GPU (tests/native/shm_ccl.cpp)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 path with all ranks on ONE GPU (halo staged through the host)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline (--no-cpu drops it), the secondary measurements "
+                         "(--no-secondary drops them), the instrumented pass behind the timed region (min / median launch), the ring's "
+                         "phase diagnosis and the state check.  Off: set up, warm up, time the K steps, dump, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed as DIR/state.npy (node State: energy, momentum x, y) and "
+                         f"DIR/particles.npy (the 5 particle components), float64, one row per node in global x-fastest order; above "
+                         f"{DUMP_NODES} nodes a fixed, seeded sample of the nodes")
     args = ap.parse_args()
 
     # stdout carries the ONE JSON line and nothing else: whatever the runtime libraries print (RCCL's version banner and
@@ -266,6 +302,8 @@ def main():
 
     cnt = model.backend.get_counters()
     tim = model.backend.get_timing()
+    if args.dump_outputs:
+        dump_outputs(model, args.dump_outputs, dist if use_dist else None)
     # where each rank's ring steps went (edge launch / exchange / interior launch, and whether the exchange was hidden behind the
     # interior launch): one line of diagnosis per rank for the multi-GPU run, from events the ring records itself
     def ring_phase_pass(m, dt):
@@ -279,7 +317,7 @@ def main():
         return m.backend.slab_phases()
 
     slab_phases = None
-    if model.native and not args.no_events:
+    if args.full and model.native and not args.no_events:
         ph = ring_phase_pass(model, configs.box4096(n=args.n).Δt)
         row = torch.tensor([float(rank), float(ph["steps"]), float(ph["exchange_hidden_steps"]), ph["edge_ms"], ph["exchange_ms"],
                             ph["interior_ms"], ph["slack_ms"], ph["span_ms"]], dtype=torch.float64,
@@ -292,7 +330,7 @@ def main():
                         "exchange_ms": float(r[4]), "interior_ms": float(r[5]), "exchange_end_to_interior_end_ms": float(r[6]),
                         "step_span_ms": float(r[7])} for r in rows]
     launch_samples = None
-    if (world == 1 and not args.no_events and not args.launch_events and not args.ring_of_one and not args.atomic):
+    if (args.full and world == 1 and not args.no_events and not args.launch_events and not args.ring_of_one and not args.atomic):
         # spread of the launch durations: a SEPARATE instrumented pass (events around every launch) right behind the timed region —
         # a few un-timed launches first, so that the pass does not start on a GPU that idled (and clocked down) during the readback
         model.run_steps(configs.box4096(n=args.n).Δt, 3, flags)
@@ -321,7 +359,7 @@ def main():
     state_check = None
     # (not for --atomic: the atomic push sums in run-dependent order, and that last-bit noise is amplified by the stiff direction
     # mode to the solver tolerance — DESIGN.md §3; the headline path is the deterministic pull)
-    if (args.winds[0] == args.winds[1] or world > 1) and not args.atomic:
+    if args.full and (args.winds[0] == args.winds[1] or world > 1) and not args.atomic:
         e = model.get_state()[..., 0]
         ext = torch.tensor([float(e.min()), -float(e.max())], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         if use_dist:
@@ -397,7 +435,8 @@ def main():
                                      else "one pair per launch")
         if getattr(model, "timing_region", False) and model.native:
             out["roofline"]["events"] += (" on the interior stream of the ring; avg_launch_ms = region / launches (edge + interior launch of a "
-                                          "step overlap: two launches per step); phase diagnosis in a separate pass behind it")
+                                          "step overlap: two launches per step)"
+                                          + ("; phase diagnosis in a separate pass behind it" if slab_phases is not None else ""))
         if launch_samples is not None:
             samples = launch_samples
             out["roofline"]["launch_samples"] = (f"separate pass of {samples.size} launches with per-launch events, right behind the timed region "
@@ -418,7 +457,7 @@ def main():
         out["config"]["step_loop"] = ("native: picles_slab_run_steps (RCCL send/recv issued from C)" if model.native else
                                       ("native: picles_run_steps" if (world == 1 and not args.atomic and model.ex is None) else
                                        "python: one C call per step" + ("" if world == 1 else ", torch.distributed P2P")))
-        if world == 1 and not args.no_secondary and not args.atomic and not args.ring_of_one:
+        if args.full and world == 1 and not args.no_secondary and not args.atomic and not args.ring_of_one:
             # the honest spread: the BASELINE winds (10,10) are the best case of the explicit pair; a generic
             # wind direction and the reference's DEFAULT solver, same box, same process
             del model
@@ -524,7 +563,7 @@ def main():
                 leg("slab_4096x512", lambda: slab_shape(False))
                 leg("slab_4096x512_ring_of_one", lambda: slab_shape(True))
             out["secondary_legs"] = ext
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, W, Ksteps)
             except Exception as e:  # the baseline is reported, never required for the GPU number

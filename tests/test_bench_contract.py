@@ -1,11 +1,13 @@
-"""bench.py's output contract: ONE JSON line with the driver's keys plus the `roofline` and `cpu_baseline`
-objects.  CPU: the committed round profile; GPU: a live (small-grid) invocation as a subprocess."""
+"""bench.py's output contract: ONE JSON line with the driver's keys plus the `roofline` object; with --full also the
+`cpu_baseline`, `secondary` and `state_check` objects.  CPU: the committed round profile; GPU: a live (small-grid) invocation as a
+subprocess."""
 import json
 import os
 import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -82,13 +84,51 @@ def _check_round4_legs(d):
 @pytest.mark.gpu
 def test_live_bench_prints_one_json_line():
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--grid-n", "256", "--cpu-seconds", "0.5"], check=True, capture_output=True, text=True).stdout
+                          "--grid-n", "256", "--cpu-seconds", "0.5", "--full"], check=True, capture_output=True, text=True).stdout
     lines = [l for l in out.splitlines() if l.strip()]
     assert len(lines) == 1, out
     d = json.loads(lines[0])
     _check(d, need_cpu=True)
     assert d["steps"] == 3 and d["warmup"] == 1 and d["config"]["particles"] == 256 * 256
     _check_round2_fields(d, steady=False)
+
+
+def test_plain_run_options_are_there():
+    """the extras of the benchmark sit behind --full; --dump-outputs writes what the timed steps computed (parsing needs no GPU)"""
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--help"], check=True, capture_output=True, text=True).stdout
+    assert "--full" in out and "--dump-outputs" in out
+
+
+def _check_dump(d, nodes):
+    """the dumped State and particles: float64, one row per (sampled) node; the homogeneous periodic box has one energy everywhere"""
+    s, z = np.load(d / "state.npy"), np.load(d / "particles.npy")
+    assert s.dtype == z.dtype == np.float64 and s.shape == (min(nodes, 1 << 19), 3) and z.shape == (s.shape[0], 5)
+    assert s.nbytes + z.nbytes <= 64 << 20
+    e = s[:, 0]
+    assert e.min() > 0 and (e.max() - e.min()) / e.max() < 1e-9
+    return s, z
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """without --full: the K timed steps and the line — no CPU baseline, no secondary legs, no instrumented pass behind the timed
+    region, no state check; --dump-outputs writes what the timed steps computed, identical for identical arguments (768^2 nodes:
+    more than the dump keeps, so the seeded sample is what is compared)"""
+    def run(d):
+        out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                              "--grid-n", "768", "--dump-outputs", str(d)], check=True, capture_output=True, text=True).stdout
+        lines = [l for l in out.splitlines() if l.strip()]
+        assert len(lines) == 1, out
+        return json.loads(lines[0])
+    a = run(tmp_path / "a")
+    _check(a, need_cpu=False)
+    assert a["steps"] == 5 and a["warmup"] == 2 and a["roofline"]["launches"] == 5 and a["config"]["particles"] == 768 * 768
+    assert not {"cpu_baseline", "secondary", "secondary_legs", "slab_phases"} & set(a) and "launch_samples" not in a["roofline"]
+    assert a["state_check"] is None
+    sa, za = _check_dump(tmp_path / "a", 768 * 768)
+    run(tmp_path / "b")
+    sb, zb = _check_dump(tmp_path / "b", 768 * 768)
+    assert np.array_equal(sa, sb) and np.array_equal(za, zb)
 
 
 @pytest.mark.gpu
@@ -98,7 +138,7 @@ def test_clock_conditioning_leaves_the_timed_steps_untouched(extra):
     exactly the model a fresh seed gives: the same steps are timed, the same work is counted, the state after them agrees to the bit"""
     def run(ms):
         out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "2", "--grid-n", "256", "--no-cpu",
-                              "--no-secondary", "--prewarm-ms", str(ms)] + extra, check=True, capture_output=True, text=True).stdout
+                              "--no-secondary", "--full", "--prewarm-ms", str(ms)] + extra, check=True, capture_output=True, text=True).stdout
         return json.loads([l for l in out.splitlines() if l.startswith("{")][0])
     a, b = run(0), run(5)
     assert a["config"]["clock_prewarm"]["untimed_steps"] == 0 and b["config"]["clock_prewarm"]["untimed_steps"] > 40      # more than one cycle
@@ -114,7 +154,7 @@ def test_ring_of_one_bench_prints_one_json_line():
     blocks sent to ourselves and consumed by the pull) on one rank: stdout still carries exactly one JSON line although RCCL
     prints its banner"""
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--ring-of-one", "--steps", "4", "--warmup", "1",
-                          "--grid-n", "256", "--no-cpu"], check=True, capture_output=True, text=True).stdout
+                          "--grid-n", "256", "--no-cpu", "--full"], check=True, capture_output=True, text=True).stdout
     lines = [l for l in out.splitlines() if l.strip()]
     assert len(lines) == 1, out
     d = json.loads(lines[0])
@@ -139,7 +179,7 @@ def shm_ccl(tmp_path_factory):
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("world,n", [(2, 512), (4, 4096)])
-def test_multi_process_launch_path_end_to_end_on_one_gpu(shm_ccl, world, n):
+def test_multi_process_launch_path_end_to_end_on_one_gpu(shm_ccl, world, n, tmp_path):
     """what the driver's SCALE run executes — `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`:
     N processes, rendezvous, the communicator id handed out by a torch.distributed broadcast, every rank in the library's NATIVE
     ring (picles_slab_comm_init / picles_slab_run_steps), the reductions of the result line, the state check across the slabs,
@@ -154,7 +194,8 @@ def test_multi_process_launch_path_end_to_end_on_one_gpu(shm_ccl, world, n):
     env = dict(os.environ, PICLES_CCL_LIB=str(shm_ccl), HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2",
-           "--grid-n", str(n), "--backend", "gloo", "--native-ring", "--no-cpu"]
+           "--grid-n", str(n), "--backend", "gloo", "--native-ring", "--no-cpu", "--full",
+           "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=540)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -171,3 +212,4 @@ def test_multi_process_launch_path_end_to_end_on_one_gpu(shm_ccl, world, n):
     for p in ph:
         assert p["steps"] == 4 and p["edge_ms"] > 0 and p["interior_ms"] > 0 and p["exchange_ms"] >= 0 and 0 <= p["exchange_hidden_steps"] <= 4
         assert p["step_span_ms"] >= max(p["edge_ms"], p["interior_ms"]) * 0.99
+    _check_dump(tmp_path, n * n)          # every rank's slab (or its part of the sample) gathered on rank 0

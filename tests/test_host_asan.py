@@ -24,12 +24,13 @@ import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-OUT = Path(os.environ.get("PICLES_HOST_ASAN_OUT", "/tmp/picles_host_asan"))
 
 
 @pytest.mark.skipif(not Path(HIPCC).exists(), reason="no hipcc")
-def test_product_host_code_is_clean_under_asan():
+def test_product_host_code_is_clean_under_asan(tmp_path_factory):
     d = ROOT / "tests" / "native" / "host_asan"
+    # a build directory of this session's own (PICLES_HOST_ASAN_OUT: a persistent one), never shared with another user or tree
+    OUT = Path(os.environ.get("PICLES_HOST_ASAN_OUT") or tmp_path_factory.mktemp("host_asan"))
     r = subprocess.run(["make", "-s", "-j4", f"OUT={OUT}"], cwd=d, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     env = dict(os.environ, PICLES_CCL_LIB=str(OUT / "libloopback_ccl.so"),
@@ -74,7 +75,8 @@ def test_oracle_and_its_glue_are_clean_on_the_scenarios_around_the_recorded_cras
                             "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fopenmp", *flag, str(src), "-o",
                             str(tmp_path / f"liboracle_{kind}.so"), "-lm"], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
-    env = dict(os.environ, LD_PRELOAD=f"{asan} {ubsan}", ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    preload = " ".join(x for x in (asan, ubsan, os.environ.get("LD_PRELOAD", "")) if x)     # the sanitizer runtimes first, nothing dropped
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
     # 5116 is the scenario whose teardown crashed; 5104-5124 brackets it (and holds the runaway particle that tripped UBSan)
     r = subprocess.run([sys.executable, "-c", REPLAY.format(root=str(ROOT), out=str(tmp_path), lo=5104, hi=5125)],
                        capture_output=True, text=True, timeout=1200, env=env)
