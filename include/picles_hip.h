@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 4
+#define PICLES_ABI_VERSION 5
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -332,6 +332,31 @@ typedef struct picles_slab_phases {
     double   span_ms;          /* edge begin -> the later of exchange end and interior end, summed              */
 } picles_slab_phases;
 int32_t picles_slab_get_phases(picles_ctx *ctx, picles_slab_phases *out);
+
+/* ---- exact restart: the checkpoint blob (run!(sim; pickup = true) of an Oceananigans-style Checkpointer; the reference's
+ * `pickup` keyword is accepted and ignored, run.jl:36) ----------------------------------------------------------------------
+ * A blob holds the prognostic state of the context's rows at a step boundary: State, the particles (z, on, status, the step-size
+ * memory dtn / qold, the AutoSwitch state), the statistics and scatter-reach counters and the clock (layout: DESIGN.md §11).  The
+ * configuration is NOT saved: the restoring program builds the same model (grid, mask, physics, ODE settings, metric, wind source)
+ * and loads the blob into it; a fingerprint of that configuration in the blob's header is checked.  A loaded context continues
+ * bit for bit as the context that wrote the blob would have.
+ *   size:  header + payload bytes of a blob of this context (no device work)
+ *   begin: completes a pending step, packs the planes into a device snapshot (one kernel on the context stream) and starts an
+ *          asynchronous copy into pinned host memory on the store stream — steps enqueued after it overlap the copy
+ *   end:   waits for that copy and writes the blob into buf (>= size bytes).  A synchronous save is begin directly followed by end.
+ *   load:  refuses (each with its code below and a picles_last_error text, the context unchanged) a short buffer, a foreign
+ *          blob, another format / ABI version, a different configuration, a payload whose checksum (verified on the device,
+ *          before anything is overwritten) does not match, and a context with a store snapshot or checkpoint in flight. */
+#define PICLES_CKPT_E_SHORT    -20   /* buffer shorter than a header, or than the payload the header announces      */
+#define PICLES_CKPT_E_MAGIC    -21   /* not a checkpoint blob                                                         */
+#define PICLES_CKPT_E_VERSION  -22   /* another blob format or ABI version                                            */
+#define PICLES_CKPT_E_CONFIG   -23   /* fingerprint mismatch: the context was not built from the same configuration   */
+#define PICLES_CKPT_E_CHECKSUM -24   /* the payload's checksum does not match                                         */
+#define PICLES_CKPT_E_BUSY     -25   /* a store snapshot or checkpoint of this context is in flight (load), or a checkpoint is (begin) */
+int32_t picles_checkpoint_size(picles_ctx *ctx, size_t *bytes);
+int32_t picles_checkpoint_begin(picles_ctx *ctx);
+int32_t picles_checkpoint_end(picles_ctx *ctx, void *buf, size_t bytes);
+int32_t picles_checkpoint_load(picles_ctx *ctx, const void *buf, size_t bytes);
 
 /* ---- generic particle->mesh scatter of an arbitrary particle list --------------
  * (ParticleInCell.push_to_grid! over a list, ParticleInCell.jl:341-376,530-538):

@@ -101,10 +101,16 @@ LATTICE_LINEAR, LATTICE_SMOOTH3 = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 4
+ABI_VERSION = 5
 SLAB_ID_BYTES = 128
 
 ROWS_ALL, ROWS_EDGE, ROWS_INTERIOR = 0, 1, 2
+
+# picles_checkpoint_load refusals (include/picles_hip.h) and the blob's header
+CKPT_E_SHORT, CKPT_E_MAGIC, CKPT_E_VERSION, CKPT_E_CONFIG, CKPT_E_CHECKSUM, CKPT_E_BUSY = -20, -21, -22, -23, -24, -25
+CKPT_MAGIC = 0x31544b4353454c43
+CKPT_HEADER_BYTES = 256
+CKPT_SEGMENTS = ("state", "z", "qold", "dtn", "asw", "status", "on", "pflags", "counters", "reach_maps")
 
 ST_STEPPED, ST_MAXITERS, ST_RESEED_NAN, ST_RESEED_INF = 1, 2, 4, 8
 ST_CLAMPED, ST_SWITCHED_ON, ST_DTMIN, ST_NONFINITE = 16, 32, 64, 128
@@ -173,6 +179,10 @@ SYMBOLS = {
     "picles_slab_comm_destroy": (C.c_int32, [_VP]),
     "picles_slab_get_phases": (C.c_int32, [_VP, C.POINTER(PiclesSlabPhases)]),
     "picles_scatter_particles": (C.c_int32, [_VP, C.c_int64, c_int32_p, c_double_p, c_double_p]),
+    "picles_checkpoint_size": (C.c_int32, [_VP, C.POINTER(C.c_size_t)]),
+    "picles_checkpoint_begin": (C.c_int32, [_VP]),
+    "picles_checkpoint_end": (C.c_int32, [_VP, _VP, C.c_size_t]),
+    "picles_checkpoint_load": (C.c_int32, [_VP, _VP, C.c_size_t]),
 }
 
 _lib = None
@@ -180,6 +190,14 @@ _lib = None
 
 class PiclesError(RuntimeError):
     pass
+
+
+class CheckpointError(PiclesError):
+    """a checkpoint blob or file was refused; `code` is one of the CKPT_E_* values (0 for refusals of the file layer)"""
+
+    def __init__(self, code, msg):
+        super().__init__(msg)
+        self.code = code
 
 
 def _settle_rocm_runtime():

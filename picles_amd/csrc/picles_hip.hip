@@ -32,6 +32,7 @@
  *   k_push_tiles     PUSH scatter: LDS-staged grid tile + apron, ds_add_f64 inside the tile,
  *                    one global fp64 atomic per touched tile node. HBM/atomic bound.
  *   k_remesh         stand-alone NodeToParticle! (split API).
+ *   k_ckpt           checkpoint payload: packs / verifies / unpacks the planes of a restart blob in one pass. HBM bound.
  */
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -420,6 +421,25 @@ __global__ void __launch_bounds__(256) k_wind_poly(WindPolyForm F, const double 
  * ---------------------------------------------------------------------------------------- */
 static thread_local std::string g_create_error;
 
+/* configuration fingerprint of a checkpoint (picles_checkpoint_*): a 64-bit word hash, FNV-style multiply + fold */
+static const uint64_t FP_SEED = 0xcbf29ce484222325ull;
+static uint64_t fp_bytes(uint64_t h, const void *p, size_t bytes)
+{
+    const unsigned char *b = (const unsigned char *)p;
+    size_t k = 0;
+    for (; k + 8 <= bytes; k += 8) {
+        uint64_t w;
+        memcpy(&w, b + k, 8);
+        h = (h ^ w) * 0x100000001b3ull;
+        h ^= h >> 29;
+    }
+    uint64_t w = (uint64_t)(bytes - k) << 56;
+    if (k < bytes) { uint64_t t = 0; memcpy(&t, b + k, bytes - k); w ^= t; }
+    h = (h ^ w) * 0x100000001b3ull;
+    return h ^ (h >> 29);
+}
+template <class T> static uint64_t fp_val(uint64_t h, T v) { return fp_bytes(h, &v, sizeof v); }
+
 struct picles_ctx {
     picles_grid g;
     picles_phys ph;
@@ -488,6 +508,14 @@ struct picles_ctx {
     int poly_cap = 0;                              /* knots the two buffers hold */
     bool ext_streams = false;      /* a caller-provided stream has been used: order across streams with device syncs */
     bool ring_orders = false;      /* inside picles_slab_run_steps: the ring orders its streams against the context stream with events */
+    /* exact restart (picles_checkpoint_*): the device snapshot of the payload + its sum words, its pinned host copy */
+    unsigned char *ck_dev = nullptr, *ck_host = nullptr;
+    size_t ck_cap = 0;
+    hipEvent_t ck_ready = nullptr, ck_done = nullptr;
+    bool ck_inflight = false;
+    unsigned char ck_hdr[256];                     /* header of the checkpoint in flight (CkptHeader), written by begin */
+    int halo0 = 0;                                 /* halo_rows the context was created with (fingerprinted; the current ones are state) */
+    uint64_t fp_metric = 0, fp_lattice = 0;        /* hashes of the metric planes / the wind lattice as the caller handed them over */
     /* generic scatter scratch */
     int *d_count = nullptr, *d_start = nullptr, *d_cursor = nullptr;
     void *d_scan_tmp = nullptr;
@@ -681,6 +709,7 @@ PX_EXPORT int32_t picles_create(const picles_grid *g, const picles_phys *p, cons
     G.j_begin = g->j_begin; G.ny_loc = g->j_end - g->j_begin;
     G.single_slab = (g->j_begin == 0 && g->j_end == g->Ny);
     G.R = halo_rows;
+    c->halo0 = halo_rows;
     G.Rp = G.single_slab ? 0 : halo_rows;
     G.ngroups = 1;
 
@@ -772,6 +801,7 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     hipSetDevice(c->device);
     if (c->ring) picles_slab_comm_destroy(c);
     if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->store_stream) hipStreamSynchronize(c->store_stream);     /* a checkpoint's copy-out may still be on PCIe */
     Arrays &A = c->A;
     hipFree(A.state); hipFree(A.movie); hipFree(A.z); hipFree(A.qold); hipFree(A.dtn); hipFree(A.asw); hipFree(A.on);
     hipFree(A.pflags); hipFree(A.status); hipFree(A.u0); hipFree(A.v0); hipFree(A.u1); hipFree(A.v1);
@@ -787,6 +817,10 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     for (auto p : c->store_host) hipHostFree(p);
     for (auto e : c->store_ready) hipEventDestroy(e);
     for (auto e : c->store_done) hipEventDestroy(e);
+    if (c->ck_dev) hipFree(c->ck_dev);
+    if (c->ck_host) hipHostFree(c->ck_host);
+    if (c->ck_ready) hipEventDestroy(c->ck_ready);
+    if (c->ck_done) hipEventDestroy(c->ck_done);
     if (c->store_stream) hipStreamDestroy(c->store_stream);
     if (c->d_wgu) hipFree(c->d_wgu);
     if (c->d_wgv) hipFree(c->d_wgv);
@@ -977,8 +1011,10 @@ PX_EXPORT int32_t picles_set_metric(picles_ctx *c, const double *m11, const doub
     HIPCHK(c, hipDeviceSynchronize());
     Arrays &A = c->A;
     if (A.m11) { hipFree(A.m11); hipFree(A.m22); hipFree(A.pc); A.m11 = A.m22 = A.pc = nullptr; }
+    c->fp_metric = 0;
     if (!m11 || !m22 || !pc) return 0;   /* back to the Cartesian constants */
     size_t b = (size_t)A.n * 8;
+    c->fp_metric = fp_bytes(fp_bytes(fp_bytes(FP_SEED, m11, b), m22, b), pc, b);
     HIPCHK(c, hipMalloc(&A.m11, b)); HIPCHK(c, hipMalloc(&A.m22, b)); HIPCHK(c, hipMalloc(&A.pc, b));
     HIPCHK(c, hipMemcpy(A.m11, m11, b, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(A.m22, m22, b, hipMemcpyHostToDevice));
@@ -1001,6 +1037,7 @@ PX_EXPORT int32_t picles_set_wind_grid(picles_ctx *c, int32_t nx, int32_t ny, in
     HIPCHK(c, hipMalloc(&c->d_wgv, nb));
     HIPCHK(c, hipMemcpy(c->d_wgu, u, nb, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_wgv, v, nb, hipMemcpyHostToDevice));
+    c->fp_lattice = fp_bytes(fp_bytes(FP_SEED, u, nb), v, nb);
     WindGrid &w = c->wg;
     w.nx = nx; w.ny = ny; w.nt = nt;
     w.x0 = x0; w.inv_dx = 1.0 / dx; w.y0 = y0; w.inv_dy = 1.0 / dy; w.t0 = t0; w.inv_dt = 1.0 / dt;
@@ -1700,7 +1737,7 @@ PX_EXPORT int32_t picles_store_init(picles_ctx *c, int32_t n_slots)
     HIPCHK(c, hipDeviceSynchronize());
     if (c->store_slots) return fail(c, -2, "store already initialised");
     size_t b = 3 * (size_t)c->A.n * 8;
-    HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));   /* (a checkpoint may have made it) */
     for (int k = 0; k < n_slots; k++) {
         double *d = nullptr, *h = nullptr;
         hipEvent_t e1, e2;
@@ -2158,5 +2195,310 @@ PX_EXPORT int32_t picles_scatter_particles(picles_ctx *c, int64_t np, const int3
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
     c->state_zero = false;
+    return 0;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * Exact restart: the checkpoint blob (picles_checkpoint_*).
+ * blob = CkptHeader (256 bytes) + payload.  The payload is the context's planes, one segment each in a fixed order, every segment
+ * starting at a multiple of 256 bytes and zero-padded up to the next:
+ *   0 State (3 planes f64)   1 z (5 planes f64)   2 qold f64   3 dtn f64   4 asw i32   5 status i32   6 on u8   7 pflags u8
+ *   8 the statistics slots + the 16 reach-counter words behind them (kernels.h: DevCounters, reach_counters)
+ *   9 the five rotating local-reach maps (Arrays::rmap)
+ * k_ckpt moves it between the planes and one contiguous device snapshot in a single pass over HBM (16-byte loads and stores,
+ * one segment per grid row) and sums it on the way.  The sum: Σ over the payload's 16-byte chunks g of
+ * mix(lo ^ 2g K) + mix(hi ^ (2g+1) K) mod 2^64 — independent of the order the chunks are visited in (the same bits for any dispatch),
+ * bound to positions, and a changed word changes exactly one term (mix is a bijection), so any changed byte changes the sum.
+ *   MODE 0: pack the planes into the snapshot, add its sum to sums[0]
+ *   MODE 1: add the sum of the snapshot (a blob being loaded) to sums[0]
+ *   MODE 2: unpack the snapshot into the planes — only where sums[0] == sums[1] (the verified sum and the header's)
+ * ---------------------------------------------------------------------------------------- */
+#define CKPT_NSEG 10
+#define CKPT_MAGIC 0x31544b4353454c43ull      /* "CLESCKT1" little-endian */
+#define CKPT_FORMAT 1
+struct CkptSegs {
+    unsigned char *ptr[CKPT_NSEG];            /* the context's plane */
+    unsigned long long off[CKPT_NSEG];        /* its offset in the payload */
+    unsigned long long len[CKPT_NSEG];        /* its length [bytes] */
+    unsigned long long span[CKPT_NSEG];       /* its length padded to 256 bytes: off[k + 1] - off[k] */
+};
+struct CkptHeader {                           /* little-endian, 256 bytes; the offsets of the fields are part of the format */
+    uint64_t magic;                           /*   0  CKPT_MAGIC                                                      */
+    uint32_t format, abi;                     /*   8  CKPT_FORMAT, PICLES_ABI_VERSION                                 */
+    uint64_t header_bytes, payload_bytes;     /*  16  sizeof(CkptHeader), the payload that follows                    */
+    uint64_t fingerprint, checksum;           /*  32  configuration hash, payload sum (k_ckpt)                        */
+    double   clock;                           /*  48  model time of the step boundary                                  */
+    int32_t  halo_rows, mr_w;                 /*  56  ghost rows; index of the reach counter of the latest step        */
+    int32_t  cur, nseg;                       /*  64  record buffer of the latest step; CKPT_NSEG                      */
+    int64_t  n;                               /*  72  nodes = particles of the context's rows                          */
+    uint64_t seg_off[CKPT_NSEG];              /*  80  segment offsets in the payload                                   */
+    uint64_t seg_len[CKPT_NSEG];              /* 160  segment lengths                                                  */
+    double   step_dt;                         /* 240  Δt of the latest step                                            */
+    int32_t  state_zero, pad_;                /* 248  State known to be all zero                                       */
+};
+static_assert(sizeof(CkptHeader) == 256, "checkpoint header layout");
+
+__device__ __forceinline__ unsigned long long ck_mix(unsigned long long x)
+{
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+    return x ^ (x >> 33);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_ckpt(CkptSegs S, unsigned char *snap, unsigned long long *sums)
+{
+    if (MODE == 2 && sums[0] != sums[1]) return;        /* not verified: nothing of the context is touched */
+    const int s = blockIdx.y;
+    unsigned char *seg = S.ptr[s];
+    const unsigned long long len = S.len[s], nch = S.span[s] >> 4, nfull = len >> 4, g0 = S.off[s] >> 4;
+    uint4 *sn = (uint4 *)(snap + S.off[s]);
+    unsigned long long acc = 0;
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < nch; q += stride) {
+        uint4 v;
+        if (MODE == 0) {
+            if (q < nfull) v = ((const uint4 *)seg)[q];
+            else {                                        /* the segment's partial last chunk, and the zero padding behind it */
+                unsigned int w[4] = {0u, 0u, 0u, 0u};
+                for (int k = 0; k < 16; k++) {
+                    const unsigned long long o = q * 16 + k;
+                    if (o < len) w[k >> 2] |= (unsigned int)seg[o] << (8 * (k & 3));
+                }
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            sn[q] = v;
+        } else {
+            v = sn[q];
+            if (MODE == 2) {
+                if (q < nfull) ((uint4 *)seg)[q] = v;
+                else {
+                    const unsigned int w[4] = {v.x, v.y, v.z, v.w};
+                    for (int k = 0; k < 16; k++) {
+                        const unsigned long long o = q * 16 + k;
+                        if (o < len) seg[o] = (unsigned char)(w[k >> 2] >> (8 * (k & 3)));
+                    }
+                }
+            }
+        }
+        if (MODE != 2) {
+            const unsigned long long g = g0 + q, K = 0x9e3779b97f4a7c15ull;
+            const unsigned long long lo = ((unsigned long long)v.y << 32) | v.x, hi = ((unsigned long long)v.w << 32) | v.z;
+            acc += ck_mix(lo ^ (2 * g) * K) + ck_mix(hi ^ (2 * g + 1) * K);
+        }
+    }
+    if (MODE != 2) {
+        acc = wave_sum_u64(acc);                          /* kernels.h: every lane of the wave is here */
+        if ((threadIdx.x & 63) == 0 && acc) atomicAdd(sums, acc);
+    }
+}
+
+static unsigned long long ckpt_layout(picles_ctx *c, CkptSegs &S)
+{
+    Arrays &A = c->A;
+    const unsigned long long n = (unsigned long long)A.n;
+    struct { void *p; unsigned long long len; } seg[CKPT_NSEG] = {
+        {A.state, 24 * n}, {A.z, 40 * n}, {A.qold, 8 * n}, {A.dtn, 8 * n}, {A.asw, 4 * n}, {A.status, 4 * n}, {A.on, n}, {A.pflags, n},
+        {A.cnt, NSLOTS * sizeof(DevCounters) + 16 * sizeof(int)}, {A.rmap, (unsigned long long)5 * A.ntile * sizeof(int)}};
+    unsigned long long off = 0;
+    for (int k = 0; k < CKPT_NSEG; k++) {
+        S.ptr[k] = (unsigned char *)seg[k].p;
+        S.off[k] = off;
+        S.len[k] = seg[k].len;
+        S.span[k] = (seg[k].len + 255) & ~255ull;
+        off += S.span[k];
+    }
+    return off;
+}
+
+/* what the blob is checked against: the configuration the restoring program builds from its script */
+static uint64_t ckpt_fingerprint(const picles_ctx *c)
+{
+    uint64_t h = FP_SEED;
+    const picles_grid &g = c->g;
+    h = fp_val(h, g.Nx); h = fp_val(h, g.Ny); h = fp_val(h, g.dx); h = fp_val(h, g.dy);
+    h = fp_val(h, g.periodic_x); h = fp_val(h, g.periodic_y); h = fp_val(h, g.j_begin); h = fp_val(h, g.j_end);
+    const picles_phys &p = c->ph;
+    for (double v : {p.r_g, p.C_alpha, p.C_phi, p.C_e, p.g, p.gamma, p.q, p.c_beta, p.c_D, p.c_e, p.c_alpha, p.dir_deadband}) h = fp_val(h, v);
+    for (int32_t v : {p.propagation, p.input, p.dissipation, p.peak_shift, p.direction}) h = fp_val(h, v);
+    const picles_ode &o = c->od;
+    for (double v : {o.abstol, o.reltol, o.dt0, o.dtmin, o.log_energy_minimum, o.log_energy_maximum, o.wind_min_squared, o.timestep}) h = fp_val(h, v);
+    h = fp_val(h, o.force_dtmin); h = fp_val(h, o.solver); h = fp_val(h, o.maxiters);
+    const picles_model &m = c->md;
+    h = fp_val(h, m.periodic_boundary); h = fp_val(h, m.init_type);
+    for (int k = 0; k < 3; k++) h = fp_val(h, m.default_particle[k]);
+    for (int k = 0; k < 2; k++) h = fp_val(h, m.minimal_state[k]);
+    h = fp_bytes(h, c->h_mask.data(), c->h_mask.size());
+    h = fp_val(h, c->G.single_slab); h = fp_val(h, c->halo0);
+    h = fp_val(h, (int32_t)(c->A.m11 != nullptr)); h = fp_val(h, c->fp_metric);
+    h = fp_val(h, (int32_t)c->wind_grid_on);
+    if (c->wind_grid_on) {
+        const WindGrid &w = c->wg;
+        h = fp_val(h, c->wind_grid_mode); h = fp_val(h, w.nx); h = fp_val(h, w.ny); h = fp_val(h, w.nt);
+        for (double v : {w.x0, w.inv_dx, w.y0, w.inv_dy, c->wg_t0, c->wg_dt, w.mesh_x0, w.mesh_y0}) h = fp_val(h, v);
+        h = fp_val(h, c->fp_lattice);
+    }
+    return h;
+}
+
+/* the device snapshot (payload + two sum words) and its pinned host copy, allocated on first use; the copy-out rides on the store stream */
+static int ckpt_buffers(picles_ctx *c, unsigned long long payload)
+{
+    const size_t need = (size_t)payload + 16;
+    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    if (!c->ck_ready) {
+        HIPCHK(c, hipEventCreateWithFlags(&c->ck_ready, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ck_done, hipEventDisableTiming));
+    }
+    if (c->ck_cap >= need) return 0;
+    if (c->ck_dev) { HIPCHK(c, hipFree(c->ck_dev)); c->ck_dev = nullptr; }
+    if (c->ck_host) { HIPCHK(c, hipHostFree(c->ck_host)); c->ck_host = nullptr; }
+    c->ck_cap = 0;
+    HIPCHK(c, hipMalloc(&c->ck_dev, need));
+    HIPCHK(c, hipHostMalloc(&c->ck_host, need, hipHostMallocDefault));
+    c->ck_cap = need;
+    return 0;
+}
+
+static void ckpt_launch(picles_ctx *c, int mode, const CkptSegs &S, unsigned long long payload)
+{
+    unsigned long long maxch = 0;
+    for (int k = 0; k < CKPT_NSEG; k++) maxch = std::max(maxch, S.span[k] >> 4);
+    const unsigned gx = (unsigned)std::min<unsigned long long>((maxch + 255) / 256, 2048);
+    dim3 grid(gx ? gx : 1, CKPT_NSEG), block(256);
+    unsigned long long *sums = (unsigned long long *)(c->ck_dev + payload);
+    if (mode == 0) hipLaunchKernelGGL(k_ckpt<0>, grid, block, 0, c->stream, S, c->ck_dev, sums);
+    else if (mode == 1) hipLaunchKernelGGL(k_ckpt<1>, grid, block, 0, c->stream, S, c->ck_dev, sums);
+    else hipLaunchKernelGGL(k_ckpt<2>, grid, block, 0, c->stream, S, c->ck_dev, sums);
+}
+
+PX_EXPORT int32_t picles_checkpoint_size(picles_ctx *c, size_t *bytes)
+{
+    if (!c || !bytes) return -1;
+    CkptSegs S;
+    *bytes = sizeof(CkptHeader) + (size_t)ckpt_layout(c, S);
+    return 0;
+}
+
+PX_EXPORT int32_t picles_checkpoint_begin(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (c->ck_inflight) return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_begin: a checkpoint is in flight (picles_checkpoint_end first)");
+    if (!c->seeded) return fail(c, -2, "picles_checkpoint_begin: nothing to save (picles_seed or picles_checkpoint_load first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flush(c); if (rc) return rc; }          /* State at the step boundary: no step is left pending */
+    if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* an un-fused slab step leaves its scatter on the ring's stream M */
+    CkptSegs S;
+    const unsigned long long payload = ckpt_layout(c, S);
+    { int rc = ckpt_buffers(c, payload); if (rc) return rc; }
+    unsigned long long *sums = (unsigned long long *)(c->ck_dev + payload);
+    HIPCHK(c, hipMemsetAsync(sums, 0, 16, c->stream));
+    timing_begin(c, c->stream, 4);
+    ckpt_launch(c, 0, S, payload);
+    timing_end(c, c->stream);
+    HIPCHK(c, hipGetLastError());
+    /* stream-ordered behind the pack; the D2H leg runs beside whatever the caller enqueues next (as picles_store_push) */
+    HIPCHK(c, hipEventRecord(c->ck_ready, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->ck_ready, 0));
+    HIPCHK(c, hipMemcpyAsync(c->ck_host, c->ck_dev, (size_t)payload + 8, hipMemcpyDeviceToHost, c->store_stream));
+    HIPCHK(c, hipEventRecord(c->ck_done, c->store_stream));
+    CkptHeader h;
+    memset(&h, 0, sizeof h);
+    h.magic = CKPT_MAGIC; h.format = CKPT_FORMAT; h.abi = PICLES_ABI_VERSION;
+    h.header_bytes = sizeof(CkptHeader); h.payload_bytes = payload;
+    h.fingerprint = ckpt_fingerprint(c);
+    h.clock = c->clock;
+    h.halo_rows = c->G.R; h.mr_w = c->mr_w; h.cur = c->cur; h.nseg = CKPT_NSEG;
+    h.n = c->A.n;
+    for (int k = 0; k < CKPT_NSEG; k++) { h.seg_off[k] = S.off[k]; h.seg_len[k] = S.len[k]; }
+    h.step_dt = c->step_dt;
+    h.state_zero = c->state_zero ? 1 : 0;
+    memcpy(c->ck_hdr, &h, sizeof h);
+    c->ck_inflight = true;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_checkpoint_end(picles_ctx *c, void *buf, size_t bytes)
+{
+    if (!c) return -1;
+    if (!c->ck_inflight) return fail(c, -2, "picles_checkpoint_end: no checkpoint in flight (picles_checkpoint_begin first)");
+    CkptHeader h;
+    memcpy(&h, c->ck_hdr, sizeof h);
+    const size_t total = sizeof h + (size_t)h.payload_bytes;
+    if (!buf || bytes < total) {
+        char m[160];
+        snprintf(m, sizeof m, "picles_checkpoint_end: the blob needs %zu bytes, the buffer has %zu", total, buf ? bytes : (size_t)0);
+        return fail(c, PICLES_CKPT_E_SHORT, m);         /* (still in flight: call again with a large enough buffer) */
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(c->ck_done));
+    memcpy(&h.checksum, c->ck_host + h.payload_bytes, 8);
+    memcpy(buf, &h, sizeof h);
+    memcpy((unsigned char *)buf + sizeof h, c->ck_host, (size_t)h.payload_bytes);
+    c->ck_inflight = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t bytes)
+{
+    if (!c || !buf) return -1;
+    if (c->ck_inflight || c->store_count > 0)
+        return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_load: a checkpoint or store snapshot of this context is in flight (end / pop it first)");
+    CkptHeader h;
+    if (bytes < sizeof h) return fail(c, PICLES_CKPT_E_SHORT, "picles_checkpoint_load: buffer shorter than a checkpoint header");
+    memcpy(&h, buf, sizeof h);
+    if (h.magic != CKPT_MAGIC) return fail(c, PICLES_CKPT_E_MAGIC, "picles_checkpoint_load: not a checkpoint blob (bad magic)");
+    if (h.format != CKPT_FORMAT || h.abi != PICLES_ABI_VERSION || h.header_bytes != sizeof h) {
+        char m[200];
+        snprintf(m, sizeof m, "picles_checkpoint_load: blob format %u / ABI %u, this library reads format %d / ABI %d", h.format, h.abi,
+                 CKPT_FORMAT, PICLES_ABI_VERSION);
+        return fail(c, PICLES_CKPT_E_VERSION, m);
+    }
+    if (bytes - sizeof h < h.payload_bytes) {
+        char m[200];
+        snprintf(m, sizeof m, "picles_checkpoint_load: truncated blob (%zu payload bytes of %llu)", bytes - sizeof h, (unsigned long long)h.payload_bytes);
+        return fail(c, PICLES_CKPT_E_SHORT, m);
+    }
+    CkptSegs S;
+    const unsigned long long payload = ckpt_layout(c, S);
+    bool same = h.fingerprint == ckpt_fingerprint(c) && h.payload_bytes == payload && h.n == c->A.n && h.nseg == CKPT_NSEG;
+    for (int k = 0; same && k < CKPT_NSEG; k++) same = h.seg_off[k] == S.off[k] && h.seg_len[k] == S.len[k];
+    if (!same) return fail(c, PICLES_CKPT_E_CONFIG, "picles_checkpoint_load: the blob was written by a model of another configuration "
+                                                    "(grid, mask, physics, ODE settings, metric, wind lattice, slab rows or slab mode differ)");
+    const GridP &G = c->G;
+    const int R = h.halo_rows;
+    if (R < 1 || R > 1024 || (!G.single_slab && ((G.periodic_y && G.Ny <= 2 * R) || G.ny_loc < R)) || h.mr_w < 0 || h.mr_w > 4 || (h.cur & ~1))
+        return fail(c, PICLES_CKPT_E_CONFIG, "picles_checkpoint_load: the blob's halo rows / counter indices do not fit this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = ckpt_buffers(c, payload); if (rc) return rc; }
+    /* verify on the device before anything of the context is touched: the snapshot buffer is scratch */
+    unsigned long long *sums = (unsigned long long *)(c->ck_dev + payload);
+    const unsigned long long want[2] = {0ull, (unsigned long long)h.checksum};
+    HIPCHK(c, hipMemcpyAsync(c->ck_dev, (const unsigned char *)buf + sizeof h, (size_t)payload, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums, want, 16, hipMemcpyHostToDevice, c->stream));
+    ckpt_launch(c, 1, S, payload);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long got = 0;
+    HIPCHK(c, hipMemcpyAsync(&got, sums, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (got != h.checksum) return fail(c, PICLES_CKPT_E_CHECKSUM, "picles_checkpoint_load: payload checksum mismatch (the blob is damaged)");
+    /* commit: a step still pending is superseded (everything it would write is replaced) */
+    HIPCHK(c, hipDeviceSynchronize());
+    c->pending = false;
+    if (R != G.R) { int rc = picles_set_halo_rows(c, R); if (rc) return rc; }
+    ckpt_launch(c, 2, S, payload);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->clock = h.clock;
+    c->step_dt = h.step_dt;
+    c->pend_t = h.clock; c->pend_dt = h.step_dt;
+    c->mr_w = h.mr_w;
+    c->cur = h.cur;
+    c->state_zero = h.state_zero != 0;
+    c->seeded = true;
+    c->edge_pending = false;
+    c->step_fresh = false;
+    c->ord_valid = false;     /* the dispatch order is scheduling only: the first fused step after a load runs in natural order */
+    c->wind_t1_valid = false; /* a lattice window is sampled afresh (the same bits: the sampler is a function of the time alone) */
     return 0;
 }

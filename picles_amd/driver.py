@@ -316,6 +316,33 @@ class HipModel:
     def store_pending(self):
         return self.lib.picles_store_pending(self.h)
 
+    # ---- exact restart (picles_checkpoint_*) ----
+    def checkpoint_size(self) -> int:
+        n = C.c_size_t()
+        self._ck(self.lib.picles_checkpoint_size(self.h, C.byref(n)), "picles_checkpoint_size")
+        return n.value
+
+    def checkpoint_begin(self):
+        """snapshot the model at the current step boundary; the copy to the host runs beside the steps enqueued next"""
+        self._ck(self.lib.picles_checkpoint_begin(self.h), "picles_checkpoint_begin")
+
+    def checkpoint_end(self) -> np.ndarray:
+        """wait for the snapshot of checkpoint_begin: the blob (uint8 array)"""
+        buf = np.empty(self.checkpoint_size(), dtype=np.uint8)
+        self._ck(self.lib.picles_checkpoint_end(self.h, buf.ctypes.data, buf.size), "picles_checkpoint_end")
+        return buf
+
+    def checkpoint_load(self, blob):
+        """load a blob written by a model of the same configuration; raises CheckpointError (its .code says why) and leaves the
+        model unchanged on a refusal"""
+        a = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+        # (State is replaced too: the model layer resets its lazy view after a load — checkpointing.load_checkpoint — as after a step)
+        self.gen += 1
+        rc = self.lib.picles_checkpoint_load(self.h, a.ctypes.data if a.size else None, a.size)
+        if rc != 0:
+            msg = self.lib.picles_last_error(self.h)
+            raise K.CheckpointError(rc, f"picles_checkpoint_load failed (rc={rc}): {msg.decode() if msg else '?'}")
+
     def get_particles(self):
         z = np.empty(5 * self.N)
         on = np.empty(self.N, dtype=np.uint8)

@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(4)
+const PICLES_ABI_VERSION = Int32(5)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -389,6 +389,55 @@ function run_stored!(model::WaveGrowth2DHIP, Δt::Float64, n_steps::Integer, sin
     after_step!(model.State)
     check_dropped(model)
     nothing
+end
+
+"""
+    checkpoint!(model, path; iteration = model.clock.iteration)
+
+Exact-restart file of the model at its current step boundary (`picles_checkpoint_begin` + `picles_checkpoint_end`: the library's
+blob, DESIGN.md §11) with the clock, in the layout of picles_amd/checkpointing.py: 8 bytes "PICLESCF" | UInt32 1 | Int32 -1 |
+Int64 iteration | Float64 time | UInt64 blob bytes | blob.  Written to a temporary name, fsync'ed and renamed.
+The reference accepts `run!(sim; pickup = true)` and ignores it (run.jl:36); `pickup!` is what that keyword means in Oceananigans.
+"""
+function checkpoint!(model::WaveGrowth2DHIP, path::AbstractString; iteration::Integer = model.clock.iteration)
+    n = Ref{Csize_t}(0)
+    check(model.ctx, ccall((:picles_checkpoint_size, libpicles), Int32, (Ptr{Cvoid}, Ref{Csize_t}), model.ctx, n), "picles_checkpoint_size")
+    blob = Vector{UInt8}(undef, n[])
+    check(model.ctx, ccall((:picles_checkpoint_begin, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_checkpoint_begin")
+    check(model.ctx, ccall((:picles_checkpoint_end, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), model.ctx, blob, n[]),
+          "picles_checkpoint_end")
+    tmp = joinpath(dirname(abspath(path)), "." * basename(path) * ".tmp-$(getpid())")
+    open(tmp, "w") do io
+        write(io, b"PICLESCF", htol(UInt32(1)), htol(Int32(-1)), htol(Int64(iteration)), htol(Float64(model.clock.time)),
+              htol(UInt64(length(blob))), blob)
+        flush(io)
+        ccall(:fsync, Cint, (Cint,), Base.Libc.fd(io))
+    end
+    mv(tmp, path; force = true)
+    path
+end
+
+"""
+    pickup!(model, path)
+
+Load a file of `checkpoint!` (or of picles_amd's Checkpointer) into a model built by the same script — grid, mask, physics,
+ODE settings, winds — and restore its clock; the library refuses a file of another configuration, a truncated or damaged one.
+"""
+function pickup!(model::WaveGrowth2DHIP, path::AbstractString)
+    raw = read(path)
+    length(raw) >= 40 && raw[1:8] == b"PICLESCF" || error("$path: not a checkpoint file")
+    iteration = ltoh(reinterpret(Int64, raw[17:24])[1])
+    time = ltoh(reinterpret(Float64, raw[25:32])[1])
+    nblob = ltoh(reinterpret(UInt64, raw[33:40])[1])
+    length(raw) - 40 == nblob || error("$path: truncated checkpoint file")
+    upload_winds!(model, time, model.ODEsettings.timestep)      # the wind source the blob's fingerprint covers
+    blob = raw[41:end]
+    check(model.ctx, ccall((:picles_checkpoint_load, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), model.ctx, blob, length(blob)),
+          "picles_checkpoint_load")
+    model.clock.time = time
+    model.clock.iteration = iteration
+    after_step!(model.State)
+    model
 end
 
 end # module

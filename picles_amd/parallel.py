@@ -457,6 +457,46 @@ class SlabModel:
             return have + 1
         return have
 
+    # ---- exact restart: each rank saves and loads its own rows (picles_checkpoint_*; same world size and rows required) ----
+    def checkpoint_begin(self):
+        """snapshot this rank's rows at the current step boundary; the copy-out runs beside the steps enqueued next"""
+        self.sync()
+        self.backend.checkpoint_begin()
+
+    def checkpoint_end(self):
+        return self.backend.checkpoint_end()
+
+    def checkpoint_load(self, blob, clock: float):
+        """load this rank's blob (halo rows grown during the run come back with it; every rank grew them together)"""
+        from .wind_emulator import GriddedWinds
+        if self.static or isinstance(self.winds, GriddedWinds):
+            self.upload_winds(float(clock), self.timestep)   # the wind source the blob's fingerprint covers (lattice) / static winds
+        self.sync()
+        self.backend.checkpoint_load(blob)
+        self.clock = float(clock)
+        if self.ex is not None and hasattr(self.ex, "rebind"):
+            self.ex.rebind()
+
+    def save_checkpoint(self, dir, iteration: int, prefix: str = "checkpoint"):
+        """synchronous save into `{prefix}_iteration{i}_rank{r}.picles` (atomic write)"""
+        from .checkpointing import checkpoint_path, write_checkpoint_file
+        self.checkpoint_begin()
+        return write_checkpoint_file(checkpoint_path(dir, prefix, iteration, self.rank), self.checkpoint_end(), self.clock, iteration,
+                                     self.rank)
+
+    def load_checkpoint(self, path=None, dir=None, prefix: str = "checkpoint"):
+        """load `path`, or the latest iteration in `dir` that every rank has a file for; returns the iteration"""
+        from .checkpointing import latest_checkpoint, read_checkpoint_file
+        if path is None:
+            path = latest_checkpoint(dir, prefix, self.rank, self.world)
+            if path is None:
+                raise K.CheckpointError(0, f"rank {self.rank}: no checkpoint '{prefix}_iteration*_rank*.picles' in {dir} that all {self.world} ranks have")
+        blob, clock, iteration, rank = read_checkpoint_file(path)
+        if rank is not None and rank != self.rank:
+            raise K.CheckpointError(0, f"{path} belongs to rank {rank}, this is rank {self.rank}")
+        self.checkpoint_load(blob, clock)
+        return iteration
+
     def sync(self):
         self.backend.sync()
         if self.use_streams:

@@ -51,6 +51,7 @@ class Simulation:
         self.initialized = False
         self.verbose = verbose
         self.store = None
+        self.output_writers = {}      # Oceananigans' output_writers; run() drives a Checkpointer found here (picles_amd/checkpointing.py)
 
 
 def init_particles(model, defaults=None, verbose=False):
@@ -86,13 +87,24 @@ def reset_simulation(sim: Simulation):
 
 
 def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=False):
-    """run!(sim) (run.jl:36-122): note `stop_time >= clock.time`, i.e. one step past stop_time."""
+    """run!(sim) (run.jl:36-122): note `stop_time >= clock.time`, i.e. one step past stop_time.
+    pickup=True: continue from the latest file of the Checkpointer in sim.output_writers; pickup=<path>: from that file (the seeding of
+    initialize_simulation is skipped, the clock restored; the reference accepts the keyword and ignores it, run.jl:36).  A Checkpointer
+    in sim.output_writers writes a file every `schedule` iterations."""
     t0 = time.perf_counter_ns()
     if store and not isinstance(sim.store, (StateStore, NpyStateStore)):
         raise ValueError("call init_state_store(sim, path) before run(sim, store=True)")
     ring = store and hasattr(sim.model.backend, "store_init")
+    if pickup is not False and pickup is not None:
+        from .checkpointing import load_checkpoint, resolve_pickup
+        load_checkpoint(sim.model, resolve_pickup(sim, pickup), sim.Δt)
+        sim.initialized = True
     if not sim.initialized:
         initialize_simulation(sim)
+    from .checkpointing import find_checkpointer
+    ckpt = find_checkpointer(sim)
+    if ckpt is not None and not hasattr(sim.model.backend, "checkpoint_begin"):
+        raise NotImplementedError("a Checkpointer needs a backend with checkpoint_begin / checkpoint_end (the HIP library)")
     sim.run_wall_time = 0.0
     sim.running = sim.stop_time >= sim.model.clock.time
     if cash_store:
@@ -110,7 +122,21 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         # nothing observes State between the steps: enqueue the whole loop from C in one call
         import math
         n = int(math.floor((sim.stop_time - m.clock.time) / sim.Δt)) + 1 if sim.running else 0   # run.jl:113: one step past stop_time
-        if n > 0:
+        if n > 0 and ckpt is not None:
+            # chunks that end on the checkpoint iterations: the snapshot of chunk k is copied out and written while chunk k+1 runs
+            m.upload_winds(m.clock.time, sim.Δt)
+            time0, it0, done = m.clock.time, m.clock.iteration, 0
+            while done < n:
+                k = min(ckpt.schedule.next_after(it0 + done) - (it0 + done), n - done)
+                m.backend.run_steps(sim.Δt, k)
+                ckpt.finish(m.backend)
+                done += k
+                m.clock.time = time0 + done * sim.Δt
+                m.clock.iteration = it0 + done
+                if ckpt.schedule(m.clock.iteration):
+                    ckpt.begin(m.backend, m.clock.time, m.clock.iteration)
+            ckpt.finish(m.backend)
+        elif n > 0:
             m.upload_winds(m.clock.time, sim.Δt)
             m.backend.run_steps(sim.Δt, n)
             m.clock.time += n * sim.Δt
@@ -130,7 +156,13 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         if cash_store:
             sim.store.store.append(sim.model.State.copy())
             sim.store.iteration += 1
+        if ckpt is not None:
+            ckpt.finish(sim.model.backend)           # the previous step's snapshot: its copy-out ran beside this step
+            if ckpt.schedule(sim.model.clock.iteration):
+                ckpt.begin(sim.model.backend, sim.model.clock.time, sim.model.clock.iteration)
         sim.running = sim.stop_time >= sim.model.clock.time
+    if ckpt is not None:
+        ckpt.finish(sim.model.backend)
     if store:
         if ring:
             b = sim.model.backend
