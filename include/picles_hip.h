@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 5
+#define PICLES_ABI_VERSION 6
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -238,6 +238,71 @@ int32_t picles_store_push(picles_ctx *ctx);
 int32_t picles_store_pop(picles_ctx *ctx, double *state, double *time);
 int32_t picles_store_pending(const picles_ctx *ctx);
 
+/* ---- coarse wave diagnostics: Hs / Tp / group velocity planes and global sums, reduced on the device ----------------------
+ * What the reference's users derive from State on the host afterwards — Hs = 4 sqrt(e) (visualization/movie_2D.jl:49,162), the
+ * group-velocity vector of GetGroupVelocity (Operators/core_2D.jl:138-147) and PartitionOutput
+ * (examples/example_00_minimal_state_vector.jl:21-57), the peak frequency of c_g_conversions_vector (particle_waves_v5.jl:281-291),
+ * mean_of_state / max_energy / max_cgx / max_cgy (Operators/TimeSteppers.jl:15-29) — formed where the data is: one kernel pass
+ * over State writes coarsened float32 planes and one partial of seven doubles per tile, and a snapshot ring like the State ring
+ * carries them to the host while the next steps run.
+ *
+ * THE DEFINITION (this text is the contract; tests restate it in NumPy).
+ * Coarsening factors cx, cy, each 1 ... 16.  Coarse cell (I, J) covers the nodes i in [I cx, min((I+1) cx, Nx)),
+ * j in [J cy, min((J+1) cy, Ny)) in GLOBAL indices: Nxc = ceil(Nx / cx), Nyc = ceil(Ny / cy); tail cells are partial.  A context
+ * holds the coarse rows of its own node rows, nyc_loc = ceil((j_end - j_begin) / cy), and needs j_begin % cy == 0.
+ * A node is WET when e, m_x, m_y are finite, e > 0 and m2 = m_x m_x + m_y m_y > 0 (land and switched-off nodes hold zeros);
+ * this is read from State alone, not from the mask.
+ * Per coarse cell, in fp64, over the wet nodes in the fixed order j outer, i inner, every sum starting from +0.0:
+ *     n = count,  E = (Σ e) / n,  MX = (Σ m_x) / n,  MY = (Σ m_y) / n,  M2 = MX MX + MY MY
+ * (the conserved quantities are averaged; the derived ones follow from the averages).  The cell is VALID when n > 0 and M2 > 0.
+ * With g, r_g of the context's picles_phys, every operation one correctly rounded IEEE operation in the order written (no
+ * contraction into fused multiply-adds):
+ *     hs   = 4.0 * sqrt(E)
+ *     cg_x = (MX * E) / (2.0 * M2)          cg_y = (MY * E) / (2.0 * M2)
+ *     cbar = E / (2.0 * sqrt(M2))
+ *     tp   = (FOUR_PI * fmax(cbar / r_g, 0.1)) / g          FOUR_PI = 12.566370614359172 (4 M_PI as a double)
+ * (The reference forms m_amp = sqrt(m2) and squares it again; here M2 is used directly.  The planes are therefore NOT
+ * bit-compatible with the Julia expressions, and do not need to be: they agree to rounding.)
+ * Each field selected in the bit mask is one plane of Nxc x nyc_loc float32 — the fp64 value rounded to nearest even —
+ * column-major [I + Nxc J], planes in ascending bit order; a cell that is not valid holds a quiet NaN in every plane.
+ *
+ * Scalars, per TILE: a tile is PICLES_DIAG_TILE = 256 consecutive coarse columns I in [256 T, 256 T + 256) of one coarse row J;
+ * tiles_per_row = ceil(Nxc / 256), n_partials = nyc_loc * tiles_per_row, partial index = J_loc * tiles_per_row + T.  A partial is
+ * seven doubles: [sum_e, sum_mx, sum_my, n_wet, max_e, max_mx, max_my].  Lane l = 0 ... 255 of a tile holds the cell
+ * I = 256 T + l: its Σ e, Σ m_x, Σ m_y and n as above (before the division; +0.0 where I >= Nxc) and the maxima of the three planes
+ * over ALL nodes of the cell, wet or not (fmax from -inf: a NaN is skipped; -inf where I >= Nxc).  The reduction tree, the same
+ * for the four sums with + and the three maxima with fmax:
+ *     inside each group of 64 lanes w = 0 ... 3 (lanes 64 w ... 64 w + 63), for s = 32, 16, 8, 4, 2, 1:  v[l] = v[l] + v[l + s]
+ *     for l < s (l counted inside the group);  the tile's value is ((v0 + v1) + v2) + v3 of the four groups' v[0].
+ * A maximum that is a zero is stored as +0.0 (x + 0.0 is applied to the three maxima of the partial).  The host combines the
+ * partials sequentially in ascending (J, T) order from +0.0 / -inf; over several slabs in rank order, J ascending — a slab whose
+ * j_begin is a multiple of cy produces exactly the tiles of the whole grid, so the totals are the same bit for bit whatever the
+ * decomposition, and no floating-point atomic is involved.  mean_of_state = sum_e / (Nx Ny) (TimeSteppers.jl:15-19).
+ *
+ *   init:    refuses factors outside 1..16, an empty or unknown field mask, n_slots < 1, a second init, a slab with j_begin % cy != 0
+ *   shape:   coarse shape, number of selected planes and partials, bytes of the field block (4 Nxc nyc_loc n_fields); no device work
+ *   push:    completes a pending fused step as picles_store_push does, launches the kernel on the context stream into the slot's
+ *            device buffer and starts the asynchronous copy into pinned host memory on the store stream: steps enqueued after it
+ *            overlap the copy.  Refuses: not initialised, ring full
+ *   pop:     waits for the OLDEST snapshot: fields (bytes of picles_diag_shape; float32 planes), partials (n_partials * 7 doubles,
+ *            may be NULL), its model time (may be NULL).  Refuses: none pending
+ *   pending: snapshots pushed and not yet popped
+ * picles_destroy frees the ring; picles_checkpoint_load / begin treat a diagnostics snapshot in flight like a store snapshot. */
+#define PICLES_DIAG_HS    1
+#define PICLES_DIAG_TP    2
+#define PICLES_DIAG_CG_X  4
+#define PICLES_DIAG_CG_Y  8
+#define PICLES_DIAG_E    16
+#define PICLES_DIAG_MX   32
+#define PICLES_DIAG_MY   64
+#define PICLES_DIAG_ALL 127
+#define PICLES_DIAG_TILE 256
+int32_t picles_diag_init(picles_ctx *ctx, int32_t cx, int32_t cy, int32_t field_mask, int32_t n_slots);
+int32_t picles_diag_shape(const picles_ctx *ctx, int32_t *nxc, int32_t *nyc_loc, int32_t *n_fields, int32_t *n_partials, size_t *bytes);
+int32_t picles_diag_push(picles_ctx *ctx);
+int32_t picles_diag_pop(picles_ctx *ctx, void *fields, double *partials, double *time);
+int32_t picles_diag_pending(const picles_ctx *ctx);
+
 /* particles (own rows; z is 5 planes: lne, c̄x, c̄y, x, y). Any pointer may be NULL.
  * The state vector of a switched-off particle (on == 0) is dead storage: its content is unspecified. */
 int32_t picles_get_particles(picles_ctx *ctx, double *z, uint8_t *on, uint8_t *boundary,
@@ -352,7 +417,7 @@ int32_t picles_slab_get_phases(picles_ctx *ctx, picles_slab_phases *out);
 #define PICLES_CKPT_E_VERSION  -22   /* another blob format or ABI version                                            */
 #define PICLES_CKPT_E_CONFIG   -23   /* fingerprint mismatch: the context was not built from the same configuration   */
 #define PICLES_CKPT_E_CHECKSUM -24   /* the payload's checksum does not match                                         */
-#define PICLES_CKPT_E_BUSY     -25   /* a store snapshot or checkpoint of this context is in flight (load), or a checkpoint is (begin) */
+#define PICLES_CKPT_E_BUSY     -25   /* a store / diagnostics snapshot or checkpoint of this context is in flight (load), or a checkpoint is (begin) */
 int32_t picles_checkpoint_size(picles_ctx *ctx, size_t *bytes);
 int32_t picles_checkpoint_begin(picles_ctx *ctx);
 int32_t picles_checkpoint_end(picles_ctx *ctx, void *buf, size_t bytes);

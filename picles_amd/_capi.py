@@ -101,7 +101,7 @@ LATTICE_LINEAR, LATTICE_SMOOTH3 = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 5
+ABI_VERSION = 6
 SLAB_ID_BYTES = 128
 
 ROWS_ALL, ROWS_EDGE, ROWS_INTERIOR = 0, 1, 2
@@ -111,6 +111,12 @@ CKPT_E_SHORT, CKPT_E_MAGIC, CKPT_E_VERSION, CKPT_E_CONFIG, CKPT_E_CHECKSUM, CKPT
 CKPT_MAGIC = 0x31544b4353454c43
 CKPT_HEADER_BYTES = 256
 CKPT_SEGMENTS = ("state", "z", "qold", "dtn", "asw", "status", "on", "pflags", "counters", "reach_maps")
+
+# coarse wave diagnostics (picles_diag_*): field bits in plane order, and the seven doubles of a tile partial
+DIAG_FIELDS = ("hs", "tp", "cg_x", "cg_y", "e", "m_x", "m_y")
+DIAG_BITS = {name: 1 << k for k, name in enumerate(DIAG_FIELDS)}
+DIAG_TILE = 256
+DIAG_PARTIAL = ("sum_e", "sum_mx", "sum_my", "n_wet", "max_e", "max_mx", "max_my")
 
 ST_STEPPED, ST_MAXITERS, ST_RESEED_NAN, ST_RESEED_INF = 1, 2, 4, 8
 ST_CLAMPED, ST_SWITCHED_ON, ST_DTMIN, ST_NONFINITE = 16, 32, 64, 128
@@ -151,6 +157,11 @@ SYMBOLS = {
     "picles_store_push": (C.c_int32, [_VP]),
     "picles_store_pop": (C.c_int32, [_VP, c_double_p, c_double_p]),
     "picles_store_pending": (C.c_int32, [_VP]),
+    "picles_diag_init": (C.c_int32, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "picles_diag_shape": (C.c_int32, [_VP, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_size_t)]),
+    "picles_diag_push": (C.c_int32, [_VP]),
+    "picles_diag_pop": (C.c_int32, [_VP, _VP, c_double_p, c_double_p]),
+    "picles_diag_pending": (C.c_int32, [_VP]),
     "picles_get_particles": (C.c_int32, [_VP, c_double_p, c_uint8_p, c_uint8_p, c_int32_p]),
     "picles_set_particles": (C.c_int32, [_VP, c_double_p, c_uint8_p]),
     "picles_get_counters": (C.c_int32, [_VP, C.POINTER(PiclesCounters)]),

@@ -33,6 +33,8 @@
  *                    one global fp64 atomic per touched tile node. HBM/atomic bound.
  *   k_remesh         stand-alone NodeToParticle! (split API).
  *   k_ckpt           checkpoint payload: packs / verifies / unpacks the planes of a restart blob in one pass. HBM bound.
+ *   k_diag           (k_diag.h) coarse wave diagnostics: float32 Hs / Tp / cg planes + one partial of sums and maxima per tile of
+ *                    256 coarse cells, one pass over State. HBM bound.
  */
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -53,6 +55,7 @@
 #define PX_EXPORT extern "C" __attribute__((visibility("default")))
 
 #include "kernels.h"
+#include "k_diag.h"
 
 /* ------------------------------------------------------------------------------------------
  * k_seed — init_particles! / SeedParticle / InitParticleValues / init_z0_to_State!
@@ -493,6 +496,14 @@ struct picles_ctx {
     std::vector<hipEvent_t> store_ready, store_done;
     std::vector<double> store_time;
     hipStream_t store_stream = nullptr;
+    /* coarse diagnostics ring (picles_diag_*): a slot is the float32 planes followed by the tile partials */
+    int diag_slots = 0, diag_head = 0, diag_count = 0;
+    DiagP diag{};
+    int diag_nfields = 0, diag_npart = 0;
+    size_t diag_field_bytes = 0, diag_part_off = 0, diag_slot_bytes = 0;
+    std::vector<unsigned char *> diag_dev, diag_host;
+    std::vector<hipEvent_t> diag_ready, diag_done;
+    std::vector<double> diag_time;
     /* gridded winds */
     bool wind_grid_on = false;
     WindGrid wg{};
@@ -817,6 +828,10 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     for (auto p : c->store_host) hipHostFree(p);
     for (auto e : c->store_ready) hipEventDestroy(e);
     for (auto e : c->store_done) hipEventDestroy(e);
+    for (auto p : c->diag_dev) hipFree(p);
+    for (auto p : c->diag_host) hipHostFree(p);
+    for (auto e : c->diag_ready) hipEventDestroy(e);
+    for (auto e : c->diag_done) hipEventDestroy(e);
     if (c->ck_dev) hipFree(c->ck_dev);
     if (c->ck_host) hipHostFree(c->ck_host);
     if (c->ck_ready) hipEventDestroy(c->ck_ready);
@@ -1790,6 +1805,108 @@ PX_EXPORT int32_t picles_store_pop(picles_ctx *c, double *state, double *time)
     return 0;
 }
 
+/* ---- coarse diagnostics ring (the definition: include/picles_hip.h; the kernel: k_diag.h) ---- */
+PX_EXPORT int32_t picles_diag_init(picles_ctx *c, int32_t cx, int32_t cy, int32_t field_mask, int32_t n_slots)
+{
+    if (!c) return -1;
+    if (cx < 1 || cx > 16 || cy < 1 || cy > 16) return fail(c, -2, "picles_diag_init: coarsening factors must be 1 ... 16");
+    if (field_mask <= 0 || (field_mask & ~PICLES_DIAG_ALL)) return fail(c, -2, "picles_diag_init: empty or unknown field mask");
+    if (n_slots < 1) return fail(c, -2, "picles_diag_init: n_slots must be >= 1");
+    if (c->diag_slots) return fail(c, -2, "picles_diag_init: diagnostics already initialised");
+    if (c->G.j_begin % cy != 0) return fail(c, -2, "picles_diag_init: the slab's j_begin must be a multiple of cy (coarse cells are global)");
+    HIPCHK(c, hipSetDevice(c->device));
+    DiagP D{};
+    D.Nx = c->G.Nx; D.ny_loc = c->G.ny_loc; D.cx = cx; D.cy = cy;
+    D.Nxc = (c->G.Nx + cx - 1) / cx; D.nyc_loc = (c->G.ny_loc + cy - 1) / cy;
+    D.tiles_per_row = (D.Nxc + DIAG_TILE - 1) / DIAG_TILE;
+    D.mask = (unsigned)field_mask; D.g = c->ph.g; D.r_g = c->ph.r_g; D.plane = c->A.n;
+    const int nf = __builtin_popcount((unsigned)field_mask), np = D.nyc_loc * D.tiles_per_row;
+    const size_t fb = (size_t)4 * D.Nxc * D.nyc_loc * nf, po = (fb + 15) & ~(size_t)15, sb = po + (size_t)np * 7 * 8;
+    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    for (int k = 0; k < n_slots; k++) {
+        unsigned char *d = nullptr, *h = nullptr;
+        hipEvent_t e1, e2;
+        HIPCHK(c, hipMalloc(&d, sb));
+        c->diag_dev.push_back(d);
+        HIPCHK(c, hipHostMalloc(&h, sb, hipHostMallocDefault));
+        c->diag_host.push_back(h);
+        HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
+        c->diag_ready.push_back(e1);
+        HIPCHK(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
+        c->diag_done.push_back(e2);
+    }
+    c->diag = D; c->diag_nfields = nf; c->diag_npart = np;
+    c->diag_field_bytes = fb; c->diag_part_off = po; c->diag_slot_bytes = sb;
+    c->diag_time.assign(n_slots, 0.0);
+    c->diag_slots = n_slots; c->diag_head = 0; c->diag_count = 0;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_diag_shape(const picles_ctx *c, int32_t *nxc, int32_t *nyc_loc, int32_t *n_fields, int32_t *n_partials, size_t *bytes)
+{
+    if (!c || !c->diag_slots) return -1;
+    if (nxc) *nxc = c->diag.Nxc;
+    if (nyc_loc) *nyc_loc = c->diag.nyc_loc;
+    if (n_fields) *n_fields = c->diag_nfields;
+    if (n_partials) *n_partials = c->diag_npart;
+    if (bytes) *bytes = c->diag_field_bytes;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_diag_pending(const picles_ctx *c) { return c ? c->diag_count : -1; }
+
+template <int CX, bool VEC>
+static void diag_launch(picles_ctx *c, unsigned char *slot)
+{
+    hipLaunchKernelGGL((k_diag<CX, VEC>), dim3((unsigned)c->diag_npart), dim3(DIAG_TILE), 0, c->stream, c->diag, (const double *)c->A.state,
+                       (float *)slot, (double *)(slot + c->diag_part_off));
+}
+
+PX_EXPORT int32_t picles_diag_push(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->diag_slots) return fail(c, -2, "picles_diag_init first");
+    if (c->diag_count == c->diag_slots) return fail(c, -3, "diagnostics ring full: pop first");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flush(c); if (rc) return rc; }
+    if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* an un-fused slab step leaves its scatter on the ring's stream M */
+    const int slot = (c->diag_head + c->diag_count) % c->diag_slots;
+    unsigned char *d = c->diag_dev[slot];
+    const bool vec = (c->diag.Nx & 1) == 0;                  /* every cell's row segment then starts on a 16-byte boundary */
+    timing_begin(c, c->stream, 4);
+    switch (c->diag.cx) {
+    case 1: diag_launch<1, false>(c, d); break;
+    case 2: if (vec) diag_launch<2, true>(c, d); else diag_launch<2, false>(c, d); break;
+    case 4: if (vec) diag_launch<4, true>(c, d); else diag_launch<4, false>(c, d); break;
+    default: diag_launch<0, false>(c, d);
+    }
+    timing_end(c, c->stream);
+    HIPCHK(c, hipGetLastError());
+    /* stream-ordered behind the step that produced State; the D2H leg runs beside the next steps */
+    HIPCHK(c, hipEventRecord(c->diag_ready[slot], c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->diag_ready[slot], 0));
+    HIPCHK(c, hipMemcpyAsync(c->diag_host[slot], d, c->diag_slot_bytes, hipMemcpyDeviceToHost, c->store_stream));
+    HIPCHK(c, hipEventRecord(c->diag_done[slot], c->store_stream));
+    c->diag_time[slot] = c->clock;
+    c->diag_count++;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_diag_pop(picles_ctx *c, void *fields, double *partials, double *time)
+{
+    if (!c || !fields) return -1;
+    if (!c->diag_count) return fail(c, -3, "no diagnostics snapshot pending");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int slot = c->diag_head;
+    HIPCHK(c, hipEventSynchronize(c->diag_done[slot]));
+    memcpy(fields, c->diag_host[slot], c->diag_field_bytes);
+    if (partials) memcpy(partials, c->diag_host[slot] + c->diag_part_off, (size_t)c->diag_npart * 7 * 8);
+    if (time) *time = c->diag_time[slot];
+    c->diag_head = (c->diag_head + 1) % c->diag_slots;
+    c->diag_count--;
+    return 0;
+}
+
 /* ---- halo blocks ---- */
 PX_EXPORT int32_t picles_halo_rows(const picles_ctx *c) { return c ? c->G.R : -1; }
 
@@ -2442,7 +2559,7 @@ PX_EXPORT int32_t picles_checkpoint_end(picles_ctx *c, void *buf, size_t bytes)
 PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t bytes)
 {
     if (!c || !buf) return -1;
-    if (c->ck_inflight || c->store_count > 0)
+    if (c->ck_inflight || c->store_count > 0 || c->diag_count > 0)
         return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_load: a checkpoint or store snapshot of this context is in flight (end / pop it first)");
     CkptHeader h;
     if (bytes < sizeof h) return fail(c, PICLES_CKPT_E_SHORT, "picles_checkpoint_load: buffer shorter than a checkpoint header");

@@ -28,6 +28,43 @@ def _col(a, n):
     return a
 
 
+def diag_field_mask(fields) -> int:
+    """field names (or a ready bit mask) -> PICLES_DIAG_* bit mask"""
+    if isinstance(fields, (int, np.integer)):
+        return int(fields)
+    if isinstance(fields, str):
+        fields = (fields,)
+    unknown = [f for f in fields if f not in K.DIAG_BITS]
+    if unknown:
+        raise ValueError(f"unknown diagnostic fields {unknown}: choose from {K.DIAG_FIELDS}")
+    mask = 0
+    for f in fields:
+        mask |= K.DIAG_BITS[f]
+    return mask
+
+
+def combine_partials(list_of_partials, Nx, Ny) -> dict:
+    """the eight global scalars from the tile partials of picles_diag_pop — one [n_partials, 7] array, or a list of them in rank
+    order for a slab run: combined sequentially in ascending (J, tile) order, sums from +0.0 and maxima (fmax) from -inf, so the
+    result does not depend on the decomposition.  mean_of_state = sum_e / (Nx Ny) (TimeSteppers.jl:15-19)."""
+    if isinstance(list_of_partials, np.ndarray) and list_of_partials.ndim == 2:
+        list_of_partials = [list_of_partials]
+    acc = [0.0, 0.0, 0.0, 0.0, -np.inf, -np.inf, -np.inf]
+    for part in list_of_partials:
+        for row in np.asarray(part, dtype=np.float64).reshape(-1, 7).tolist():
+            for k in range(4):
+                acc[k] = acc[k] + row[k]
+            for k in range(4, 7):
+                b = row[k]
+                if b == b and (acc[k] != acc[k] or b > acc[k]):
+                    acc[k] = b
+    out = dict(zip(K.DIAG_PARTIAL, acc))
+    out["mean_of_state"] = out["sum_e"] / (float(Nx) * float(Ny))
+    return out
+
+
+SCALAR_NAMES = K.DIAG_PARTIAL + ("mean_of_state",)
+
 _live = weakref.WeakSet()
 
 
@@ -91,6 +128,8 @@ class HipModel:
         u0, v0 = _col(u0, self.N), _col(v0, self.N)
         if u1 is not None:
             u1, v1 = _col(u1, self.N), _col(v1, self.N)
+        if tk is not None and um is None:
+            raise ValueError("set_winds: tk names the time of the level (um, vm); it was given without one")
         if um is not None:
             um, vm = _col(um, self.N), _col(vm, self.N)
             if tk is not None:
@@ -315,6 +354,42 @@ class HipModel:
     @property
     def store_pending(self):
         return self.lib.picles_store_pending(self.h)
+
+    # ---- coarse wave diagnostics (picles_diag_*: Hs / Tp / group velocity planes + global sums, reduced on the device) ----
+    def diag_init(self, coarsen=(4, 4), fields=("hs", "tp", "cg_x", "cg_y"), n_slots=3):
+        """coarsen = (cx, cy), each 1 ... 16; fields: names out of _capi.DIAG_FIELDS (the planes come in that order, whatever the
+        order given here) or the bit mask itself"""
+        cx, cy = (coarsen, coarsen) if np.isscalar(coarsen) else coarsen
+        mask = diag_field_mask(fields)
+        self._ck(self.lib.picles_diag_init(self.h, int(cx), int(cy), mask, int(n_slots)), "picles_diag_init")
+        self.diag_fields = tuple(f for f in K.DIAG_FIELDS if mask & K.DIAG_BITS[f])
+        self.diag_coarsen = (int(cx), int(cy))
+
+    def diag_shape(self):
+        """(Nxc, nyc_loc, n_fields, n_partials, bytes of the float32 field block); no device work"""
+        a = [C.c_int32() for _ in range(4)]
+        b = C.c_size_t()
+        rc = self.lib.picles_diag_shape(self.h, *[C.byref(x) for x in a], C.byref(b))
+        if rc != 0:
+            raise K.PiclesError("picles_diag_shape failed: diag_init first")
+        return tuple(x.value for x in a) + (b.value,)
+
+    def diag_push(self):
+        self._ck(self.lib.picles_diag_push(self.h), "picles_diag_push")
+
+    def diag_pop(self):
+        """the oldest snapshot: (fields float32 [n_fields, Nxc, nyc_loc] — each plane Fortran-ordered, i.e. [I + Nxc J] in memory —,
+        partials float64 [n_partials, 7], model time)"""
+        nxc, nyc, nf, npart, _ = self.diag_shape()
+        f = np.empty(nf * nxc * nyc, dtype=np.float32)
+        p = np.empty((npart, 7))
+        t = C.c_double()
+        self._ck(self.lib.picles_diag_pop(self.h, f.ctypes.data, K.dptr(p), C.byref(t)), "picles_diag_pop")
+        return f.reshape((nf, nyc, nxc)).transpose(0, 2, 1), p, t.value
+
+    @property
+    def diag_pending(self):
+        return self.lib.picles_diag_pending(self.h)
 
     # ---- exact restart (picles_checkpoint_*) ----
     def checkpoint_size(self) -> int:

@@ -1,0 +1,212 @@
+"""FieldWriter: coarse wave fields (Hs, Tp, group velocity, ...) and global scalars on a schedule — the output a user of a wave
+model takes home, formed on the device (picles_diag_*, include/picles_hip.h) instead of from full State snapshots on the host.
+The reference derives the same quantities from `State` afterwards: Hs = 4 sqrt(e) (visualization/movie_2D.jl:49,162), the group
+velocity of GetGroupVelocity (Operators/core_2D.jl:138-147) / PartitionOutput (examples/example_00_minimal_state_vector.jl:21-57),
+mean_of_state and max_energy / max_cgx / max_cgy (Operators/TimeSteppers.jl:15-29).
+
+Attach like the Checkpointer: `sim.output_writers["fields"] = FieldWriter(model, schedule=10, path="out", coarsen=(4, 4))`.
+`run(sim)` then stays on the `picles_run_steps` path between outputs: a snapshot is pushed into the library's ring at every output
+iteration and popped — waited for and written — only when the ring is full or the run ends, so the copy to the host and the file
+write of output k run beside the steps that follow it.  The record of the run's first iteration (the seeded state) is written too,
+as `run(sim, store=True)` writes it.
+
+File, following the conventions of picles_amd/storing.py (HDF5 datasets are row-major, i.e. the reverse of the Julia order):
+
+    /waves/data           float32 (field, y, x, time)         NaN where a coarse cell holds no wet node
+    /waves/x, /waves/y    float64: mean coordinate of the nodes a coarse cell covers;  /waves/time float64
+    /waves/var_names      the fields, in plane order (a subset of hs, tp, cg_x, cg_y, e, m_x, m_y)
+    /waves/scalars        float64 (time, 8);  /waves/scalar_names = sum_e, sum_mx, sum_my, n_wet, max_e, max_mx, max_my, mean_of_state
+
+written as `<name>.h5` where a libhdf5 loads, else as `<name>.waves.data.npy` [time, x, y, field] + `<name>.waves.scalars.npy`
+[time, 8] + `<name>.json` (the same logical layout, like NpyStateStore).
+"""
+from __future__ import annotations
+
+import json
+from pathlib import Path
+
+import numpy as np
+
+from . import _capi as K
+from .checkpointing import IterationInterval
+from .driver import SCALAR_NAMES, combine_partials, diag_field_mask
+
+
+def coarse_coordinate(x, c: int):
+    """mean coordinate of the nodes each coarse cell covers (the last cell may cover fewer than c)"""
+    x = np.asarray(x, dtype=np.float64)
+    return np.array([x[k:k + c].mean() for k in range(0, len(x), c)])
+
+
+class NpyFieldStore:
+    format = "npy"
+
+    def __init__(self, path, name, time, x, y, var_names):
+        self.dir = Path(path)
+        self.dir.mkdir(parents=True, exist_ok=True)
+        self.shape = (len(time), len(x), len(y), len(var_names))
+        self.path = self.dir / f"{name}.waves.data.npy"
+        self.data = np.lib.format.open_memmap(self.path, mode="w+", dtype=np.float32, shape=self.shape)
+        self.scalars = np.lib.format.open_memmap(self.dir / f"{name}.waves.scalars.npy", mode="w+", dtype=np.float64,
+                                                 shape=(len(time), len(SCALAR_NAMES)))
+        self.data[:] = np.nan
+        self.scalars[:] = np.nan
+        self.json = self.dir / f"{name}.json"
+        self.meta = {"group": "waves", "dims": ["time", "x", "y", "field"], "var_names": list(var_names),
+                     "scalar_names": list(SCALAR_NAMES), "time": [float("nan")] * len(time), "x": list(map(float, x)),
+                     "y": list(map(float, y))}
+
+    def write(self, i, fields, scalars, time):
+        self.data[i] = np.moveaxis(fields, 0, -1)
+        self.scalars[i] = scalars
+        self.meta["time"][i] = float(time)
+
+    def close(self):
+        self.data.flush()
+        self.scalars.flush()
+        self.json.write_text(json.dumps(self.meta))
+
+
+class H5FieldStore:
+    """the HDF5 form, through the ctypes binding of picles_amd/storing.py"""
+
+    format = "hdf5"
+
+    def __init__(self, path, name, time, x, y, var_names):
+        from . import storing as S
+        L = self.L = S.hdf5()
+        self.S = S
+        self.dir = Path(path)
+        self.dir.mkdir(parents=True, exist_ok=True)
+        self.path = self.dir / f"{name}.h5"
+        if self.path.exists():
+            self.path.unlink()
+        self.f32 = S._hid.in_dll(L, "H5T_NATIVE_FLOAT_g").value
+        nt, nx, ny, nf = self.shape = (len(time), len(x), len(y), len(var_names))
+        self.file = S._ok(L.H5Fcreate(str(self.path).encode(), S._H5F_ACC_TRUNC, 0, 0), f"H5Fcreate({self.path})")
+        self.group = S._ok(L.H5Gcreate2(self.file, b"waves", 0, 0, 0), "H5Gcreate2(waves)")
+        self.fspace = S._ok(L.H5Screate_simple(4, S._dims((nf, ny, nx, nt)), None), "H5Screate_simple")
+        self.data = S._ok(L.H5Dcreate2(self.group, b"data", self.f32, self.fspace, 0, 0, 0), "H5Dcreate2(data)")
+        self.mspace = S._ok(L.H5Screate_simple(4, S._dims((nf, ny, nx, 1)), None), "H5Screate_simple")
+        full = np.full((nf, ny, nx, nt), np.nan, dtype=np.float32)
+        S._ok(L.H5Dwrite(self.data, self.f32, 0, 0, 0, full.ctypes.data), "H5Dwrite(data)")
+        S._write_strings(L, self.group, "dims", ["time", "x", "y", "field"], attribute=True)
+        S._write_f64(L, self.group, "x", x)
+        S._write_f64(L, self.group, "y", y)
+        S._write_strings(L, self.group, "var_names", list(var_names))
+        S._write_strings(L, self.group, "scalar_names", list(SCALAR_NAMES))
+        self.times = np.full(nt, np.nan)
+        self.scalars = np.full((nt, len(SCALAR_NAMES)), np.nan)
+
+    def write(self, i, fields, scalars, time):
+        L, S = self.L, self.S
+        nt, nx, ny, nf = self.shape
+        plane = np.ascontiguousarray(np.asarray(fields, dtype=np.float32).transpose(0, 2, 1))      # (field, y, x): a no-op for the planes as popped
+        S._ok(L.H5Sselect_hyperslab(self.fspace, S._H5S_SELECT_SET, S._dims((0, 0, 0, i)), None, S._dims((nf, ny, nx, 1)), None),
+              "H5Sselect_hyperslab")
+        S._ok(L.H5Dwrite(self.data, self.f32, self.mspace, self.fspace, 0, plane.ctypes.data), "H5Dwrite(data)")
+        self.scalars[i] = scalars
+        self.times[i] = time
+
+    def close(self):
+        if self.file is None:
+            return
+        L, S = self.L, self.S
+        S._write_f64(L, self.group, "time", self.times)
+        S._write_f64(L, self.group, "scalars", self.scalars)
+        L.H5Sclose(self.mspace); L.H5Sclose(self.fspace); L.H5Dclose(self.data); L.H5Gclose(self.group)
+        S._ok(L.H5Fclose(self.file), "H5Fclose")
+        self.file = None
+
+
+def make_field_store(path, name, time, x, y, var_names, format="auto"):
+    if format not in ("auto", "hdf5", "npy"):
+        raise ValueError(f"unknown field output format {format!r}")
+    if format != "npy":
+        try:
+            return H5FieldStore(path, name, time, x, y, var_names)
+        except OSError:
+            if format == "hdf5":
+                raise
+    return NpyFieldStore(path, name, time, x, y, var_names)
+
+
+class FieldWriter:
+    """FieldWriter(model, schedule=IterationInterval(N) | N, path=..., coarsen=(cx, cy), fields=("hs", "tp", "cg_x", "cg_y"))"""
+
+    def __init__(self, model=None, *, schedule=None, path=".", name="fields", coarsen=(4, 4), fields=("hs", "tp", "cg_x", "cg_y"),
+                 format="auto", slots=3):
+        if schedule is None:
+            raise ValueError("FieldWriter needs a schedule (IterationInterval(N) or N)")
+        self.model = model
+        self.schedule = schedule if isinstance(schedule, IterationInterval) else IterationInterval(int(schedule))
+        self.path, self.name, self.format = Path(path), name, format
+        self.coarsen = (int(coarsen), int(coarsen)) if np.isscalar(coarsen) else (int(coarsen[0]), int(coarsen[1]))
+        mask = diag_field_mask(fields)
+        self.fields = tuple(f for f in K.DIAG_FIELDS if mask & K.DIAG_BITS[f])      # plane order
+        self.slots = int(slots)
+        self.store = None
+        self.written = 0              # records in the file so far
+        self.iterations = []          # the iteration of every record pushed, in order
+        self._initialised = None      # the backend whose ring was set up
+
+    def records_of(self, it0: int, n_steps: int) -> int:
+        """records a run of n_steps from iteration it0 writes: the first iteration's and one per scheduled iteration after it"""
+        N = self.schedule.interval
+        return 1 + (it0 + n_steps) // N - it0 // N
+
+    def begin_run(self, model, n_steps: int):
+        """set the ring up (once per backend), open the file for this run and push the record of the current iteration"""
+        b = model.backend
+        if self._initialised is not b:
+            b.diag_init(self.coarsen, self.fields, self.slots)
+            self._initialised = b
+        g = model.grid
+        self.Nx, self.Ny = int(g.stats.Nx), int(g.stats.Ny)
+        nt = self.records_of(model.clock.iteration, n_steps)
+        x, y = coarse_coordinate(g.data.x[:, 0], self.coarsen[0]), coarse_coordinate(g.data.y[0, :], self.coarsen[1])
+        self.store = make_field_store(self.path, self.name, np.zeros(nt), x, y, self.fields, format=self.format)
+        self.written = 0
+        self.iterations = []
+        self.push(b, model.clock.iteration)
+
+    def push(self, backend, iteration: int):
+        """snapshot now; a full ring first gives up its oldest snapshot (waited for and written)"""
+        if backend.diag_pending >= self.slots:
+            self.drain(backend, 1)
+        backend.diag_push()
+        self.iterations.append(int(iteration))
+
+    def drain(self, backend, count=None):
+        """pop and write `count` snapshots (all that are pending when None)"""
+        while backend.diag_pending > 0 and (count is None or count > 0):
+            f, p, t = backend.diag_pop()
+            s = combine_partials([p], self.Nx, self.Ny)
+            self.store.write(self.written, f, [s[k] for k in SCALAR_NAMES], t)
+            self.written += 1
+            if count is not None:
+                count -= 1
+
+    def finish(self, backend):
+        """end of the run: write what is pending and close the file"""
+        if self.store is None:
+            return
+        self.drain(backend)
+        self.store.close()
+        self.last_store, self.store = self.store, None
+
+
+def find_field_writer(sim):
+    for w in getattr(sim, "output_writers", {}).values():
+        if isinstance(w, FieldWriter):
+            return w
+    return None
+
+
+def read_field_output(path, name="fields"):
+    """read the .npy + .json form back: dict with `data` [time, x, y, field], `scalars` [time, 8] and the side-car's entries"""
+    d = Path(path)
+    out = json.loads((d / f"{name}.json").read_text())
+    out["data"] = np.load(d / f"{name}.waves.data.npy")
+    out["scalars"] = np.load(d / f"{name}.waves.scalars.npy")
+    return out

@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(5)
+const PICLES_ABI_VERSION = Int32(6)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -384,6 +384,64 @@ function run_stored!(model::WaveGrowth2DHIP, Δt::Float64, n_steps::Integer, sin
         check(model.ctx, ccall((:picles_store_push, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_store_push")
     end
     while ccall((:picles_store_pending, libpicles), Int32, (Ptr{Cvoid},), model.ctx) > 0
+        drain_one()
+    end
+    after_step!(model.State)
+    check_dropped(model)
+    nothing
+end
+
+const DIAG_FIELDS = (:hs, :tp, :cg_x, :cg_y, :e, :m_x, :m_y)      # PICLES_DIAG_* bits in plane order
+
+"""
+    run_fields!(model, Δt, n_steps, sink!; every=10, coarsen=(4, 4), fields=(:hs, :tp, :cg_x, :cg_y), slots=3)
+
+The stepping loop of `run!` with coarse wave fields as its output instead of State snapshots: what `PartitionOutput`
+(examples/example_00_minimal_state_vector.jl:21-57), `GetGroupVelocity` (Operators/core_2D.jl:138-147) and `mean_of_state` /
+`max_energy` (Operators/TimeSteppers.jl:15-29) derive from State on the host is formed on the device (`picles_diag_*`, the
+definition is in include/picles_hip.h).  `picles_run_steps` enqueues `every` fused steps from C, `picles_diag_push` reduces State
+to float32 planes and tile partials and copies them to pinned host memory on a side stream while the next steps run;
+`sink!(i, planes::Array{Float32,3}, partials::Matrix{Float64}, t)` receives the snapshots in order, the first being the state the
+loop starts from: `planes[I, J, f]` with f in the order of `DIAG_FIELDS`, `partials[:, k]` the seven doubles
+(sum_e, sum_mx, sum_my, n_wet, max_e, max_mx, max_my) of tile k, to be summed / maximised sequentially in k.
+"""
+function run_fields!(model::WaveGrowth2DHIP, Δt::Float64, n_steps::Integer, sink!; every::Integer=10, coarsen=(4, 4),
+                     fields=(:hs, :tp, :cg_x, :cg_y), slots::Integer=3)
+    upload_winds!(model, model.clock.time, Δt)
+    model.winds_static || error("run_fields! needs winds the device can produce by itself (static winds or wind_lattice)")
+    mask = Int32(0)
+    for f in fields
+        k = findfirst(==(Symbol(f)), DIAG_FIELDS)
+        k === nothing && error("unknown diagnostic field $f")
+        mask |= Int32(1) << (k - 1)
+    end
+    check(model.ctx, ccall((:picles_diag_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Int32), model.ctx, coarsen[1], coarsen[2], mask, slots), "picles_diag_init")
+    nxc, nyc, nf, np = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    nbytes = Ref{Csize_t}(0)
+    ccall((:picles_diag_shape, libpicles), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Csize_t}), model.ctx, nxc, nyc, nf, np, nbytes) == 0 ||
+        error("picles_diag_shape failed")
+    planes = Array{Float32,3}(undef, nxc[], nyc[], nf[])
+    partials = Matrix{Float64}(undef, 7, np[])
+    t = Ref(0.0)
+    i = 1
+    drain_one() = begin
+        check(model.ctx, ccall((:picles_diag_pop, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}), model.ctx, planes, partials, t), "picles_diag_pop")
+        sink!(i, planes, partials, t[]); i += 1
+    end
+    check(model.ctx, ccall((:picles_diag_push, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_diag_push")
+    done = 0
+    while done < n_steps
+        k = min(every, n_steps - done)
+        check(model.ctx, ccall((:picles_run_steps, libpicles), Int32, (Ptr{Cvoid}, Float64, Int32), model.ctx, Δt, k), "picles_run_steps")
+        for _ in 1:k
+            PiCLES.Operators.TimeSteppers.tick!(model.clock, Δt)
+        end
+        done += k
+        k == every || break                       # a remainder shorter than `every` ends the run without an output
+        ccall((:picles_diag_pending, libpicles), Int32, (Ptr{Cvoid},), model.ctx) == slots && drain_one()
+        check(model.ctx, ccall((:picles_diag_push, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_diag_push")
+    end
+    while ccall((:picles_diag_pending, libpicles), Int32, (Ptr{Cvoid},), model.ctx) > 0
         drain_one()
     end
     after_step!(model.State)

@@ -507,6 +507,39 @@ class SlabModel:
         self.sync()
         return self.backend.get_state()
 
+    # ---- coarse wave diagnostics of this rank's rows (picles_diag_*; needs j_begin % cy == 0 on every rank) ----
+    def diag_init(self, coarsen=(4, 4), fields=("hs", "tp", "cg_x", "cg_y"), n_slots=3):
+        self.backend.diag_init(coarsen, fields, n_slots)
+
+    def diag_shape(self):
+        return self.backend.diag_shape()
+
+    def diag_push(self):
+        """snapshot the diagnostics of the current step boundary (collective in effect: every rank pushes at the same step)"""
+        self.sync()
+        self.backend.diag_push()
+
+    def diag_pop(self):
+        return self.backend.diag_pop()
+
+    @property
+    def diag_pending(self):
+        return self.backend.diag_pending
+
+    def gather_fields(self):
+        """pop this rank's oldest diagnostics snapshot and gather all ranks': (fields [n_fields, Nxc, Nyc] concatenated along y
+        in rank order, the eight global scalars formed from the rank-ordered partials, model time).  Coarse cells are global,
+        so both equal a single context's bit for bit."""
+        from .driver import combine_partials
+        f, p, t = self.backend.diag_pop()
+        Nx, Ny = int(self.grid.stats.Nx), int(self.grid.stats.Ny)
+        if self.world == 1:
+            return f, combine_partials([p], Nx, Ny), t
+        import torch.distributed as dist
+        parts = [None] * self.world
+        dist.all_gather_object(parts, (f, p))
+        return (np.concatenate([a for a, _ in parts], axis=2), combine_partials([b for _, b in parts], Nx, Ny), t)
+
     def gather_state(self):
         """all ranks' slabs concatenated along y (host; for tests)"""
         s = self.get_state()

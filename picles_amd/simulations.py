@@ -105,6 +105,10 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
     ckpt = find_checkpointer(sim)
     if ckpt is not None and not hasattr(sim.model.backend, "checkpoint_begin"):
         raise NotImplementedError("a Checkpointer needs a backend with checkpoint_begin / checkpoint_end (the HIP library)")
+    from .field_output import find_field_writer
+    fw = find_field_writer(sim)
+    if fw is not None and not hasattr(sim.model.backend, "diag_init"):
+        raise NotImplementedError("a FieldWriter needs a backend with diag_init / diag_push / diag_pop (the HIP library)")
     sim.run_wall_time = 0.0
     sim.running = sim.stop_time >= sim.model.clock.time
     if cash_store:
@@ -122,26 +126,40 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         # nothing observes State between the steps: enqueue the whole loop from C in one call
         import math
         n = int(math.floor((sim.stop_time - m.clock.time) / sim.Δt)) + 1 if sim.running else 0   # run.jl:113: one step past stop_time
-        if n > 0 and ckpt is not None:
-            # chunks that end on the checkpoint iterations: the snapshot of chunk k is copied out and written while chunk k+1 runs
+        if n > 0 and (ckpt is not None or fw is not None):
+            # chunks that end on the next output or checkpoint iteration, whichever is first: the snapshot of chunk k is copied
+            # out and written while chunk k+1 runs
             m.upload_winds(m.clock.time, sim.Δt)
             time0, it0, done = m.clock.time, m.clock.iteration, 0
+            if fw is not None:
+                fw.begin_run(m, n)                      # the record of the first iteration
             while done < n:
-                k = min(ckpt.schedule.next_after(it0 + done) - (it0 + done), n - done)
+                nxt = min(w.schedule.next_after(it0 + done) for w in (ckpt, fw) if w is not None)
+                k = min(nxt - (it0 + done), n - done)
                 m.backend.run_steps(sim.Δt, k)
-                ckpt.finish(m.backend)
+                if ckpt is not None:
+                    ckpt.finish(m.backend)
                 done += k
                 m.clock.time = time0 + done * sim.Δt
                 m.clock.iteration = it0 + done
-                if ckpt.schedule(m.clock.iteration):
+                if ckpt is not None and ckpt.schedule(m.clock.iteration):
                     ckpt.begin(m.backend, m.clock.time, m.clock.iteration)
-            ckpt.finish(m.backend)
+                if fw is not None and fw.schedule(m.clock.iteration):
+                    fw.push(m.backend, m.clock.iteration)
+            if ckpt is not None:
+                ckpt.finish(m.backend)
         elif n > 0:
             m.upload_winds(m.clock.time, sim.Δt)
             m.backend.run_steps(sim.Δt, n)
             m.clock.time += n * sim.Δt
             m.clock.iteration += n
         sim.running = False
+    if fw is not None and sim.running:
+        # the per-step loop (time-varying winds, stores): the writer needs the number of steps for the size of its file
+        import math
+        if sim.stop_time == float("inf"):
+            raise ValueError("a FieldWriter needs a finite stop_time (its file is sized for the run)")
+        fw.begin_run(sim.model, int(math.floor((sim.stop_time - sim.model.clock.time) / sim.Δt)) + 1)
     while sim.running:
         sim.model.State.fill(0.0)          # State .= 0 (run.jl:75-79): recorded by the lazy view, fused into the scatter's store
         time_step(sim.model, sim.Δt, debug=debug)
@@ -160,9 +178,13 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
             ckpt.finish(sim.model.backend)           # the previous step's snapshot: its copy-out ran beside this step
             if ckpt.schedule(sim.model.clock.iteration):
                 ckpt.begin(sim.model.backend, sim.model.clock.time, sim.model.clock.iteration)
+        if fw is not None and fw.schedule(sim.model.clock.iteration):
+            fw.push(sim.model.backend, sim.model.clock.iteration)
         sim.running = sim.stop_time >= sim.model.clock.time
     if ckpt is not None:
         ckpt.finish(sim.model.backend)
+    if fw is not None:
+        fw.finish(sim.model.backend)
     if store:
         if ring:
             b = sim.model.backend
