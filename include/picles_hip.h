@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 6
+#define PICLES_ABI_VERSION 7
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -302,6 +302,55 @@ int32_t picles_diag_shape(const picles_ctx *ctx, int32_t *nxc, int32_t *nyc_loc,
 int32_t picles_diag_push(picles_ctx *ctx);
 int32_t picles_diag_pop(picles_ctx *ctx, void *fields, double *partials, double *time);
 int32_t picles_diag_pending(const picles_ctx *ctx);
+
+/* ---- station probes: the State value of chosen nodes after every step, with the fused path kept --------------------------------
+ * Point output — the series of the sea state at buoys, platforms, validation points — is what the reference's scripts cut out of
+ * full cash_store snapshots (State[i, j, :] against time: tests/T04_2D_reg_test.jl and the B0x regressions).  Here a few thousand
+ * nodes are sampled on the device behind each step and carried to the host by a ring like the two above.
+ *
+ * THE CONTRACT (tests restate it).
+ * A context holds at most one probe set: n >= 1 nodes given by GLOBAL 0-based indices (i, j), 0 <= i < Nx and j_begin <= j < j_end
+ * (the context's own rows), as two planes ij[0 .. n) = i, ij[n .. 2n) = j like picles_scatter_particles.  Duplicates, land nodes
+ * and nodes on the grid's boundary are allowed.
+ * A SAMPLE is, for every node of the set in the order given, the three doubles (e, m_x, m_y) picles_get_state would return for
+ * that node if it were called at that moment — bit for bit — laid out as 3 planes of n doubles, [k][node], k = e, m_x, m_y.
+ * Taking a sample does NOT complete a pending fused step, does not synchronise the host, and leaves State, particles, counters,
+ * reach counters, dispatch order and clock untouched.  With a fused step pending the values are formed from that step's scatter
+ * records by the pull k_scatter would run for the node; otherwise (freshly seeded, after a step of the plain phases, after
+ * PICLES_STEP_MOVIE — then zeros, as picles_get_state shows —, PICLES_STEP_ATOMIC, picles_set_state, a checkpoint load) they
+ * are read from State.  A sample carries the model clock and s, the number of model steps the context has completed since
+ * picles_probe_init (a step completes in picles_end_fused_step or picles_scatter_remesh, whoever calls them).
+ *
+ * AUTOMATIC SAMPLING: picles_time_step, picles_run_steps and picles_slab_run_steps take a sample after every model step they
+ * complete (fused or plain, any flags) for which s >= first and (s - first) % every == 0; every >= 1, first >= 1 (a run picked up
+ * from a checkpoint continues the cadence of the run that wrote it through `first`).  The split-phase calls (picles_begin_step /
+ * advance_rows / scatter_remesh, picles_begin_fused_step / step_rows / end_fused_step) count steps and do not sample: their
+ * caller calls picles_probe_sample once the step's halo exchange has been delivered.
+ *
+ * RING: capacity samples in device memory and as many in pinned host memory; each sample is copied out asynchronously on the store
+ * stream behind an event, and the steps enqueued after it overlap the copy.  When a sample is due and capacity samples are
+ * un-popped, the step entry point refuses with PICLES_PROBE_E_FULL before it has changed anything (clock, particles and records
+ * as they were; the same call succeeds after a pop); picles_run_steps / picles_slab_run_steps (n) refuse up front when the n steps
+ * would overrun the ring, not half-way.  Nothing is dropped silently.
+ *
+ *   init:    refuses (context unchanged, picles_last_error set) n < 1, a node outside [0, Nx) x [j_begin, j_end), every < 1,
+ *            first < 1, capacity < 1, a second init without picles_probe_free
+ *   sample:  one sample now, on `stream` (NULL: the context stream) — the stream behind which the caller has ordered everything
+ *            the sample depends on: the seeded state, or the launches and the delivered halo of a split-phase step.
+ *            Refuses: no set, ring full (PICLES_PROBE_E_FULL)
+ *   pop:     waits for the OLDEST samples only and hands out min(max_samples, pending) of them, oldest first: values
+ *            (3 n doubles each), times and steps (one each; may be NULL), *n_out = their number.  Refuses: no set,
+ *            max_samples < 1, none pending (-3, as the other rings)
+ *   pending: samples taken and not yet popped;  shape: n, every, capacity (-1 without a set; no device work)
+ *   free:    drops the set — samples pending with it — so that a new one may be created; picles_destroy does it too
+ * picles_checkpoint_load with samples pending is PICLES_CKPT_E_BUSY; the probe set is no part of the blob or its fingerprint. */
+#define PICLES_PROBE_E_FULL -30
+int32_t picles_probe_init(picles_ctx *ctx, int32_t n, const int32_t *ij, int32_t every, int32_t first, int32_t capacity);
+int32_t picles_probe_sample(picles_ctx *ctx, void *stream);
+int32_t picles_probe_pop(picles_ctx *ctx, int32_t max_samples, double *values, double *times, int64_t *steps, int32_t *n_out);
+int32_t picles_probe_pending(const picles_ctx *ctx);
+int32_t picles_probe_shape(const picles_ctx *ctx, int32_t *n, int32_t *every, int32_t *capacity);
+int32_t picles_probe_free(picles_ctx *ctx);
 
 /* particles (own rows; z is 5 planes: lne, c̄x, c̄y, x, y). Any pointer may be NULL.
  * The state vector of a switched-off particle (on == 0) is dead storage: its content is unspecified. */

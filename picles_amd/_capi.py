@@ -101,8 +101,9 @@ LATTICE_LINEAR, LATTICE_SMOOTH3 = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 6
+ABI_VERSION = 7
 SLAB_ID_BYTES = 128
+PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
 
 ROWS_ALL, ROWS_EDGE, ROWS_INTERIOR = 0, 1, 2
 
@@ -162,6 +163,12 @@ SYMBOLS = {
     "picles_diag_push": (C.c_int32, [_VP]),
     "picles_diag_pop": (C.c_int32, [_VP, _VP, c_double_p, c_double_p]),
     "picles_diag_pending": (C.c_int32, [_VP]),
+    "picles_probe_init": (C.c_int32, [_VP, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32]),
+    "picles_probe_sample": (C.c_int32, [_VP, _VP]),
+    "picles_probe_pop": (C.c_int32, [_VP, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int64), c_int32_p]),
+    "picles_probe_pending": (C.c_int32, [_VP]),
+    "picles_probe_shape": (C.c_int32, [_VP, c_int32_p, c_int32_p, c_int32_p]),
+    "picles_probe_free": (C.c_int32, [_VP]),
     "picles_get_particles": (C.c_int32, [_VP, c_double_p, c_uint8_p, c_uint8_p, c_int32_p]),
     "picles_set_particles": (C.c_int32, [_VP, c_double_p, c_uint8_p]),
     "picles_get_counters": (C.c_int32, [_VP, C.POINTER(PiclesCounters)]),

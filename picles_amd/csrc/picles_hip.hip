@@ -56,6 +56,7 @@
 
 #include "kernels.h"
 #include "k_diag.h"
+#include "k_probe.h"
 
 /* ------------------------------------------------------------------------------------------
  * k_seed — init_particles! / SeedParticle / InitParticleValues / init_z0_to_State!
@@ -504,6 +505,15 @@ struct picles_ctx {
     std::vector<unsigned char *> diag_dev, diag_host;
     std::vector<hipEvent_t> diag_ready, diag_done;
     std::vector<double> diag_time;
+    /* station probes (picles_probe_*): the node list, a ring of probe_cap samples (3 planes of probe_n doubles each) on the device
+     * and in pinned host memory, and the step counter the cadence is counted in */
+    int probe_n = 0, probe_every = 1, probe_first = 1, probe_cap = 0, probe_head = 0, probe_count = 0;
+    long long probe_steps = 0;                     /* model steps completed since picles_probe_init */
+    int *probe_nodes = nullptr;                    /* device: i plane, then the LOCAL row plane */
+    double *probe_dev = nullptr, *probe_host = nullptr;
+    std::vector<hipEvent_t> probe_ready, probe_done;
+    std::vector<double> probe_time;
+    std::vector<long long> probe_step;
     /* gridded winds */
     bool wind_grid_on = false;
     WindGrid wg{};
@@ -606,6 +616,12 @@ static Arrays arrays_for(picles_ctx *c, int read_buf, int write_buf)
 }
 
 static int launch_scatter(picles_ctx *c, hipStream_t s, bool remesh);
+
+/* station probes (defined behind the diagnostics ring) */
+static int probe_room(picles_ctx *c, long long n_steps, const char *who);
+static int probe_take(picles_ctx *c, hipStream_t s);
+static bool probe_due(const picles_ctx *c, long long s);
+static void probe_release(picles_ctx *c);
 
 /* scatter + remesh of the last fused step, if still outstanding */
 static int flush(picles_ctx *c)
@@ -832,6 +848,7 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     for (auto p : c->diag_host) hipHostFree(p);
     for (auto e : c->diag_ready) hipEventDestroy(e);
     for (auto e : c->diag_done) hipEventDestroy(e);
+    probe_release(c);
     if (c->ck_dev) hipFree(c->ck_dev);
     if (c->ck_host) hipHostFree(c->ck_host);
     if (c->ck_ready) hipEventDestroy(c->ck_ready);
@@ -1477,6 +1494,7 @@ PX_EXPORT int32_t picles_end_fused_step(picles_ctx *c)
     c->state_zero = false;
     c->edge_pending = false;
     c->clock += c->step_dt;
+    c->probe_steps++;
     return 0;
 }
 
@@ -1533,14 +1551,12 @@ PX_EXPORT int32_t picles_scatter_remesh(picles_ctx *c, void *stream)
     int rc = launch_scatter(c, s, true);
     if (rc) return rc;
     c->clock += c->step_dt;
+    c->probe_steps++;
     return 0;
 }
 
-PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
+static int time_step_phases(picles_ctx *c, double dt, int32_t flags)
 {
-    if (!c) return -1;
-    if (!c->G.single_slab) return fail(c, -5, "picles_time_step needs the whole grid; slabs use begin_step/advance_rows/scatter_remesh");
-    if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     if (step_fusable(c, flags, dt)) {
         /* run!-style consecutive steps: one launch per step (k_step), the scatter + remesh of the
          * previous step ride along; the last one is flushed when somebody looks */
@@ -1556,9 +1572,24 @@ PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
     return picles_scatter_remesh(c, nullptr);
 }
 
+PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
+{
+    if (!c) return -1;
+    if (!c->G.single_slab) return fail(c, -5, "picles_time_step needs the whole grid; slabs use begin_step/advance_rows/scatter_remesh");
+    if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
+    { int rc = probe_room(c, 1, "picles_time_step"); if (rc) return rc; }      /* refused before anything has changed */
+    int rc = time_step_phases(c, dt, flags);
+    if (rc) return rc;
+    /* the sample of this step: directly behind its launch on the context stream.  The next step's launch reads the record buffer
+     * the probe reads and writes the other one: stream order is all the ordering there is */
+    if (c->probe_n && probe_due(c, c->probe_steps)) return probe_take(c, c->stream);
+    return 0;
+}
+
 PX_EXPORT int32_t picles_run_steps(picles_ctx *c, double dt, int32_t n_steps)
 {
     if (!c || n_steps < 0) return -1;
+    if (c->G.single_slab && dt > 0.0) { int rc = probe_room(c, n_steps, "picles_run_steps"); if (rc) return rc; }   /* up front, not half-way */
     const bool region = c->timing && c->timing_mode == 2 && n_steps > 0;
     if (region) {      /* one event pair around the whole call, on the stream the launches go to */
         HIPCHK(c, hipSetDevice(c->device));
@@ -1907,6 +1938,165 @@ PX_EXPORT int32_t picles_diag_pop(picles_ctx *c, void *fields, double *partials,
     return 0;
 }
 
+/* ---- station probes (the contract: include/picles_hip.h; the kernel: k_probe.h) ---- */
+static bool probe_due(const picles_ctx *c, long long s)
+{
+    return s >= c->probe_first && (s - c->probe_first) % c->probe_every == 0;
+}
+
+/* samples the next n_steps model steps will take */
+static long long probe_due_within(const picles_ctx *c, long long n_steps)
+{
+    const long long a = c->probe_steps + 1, b = c->probe_steps + n_steps, f = c->probe_first, e = c->probe_every;
+    if (b < f || n_steps <= 0) return 0;
+    /* multiples f + k e inside [max(a, f), b] */
+    const long long lo = a > f ? a : f;
+    const long long k0 = (lo - f + e - 1) / e, k1 = (b - f) / e;
+    return k1 >= k0 ? k1 - k0 + 1 : 0;
+}
+
+/* would the samples of the next n_steps steps overrun the ring?  Asked by the step entry points before they change anything */
+static int probe_room(picles_ctx *c, long long n_steps, const char *who)
+{
+    if (!c->probe_n) return 0;
+    const long long due = probe_due_within(c, n_steps);
+    if (due && c->probe_count + due > c->probe_cap)
+        return fail(c, PICLES_PROBE_E_FULL, std::string(who) + ": probe ring full (" + std::to_string(c->probe_count) + " samples pending, " +
+                                            std::to_string(due) + " due, capacity " + std::to_string(c->probe_cap) + "): picles_probe_pop first");
+    return 0;
+}
+
+/* One sample into the next ring slot, on stream s — which the caller has ordered behind everything the sample depends on.  With a
+ * fused step pending the values come from its records, with the arrays and reach indices flush() would hand k_scatter at this
+ * point; otherwise from State.  Neither the pending step nor any plane of the model is touched; the host does not wait. */
+static int probe_take(picles_ctx *c, hipStream_t s)
+{
+    if (c->probe_count == c->probe_cap) return fail(c, PICLES_PROBE_E_FULL, "probe ring full: picles_probe_pop first");
+    const int slot = (c->probe_head + c->probe_count) % c->probe_cap;
+    const size_t sample = (size_t)3 * c->probe_n;
+    double *d = c->probe_dev + (size_t)slot * sample;
+    const dim3 grid(nblocks(c->probe_n, PROBE_BLOCK)), block(PROBE_BLOCK);
+    if (c->pending)
+        hipLaunchKernelGGL(k_probe<true>, grid, block, 0, s, c->G, arrays_for(c, c->cur, c->cur), c->probe_n, (const int *)c->probe_nodes, d);
+    else
+        hipLaunchKernelGGL(k_probe<false>, grid, block, 0, s, c->G, c->A, c->probe_n, (const int *)c->probe_nodes, d);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->probe_ready[slot], s));
+    HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->probe_ready[slot], 0));
+    HIPCHK(c, hipMemcpyAsync(c->probe_host + (size_t)slot * sample, d, sample * sizeof(double), hipMemcpyDeviceToHost, c->store_stream));
+    HIPCHK(c, hipEventRecord(c->probe_done[slot], c->store_stream));
+    c->probe_time[slot] = c->clock;
+    c->probe_step[slot] = c->probe_steps;
+    c->probe_count++;
+    return 0;
+}
+
+static void probe_release(picles_ctx *c)
+{
+    if (c->probe_nodes) hipFree(c->probe_nodes);
+    if (c->probe_dev) hipFree(c->probe_dev);
+    if (c->probe_host) hipHostFree(c->probe_host);
+    for (auto e : c->probe_ready) hipEventDestroy(e);
+    for (auto e : c->probe_done) hipEventDestroy(e);
+    c->probe_nodes = nullptr; c->probe_dev = nullptr; c->probe_host = nullptr;
+    c->probe_ready.clear(); c->probe_done.clear(); c->probe_time.clear(); c->probe_step.clear();
+    c->probe_n = 0; c->probe_cap = 0; c->probe_head = 0; c->probe_count = 0; c->probe_steps = 0;
+    c->probe_every = 1; c->probe_first = 1;
+}
+
+PX_EXPORT int32_t picles_probe_init(picles_ctx *c, int32_t n, const int32_t *ij, int32_t every, int32_t first, int32_t capacity)
+{
+    if (!c) return -1;
+    if (c->probe_n) return fail(c, -2, "picles_probe_init: a probe set exists (picles_probe_free first)");
+    if (n < 1 || !ij) return fail(c, -2, "picles_probe_init: n must be >= 1 and the node list given");
+    if (every < 1 || first < 1 || capacity < 1) return fail(c, -2, "picles_probe_init: every, first and capacity must be >= 1");
+    const GridP &G = c->G;
+    std::vector<int> loc((size_t)2 * n);
+    for (int k = 0; k < n; k++) {
+        const int i = ij[k], j = ij[(size_t)n + k];
+        if (i < 0 || i >= G.Nx || j < G.j_begin || j >= G.j_begin + G.ny_loc)
+            return fail(c, -2, "picles_probe_init: node " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) +
+                                   ") lies outside [0, Nx) x [j_begin, j_end)");
+        loc[k] = i;
+        loc[(size_t)n + k] = j - G.j_begin;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t ring = (size_t)capacity * 3 * (size_t)n * sizeof(double);
+    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) probe_release(c); } } undo{c, true};
+    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    HIPCHK(c, hipMalloc(&c->probe_nodes, (size_t)2 * n * sizeof(int)));
+    HIPCHK(c, hipMalloc(&c->probe_dev, ring));
+    HIPCHK(c, hipHostMalloc(&c->probe_host, ring, hipHostMallocDefault));
+    for (int k = 0; k < capacity; k++) {
+        hipEvent_t e1, e2;
+        HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
+        c->probe_ready.push_back(e1);
+        HIPCHK(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
+        c->probe_done.push_back(e2);
+    }
+    HIPCHK(c, hipMemcpy(c->probe_nodes, loc.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice));     /* blocking: loc dies here */
+    c->probe_time.assign(capacity, 0.0);
+    c->probe_step.assign(capacity, 0);
+    c->probe_every = every; c->probe_first = first; c->probe_cap = capacity;
+    c->probe_head = 0; c->probe_count = 0; c->probe_steps = 0;
+    c->probe_n = n;
+    undo.armed = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_probe_shape(const picles_ctx *c, int32_t *n, int32_t *every, int32_t *capacity)
+{
+    if (!c || !c->probe_n) return -1;
+    if (n) *n = c->probe_n;
+    if (every) *every = c->probe_every;
+    if (capacity) *capacity = c->probe_cap;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_probe_pending(const picles_ctx *c) { return c ? c->probe_count : -1; }
+
+PX_EXPORT int32_t picles_probe_sample(picles_ctx *c, void *stream)
+{
+    if (!c) return -1;
+    if (!c->probe_n) return fail(c, -2, "picles_probe_init first");
+    if (c->probe_count == c->probe_cap) return fail(c, PICLES_PROBE_E_FULL, "picles_probe_sample: probe ring full: picles_probe_pop first");
+    HIPCHK(c, hipSetDevice(c->device));
+    return probe_take(c, stream ? (hipStream_t)stream : c->stream);
+}
+
+PX_EXPORT int32_t picles_probe_pop(picles_ctx *c, int32_t max_samples, double *values, double *times, int64_t *steps, int32_t *n_out)
+{
+    if (!c) return -1;
+    if (n_out) *n_out = 0;
+    if (!c->probe_n) return fail(c, -2, "picles_probe_init first");
+    if (max_samples < 1 || !values || !n_out) return fail(c, -2, "picles_probe_pop: max_samples must be >= 1, values and n_out given");
+    if (!c->probe_count) return fail(c, -3, "no probe sample pending");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int m = max_samples < c->probe_count ? max_samples : c->probe_count;
+    const size_t sample = (size_t)3 * c->probe_n;
+    for (int k = 0; k < m; k++) {
+        const int slot = c->probe_head;
+        HIPCHK(c, hipEventSynchronize(c->probe_done[slot]));      /* this sample's copy alone: later steps stay enqueued */
+        memcpy(values + (size_t)k * sample, c->probe_host + (size_t)slot * sample, sample * sizeof(double));
+        if (times) times[k] = c->probe_time[slot];
+        if (steps) steps[k] = (int64_t)c->probe_step[slot];
+        c->probe_head = (c->probe_head + 1) % c->probe_cap;
+        c->probe_count--;
+        *n_out = k + 1;
+    }
+    return 0;
+}
+
+PX_EXPORT int32_t picles_probe_free(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->probe_n) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());       /* probe launches and copies in flight read and write the buffers about to go */
+    probe_release(c);
+    return 0;
+}
+
 /* ---- halo blocks ---- */
 PX_EXPORT int32_t picles_halo_rows(const picles_ctx *c) { return c ? c->G.R : -1; }
 
@@ -2037,6 +2227,12 @@ struct SlabRing {
     hipStream_t sE = nullptr, sM = nullptr;
     hipEvent_t evE = nullptr, evM = nullptr, evEd = nullptr;      /* evEd: this step's edge launch alone (without the exchange behind it) */
     unsigned long long steps = 0, exchanged_bytes = 0;
+    /* station probes of fused steps run on a side stream P that waits for the step's interior launch (evPm, stream M) and for its
+     * exchange (evPx, stream E): neither M nor E waits for the other on the probe's account.  evP[b]: the latest probe that reads
+     * record buffer b; the launches that overwrite the buffer two steps later wait for it (it completed long before) */
+    hipStream_t sP = nullptr;
+    hipEvent_t evPx = nullptr, evPm = nullptr, evP[2] = {nullptr, nullptr};
+    bool evP_live[2] = {false, false};
     /* phase timing (picles_slab_get_phases): five events per step while per-launch timing is on */
     struct PhaseEv { hipEvent_t e0, e1, x1, m0, m1; };
     std::vector<PhaseEv> ph_used, ph_free;
@@ -2076,6 +2272,8 @@ PX_EXPORT int32_t picles_slab_comm_destroy(picles_ctx *c)
     if (R->evE) hipEventDestroy(R->evE);
     if (R->evM) hipEventDestroy(R->evM);
     if (R->evEd) hipEventDestroy(R->evEd);
+    for (hipEvent_t e : {R->evPx, R->evPm, R->evP[0], R->evP[1]}) if (e) hipEventDestroy(e);
+    if (R->sP) hipStreamDestroy(R->sP);
     for (auto *v : {&R->ph_used, &R->ph_free})
         for (auto &e : *v) { hipEventDestroy(e.e0); hipEventDestroy(e.e1); hipEventDestroy(e.x1); hipEventDestroy(e.m0); hipEventDestroy(e.m1); }
     if (R->sE) hipStreamDestroy(R->sE);
@@ -2163,7 +2361,12 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
     if (!R) return fail(c, -2, "picles_slab_comm_init first");
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     if (flags & PICLES_STEP_ATOMIC) return fail(c, -5, "PICLES_STEP_ATOMIC is single-slab only");
+    { int rc = probe_room(c, n_steps, "picles_slab_run_steps"); if (rc) return rc; }      /* up front: nothing has changed yet */
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->probe_n && !R->sP) {
+        HIPCHK(c, hipStreamCreateWithFlags(&R->sP, hipStreamNonBlocking));
+        for (hipEvent_t *e : {&R->evPx, &R->evPm, &R->evP[0], &R->evP[1]}) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
     c->ext_streams = true;
     c->ring_orders = true;
     /* timing mode 2: ONE event pair around the whole call, on the stream of the interior launches (every step's edge launch and
@@ -2199,6 +2402,12 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
         int fused = (flags == PICLES_STEP_ZERO_FIRST) ? picles_begin_fused_step(c, dt) : 1;
         if (fused < 0) return fused;
         if (fused == 1) { int rc = picles_begin_step(c, dt, flags); if (rc) return rc; }
+        if (R->evP_live[c->cur]) {
+            /* this step's launches overwrite the record buffer that the probe of two steps ago reads */
+            HIPCHK(c, hipStreamWaitEvent(R->sE, R->evP[c->cur], 0));
+            HIPCHK(c, hipStreamWaitEvent(R->sM, R->evP[c->cur], 0));
+            R->evP_live[c->cur] = false;
+        }
         /* the previous step's interior launch (stream M) wrote / read what the edge launch touches */
         HIPCHK(c, hipStreamWaitEvent(R->sE, R->evM, 0));
         const bool phases = c->timing && c->timing_mode == 1 && R->ph_used.size() < (1u << 16);
@@ -2217,6 +2426,11 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
         rc = (fused == 0) ? picles_step_rows(c, PICLES_ROWS_INTERIOR, R->sM) : picles_advance_rows(c, PICLES_ROWS_INTERIOR, R->sM);
         if (rc) return rc;
         if (phases) { HIPCHK(c, hipEventRecord(pe.m1, R->sM)); R->ph_used.push_back(pe); }
+        const bool sample = c->probe_n && probe_due(c, c->probe_steps + 1);
+        if (sample && fused == 0) {      /* what the probe of a fused step waits for: the interior launch and the delivered halo */
+            HIPCHK(c, hipEventRecord(R->evPm, R->sM));
+            HIPCHK(c, hipEventRecord(R->evPx, R->sE));
+        }
         if (fused == 0) {
             /* fused steps: what runs next on M is the next step's interior launch.  Its pull reads own rows only — the records the
              * edge launch of THIS step wrote among them — never the ghost rows: it waits for the edge kernel, not for the exchange
@@ -2230,6 +2444,17 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
         c->edge_pending = false;
         rc = (fused == 0) ? picles_end_fused_step(c) : picles_scatter_remesh(c, R->sM);
         if (rc) return rc;
+        if (sample && fused == 0) {
+            /* records: edge-row nodes are fed by the neighbour's records, so the probe needs the exchange as well as both launches
+             * — on the side stream, so that stream M never waits for the exchange */
+            HIPCHK(c, hipStreamWaitEvent(R->sP, R->evPm, 0));
+            HIPCHK(c, hipStreamWaitEvent(R->sP, R->evPx, 0));
+            if ((rc = probe_take(c, R->sP))) return rc;
+            HIPCHK(c, hipEventRecord(R->evP[c->cur], R->sP));
+            R->evP_live[c->cur] = true;
+        } else if (sample) {
+            if ((rc = probe_take(c, R->sM))) return rc;      /* State is in memory: gathered on the stream that ran the scatter */
+        }
         R->steps++;
     }
     return 0;
@@ -2559,6 +2784,8 @@ PX_EXPORT int32_t picles_checkpoint_end(picles_ctx *c, void *buf, size_t bytes)
 PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t bytes)
 {
     if (!c || !buf) return -1;
+    if (c->probe_count > 0)
+        return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_load: probe samples of this context are pending (picles_probe_pop first)");
     if (c->ck_inflight || c->store_count > 0 || c->diag_count > 0)
         return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_load: a checkpoint or store snapshot of this context is in flight (end / pop it first)");
     CkptHeader h;

@@ -18,7 +18,9 @@ from . import _capi as K
 def _check(lib, h, rc, what):
     if rc != 0:
         msg = lib.picles_last_error(h)
-        raise K.PiclesError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
+        e = K.PiclesError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
+        e.code = rc          # (e.g. K.PROBE_E_FULL: the caller pops and repeats the call)
+        raise e
 
 
 def _col(a, n):
@@ -390,6 +392,50 @@ class HipModel:
     @property
     def diag_pending(self):
         return self.lib.picles_diag_pending(self.h)
+
+    # ---- station probes (picles_probe_*: the State value of chosen nodes behind every step, the fused path kept) ----
+    def probe_init(self, nodes, every=1, first=1, capacity=64):
+        """nodes: (n, 2) global 0-based (i, j), j inside this context's rows; a sample is taken after every model step s (counted
+        from here) with s >= first and (s - first) % every == 0; `capacity` samples may wait for probe_pop"""
+        ij = np.asarray(nodes, dtype=np.int64)
+        if ij.ndim != 2 or ij.shape[1] != 2:
+            raise ValueError("probe_init: nodes must be an (n, 2) array of (i, j)")
+        if ij.size and (np.abs(ij).max() > 2**31 - 1):
+            raise ValueError("probe_init: node index out of the int32 range")
+        planes = np.ascontiguousarray(ij.T.astype(np.int32))
+        self._ck(self.lib.picles_probe_init(self.h, int(ij.shape[0]), planes.ctypes.data_as(K.c_int32_p), int(every), int(first),
+                                            int(capacity)), "picles_probe_init")
+
+    def probe_shape(self):
+        """(n, every, capacity) of the probe set; no device work"""
+        a = [C.c_int32() for _ in range(3)]
+        if self.lib.picles_probe_shape(self.h, *[C.byref(x) for x in a]) != 0:
+            raise K.PiclesError("picles_probe_shape failed: probe_init first")
+        return tuple(x.value for x in a)
+
+    def probe_sample(self, stream=None):
+        """one sample now (the seeded state; callers of the split-phase API, on the stream their step is ordered on)"""
+        self._ck(self.lib.picles_probe_sample(self.h, stream), "picles_probe_sample")
+
+    def probe_pop(self, max_samples=None):
+        """the oldest samples, up to max_samples (all pending when None): (values [samples, 3, n], times [samples], steps [samples])"""
+        n, _, cap = self.probe_shape()
+        m = cap if max_samples is None else int(max_samples)
+        m = max(1, min(m, max(self.probe_pending, 1)))
+        v = np.empty((m, 3, n))
+        t = np.empty(m)
+        s = np.empty(m, dtype=np.int64)
+        got = C.c_int32()
+        self._ck(self.lib.picles_probe_pop(self.h, m, K.dptr(v), K.dptr(t), s.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(got)),
+                 "picles_probe_pop")
+        return v[:got.value], t[:got.value], s[:got.value]
+
+    @property
+    def probe_pending(self):
+        return self.lib.picles_probe_pending(self.h)
+
+    def probe_free(self):
+        self._ck(self.lib.picles_probe_free(self.h), "picles_probe_free")
 
     # ---- exact restart (picles_checkpoint_*) ----
     def checkpoint_size(self) -> int:

@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(6)
+const PICLES_ABI_VERSION = Int32(7)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -448,6 +448,47 @@ function run_fields!(model::WaveGrowth2DHIP, Δt::Float64, n_steps::Integer, sin
     check_dropped(model)
     nothing
 end
+
+"""
+    probe_init!(model, nodes; every=1, first=1, capacity=64)
+
+Station probes (`picles_probe_*`, the contract is in include/picles_hip.h): `nodes` is a vector of 1-based `(i, j)` (Julia indices
+of `State[i, j, :]`).  After every model step `s` with `s >= first` and `(s - first) % every == 0` the library samples
+`State[i, j, :]` at these nodes on the device — from the scatter records of the pending fused step, which stays pending — and
+copies the sample to pinned host memory beside the steps that follow.  What the reference's scripts cut out of `cash_store`
+snapshots (tests/T04_2D_reg_test.jl) without a snapshot.  `probe_sample!` takes one sample now (the seeded state), `probe_pop!`
+hands out the oldest samples, `probe_free!` drops the set.
+"""
+function probe_init!(model::WaveGrowth2DHIP, nodes; every::Integer=1, first::Integer=1, capacity::Integer=64)
+    n = length(nodes)
+    ij = Vector{Int32}(undef, 2n)
+    for (k, (i, j)) in enumerate(nodes)
+        ij[k] = Int32(i - 1); ij[n + k] = Int32(j - 1)
+    end
+    check(model.ctx, ccall((:picles_probe_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Int32, Int32), model.ctx, n, ij, every, first, capacity), "picles_probe_init")
+    nothing
+end
+
+probe_sample!(model::WaveGrowth2DHIP) =
+    check(model.ctx, ccall((:picles_probe_sample, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), model.ctx, C_NULL), "picles_probe_sample")
+
+probe_pending(model::WaveGrowth2DHIP) = ccall((:picles_probe_pending, libpicles), Int32, (Ptr{Cvoid},), model.ctx)
+
+"`(values[node, k, sample], times, steps)` of the oldest samples (all that are pending by default); k = e, m_x, m_y"
+function probe_pop!(model::WaveGrowth2DHIP; max_samples::Integer=typemax(Int32))
+    n, every, cap = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    ccall((:picles_probe_shape, libpicles), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}), model.ctx, n, every, cap) == 0 ||
+        error("picles_probe_shape failed: probe_init! first")
+    m = max(1, min(Int(max_samples), Int(probe_pending(model))))
+    values = Array{Float64,3}(undef, n[], 3, m)
+    times = Vector{Float64}(undef, m)
+    steps = Vector{Int64}(undef, m)
+    got = Ref{Int32}(0)
+    check(model.ctx, ccall((:picles_probe_pop, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ref{Int32}), model.ctx, m, values, times, steps, got), "picles_probe_pop")
+    values[:, :, 1:got[]], times[1:got[]], steps[1:got[]]
+end
+
+probe_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_probe_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_probe_free")
 
 """
     checkpoint!(model, path; iteration = model.clock.iteration)

@@ -404,6 +404,7 @@ class SlabModel:
             b.scatter_remesh()
         self.clock += dt
         self._steps_done += 1
+        self._probe_after_steps(1, split_phase=not self.native and self.ex is not None)
         if self.auto_halo_every > 0 and self.world > 1 and self._steps_done % self.auto_halo_every == 0:
             self.grow_halo_if_needed()
 
@@ -426,6 +427,7 @@ class SlabModel:
             self.backend.slab_run_steps(dt, n, flags)
         self.clock += n * dt
         self._steps_done += n
+        self._probe_after_steps(n, split_phase=False)
 
     def check_overflow(self):
         """raise if any particle travelled beyond the ghost rows (it was not scattered: the State is incomplete)"""
@@ -540,6 +542,63 @@ class SlabModel:
         dist.all_gather_object(parts, (f, p))
         return (np.concatenate([a for a, _ in parts], axis=2), combine_partials([b for _, b in parts], Nx, Ny), t)
 
+    # ---- station probes: every rank samples the nodes of its own rows (picles_probe_*) ----
+    def probe_init(self, nodes, every=1, first=1, capacity=64):
+        """nodes: (n, 2) global 0-based (i, j) anywhere on the grid, the same list on every rank; each rank probes those inside its
+        rows.  The native ring, picles_run_steps and picles_time_step sample by themselves; the Python-driven split-phase loop
+        calls picles_probe_sample behind the halo exchange of every due step."""
+        nodes = np.asarray(nodes, dtype=np.int64).reshape(-1, 2)
+        Nx, Ny = int(self.grid.stats.Nx), int(self.grid.stats.Ny)
+        if len(nodes) < 1 or nodes.min() < 0 or nodes[:, 0].max() >= Nx or nodes[:, 1].max() >= Ny:
+            raise ValueError(f"probe_init: need at least one node, all inside [0, {Nx}) x [0, {Ny})")
+        if every < 1 or first < 1 or capacity < 1:
+            raise ValueError("probe_init: every, first and capacity must be >= 1")
+        mine = np.flatnonzero((nodes[:, 1] >= self.j0) & (nodes[:, 1] < self.j1))
+        if len(mine):
+            self.backend.probe_init(nodes[mine], every=every, first=first, capacity=capacity)
+        self._probe = dict(n=len(nodes), mine=mine, every=int(every), first=int(first), steps=0)
+
+    def _probe_after_steps(self, n, split_phase):
+        p = getattr(self, "_probe", None)
+        if p is None:
+            return
+        p["steps"] += n
+        s = p["steps"]
+        if split_phase and len(p["mine"]) and s >= p["first"] and (s - p["first"]) % p["every"] == 0:
+            # the step's launches and its delivered halo are ordered on the interior stream (or on the context stream)
+            self.backend.probe_sample(self.s_main.cuda_stream if self.use_streams else None)
+
+    def probe_sample(self):
+        """one sample now on every rank (the seeded state)"""
+        p = self._probe
+        if len(p["mine"]):
+            self.sync()
+            self.backend.probe_sample()
+
+    def probe_free(self):
+        p = getattr(self, "_probe", None)
+        if p is not None and len(p["mine"]):
+            self.backend.probe_free()
+        self._probe = None
+
+    def pop_probes(self, max_samples=None):
+        """this rank's part: (indices of its nodes in the caller's list, values [samples, 3, n_mine], times, steps)"""
+        p = self._probe
+        if not len(p["mine"]) or self.backend.probe_pending == 0:
+            return p["mine"], np.empty((0, 3, len(p["mine"]))), np.empty(0), np.empty(0, dtype=np.int64)
+        return (p["mine"],) + self.backend.probe_pop(max_samples)
+
+    def gather_probes(self, max_samples=None):
+        """pop this rank's pending samples and gather all ranks': (values [samples, 3, n] in the caller's node order, times, steps).
+        No arithmetic crosses ranks: the result is bitwise what a whole-grid context gives, whatever the decomposition."""
+        part = self.pop_probes(max_samples)
+        if self.world == 1:
+            return assemble_probes(self._probe["n"], [part])
+        import torch.distributed as dist
+        parts = [None] * self.world
+        dist.all_gather_object(parts, part)
+        return assemble_probes(self._probe["n"], parts)
+
     def gather_state(self):
         """all ranks' slabs concatenated along y (host; for tests)"""
         s = self.get_state()
@@ -549,3 +608,18 @@ class SlabModel:
         parts = [None] * self.world
         dist.all_gather_object(parts, s)
         return np.concatenate(parts, axis=1)
+
+
+def assemble_probes(n, parts):
+    """the ranks' parts of pop_probes -> (values [samples, 3, n] in the caller's node order, times, steps); ranks without a node
+    contribute nothing, the others must hold the same samples"""
+    have = [q for q in parts if len(q[0])]
+    if not have:
+        raise ValueError("assemble_probes: no rank holds a node")
+    t, s = have[0][2], have[0][3]
+    out = np.empty((len(s), 3, n))
+    for mine, v, tt, ss in have:
+        if not (np.array_equal(ss, s) and np.array_equal(tt, t)):
+            raise ValueError("assemble_probes: the ranks hold different samples (pop them at the same step)")
+        out[:, :, mine] = v
+    return out, t, s

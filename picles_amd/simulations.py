@@ -109,6 +109,10 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
     fw = find_field_writer(sim)
     if fw is not None and not hasattr(sim.model.backend, "diag_init"):
         raise NotImplementedError("a FieldWriter needs a backend with diag_init / diag_push / diag_pop (the HIP library)")
+    from .station_output import find_station_writer
+    sw = find_station_writer(sim)
+    if sw is not None and not hasattr(sim.model.backend, "probe_init"):
+        raise NotImplementedError("a StationWriter needs a backend with probe_init / probe_sample / probe_pop (the HIP library)")
     sim.run_wall_time = 0.0
     sim.running = sim.stop_time >= sim.model.clock.time
     if cash_store:
@@ -126,17 +130,28 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         # nothing observes State between the steps: enqueue the whole loop from C in one call
         import math
         n = int(math.floor((sim.stop_time - m.clock.time) / sim.Δt)) + 1 if sim.running else 0   # run.jl:113: one step past stop_time
-        if n > 0 and (ckpt is not None or fw is not None):
-            # chunks that end on the next output or checkpoint iteration, whichever is first: the snapshot of chunk k is copied
-            # out and written while chunk k+1 runs
+        if n > 0 and (ckpt is not None or fw is not None or sw is not None):
+            # chunks that end on the next output or checkpoint iteration or where the probe ring would fill, whichever is first:
+            # the snapshot of chunk k is copied out and written — and the station samples of chunk k-1 are — while chunk k+1 runs
             m.upload_winds(m.clock.time, sim.Δt)
             time0, it0, done = m.clock.time, m.clock.iteration, 0
             if fw is not None:
                 fw.begin_run(m, n)                      # the record of the first iteration
+            if sw is not None:
+                sw.begin_run(m, n)
             while done < n:
-                nxt = min(w.schedule.next_after(it0 + done) for w in (ckpt, fw) if w is not None)
-                k = min(nxt - (it0 + done), n - done)
+                k = n - done
+                if ckpt is not None or fw is not None:
+                    k = min(k, min(w.schedule.next_after(it0 + done) for w in (ckpt, fw) if w is not None) - (it0 + done))
+                earlier = 0
+                if sw is not None:
+                    if sw.steps_allowed(m.backend, it0 + done) < 1:
+                        sw.drain(m.backend)
+                    k = min(k, sw.steps_allowed(m.backend, it0 + done))
+                    earlier = m.backend.probe_pending       # samples of the chunks before this one
                 m.backend.run_steps(sim.Δt, k)
+                if sw is not None:
+                    sw.drain(m.backend, earlier)
                 if ckpt is not None:
                     ckpt.finish(m.backend)
                 done += k
@@ -154,13 +169,19 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
             m.clock.time += n * sim.Δt
             m.clock.iteration += n
         sim.running = False
-    if fw is not None and sim.running:
-        # the per-step loop (time-varying winds, stores): the writer needs the number of steps for the size of its file
+    if (fw is not None or sw is not None) and sim.running:
+        # the per-step loop (time-varying winds, stores): the writers need the number of steps for the size of their files
         import math
         if sim.stop_time == float("inf"):
-            raise ValueError("a FieldWriter needs a finite stop_time (its file is sized for the run)")
-        fw.begin_run(sim.model, int(math.floor((sim.stop_time - sim.model.clock.time) / sim.Δt)) + 1)
+            raise ValueError("a FieldWriter or StationWriter needs a finite stop_time (its file is sized for the run)")
+        n_loop = int(math.floor((sim.stop_time - sim.model.clock.time) / sim.Δt)) + 1
+        if fw is not None:
+            fw.begin_run(sim.model, n_loop)
+        if sw is not None:
+            sw.begin_run(sim.model, n_loop)
     while sim.running:
+        if sw is not None:
+            sw.make_room(sim.model.backend)     # the library samples inside time_step and refuses a full ring
         sim.model.State.fill(0.0)          # State .= 0 (run.jl:75-79): recorded by the lazy view, fused into the scatter's store
         time_step(sim.model, sim.Δt, debug=debug)
         if store:
@@ -185,6 +206,8 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         ckpt.finish(sim.model.backend)
     if fw is not None:
         fw.finish(sim.model.backend)
+    if sw is not None:
+        sw.finish(sim.model.backend)
     if store:
         if ring:
             b = sim.model.backend

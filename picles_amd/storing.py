@@ -281,6 +281,42 @@ def read_state_store(path):
     return out
 
 
+def read_h5_group(path, group, f64=(), strings=(), attrs=()):
+    """the named float64 datasets (arrays in the file's row-major shape), string datasets and string attributes of one group"""
+    L = hdf5()
+    f = _ok(L.H5Fopen(str(path).encode(), _H5F_ACC_RDONLY, 0), f"H5Fopen({path})")
+    g = _ok(L.H5Gopen2(f, group.encode(), 0), f"H5Gopen2({group})")
+    out = {}
+
+    def shape_of(space):
+        nd = L.H5Sget_simple_extent_ndims(space)
+        d = (C.c_uint64 * nd)()
+        L.H5Sget_simple_extent_dims(space, d, None)
+        return tuple(int(v) for v in d)
+
+    for name in f64:
+        d = _ok(L.H5Dopen2(g, name.encode(), 0), f"H5Dopen2({name})")
+        sp = L.H5Dget_space(d)
+        a = np.empty(shape_of(sp), dtype=np.float64)
+        _ok(L.H5Dread(d, L.NATIVE_DOUBLE, 0, 0, 0, a.ctypes.data), f"H5Dread({name})")
+        L.H5Sclose(sp); L.H5Dclose(d)
+        out[name] = a
+    for name, attribute in [(n, False) for n in strings] + [(n, True) for n in attrs]:
+        t = _vlen_str_type(L)
+        h = _ok((L.H5Aopen(g, name.encode(), 0) if attribute else L.H5Dopen2(g, name.encode(), 0)), f"open({name})")
+        sp = L.H5Aget_space(h) if attribute else L.H5Dget_space(h)
+        n = shape_of(sp)[0]
+        buf = (C.c_char_p * n)()
+        _ok(L.H5Aread(h, t, buf) if attribute else L.H5Dread(h, t, 0, 0, 0, buf), f"read({name})")
+        out[name] = [b.decode("utf-8") for b in buf]
+        L.H5Dvlen_reclaim(t, sp, 0, buf)
+        L.H5Sclose(sp)
+        (L.H5Aclose if attribute else L.H5Dclose)(h)
+        L.H5Tclose(t)
+    L.H5Gclose(g); L.H5Fclose(f)
+    return out
+
+
 class NpyStateStore:
     """the same logical layout without libhdf5: `<name>.waves.data.npy` [time, x, y, state] + `<name>.json`"""
 
