@@ -13,6 +13,13 @@ TILE = 256
 FOUR_PI = 4.0 * math.pi
 
 
+def fmax(a, b):
+    """the fmax of the definition: a NaN — quiet or signalling — is skipped; NaN only when both are.  (np.fmax hands a signalling NaN
+    to the C library, which answers NaN or the number depending on the loop NumPy happens to take.)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.where(np.isnan(b), a, np.where(np.isnan(a), b, np.maximum(a, b)))
+
+
 def coarse_shape(Nx, ny, cx, cy):
     return -(-Nx // cx), -(-ny // cy)
 
@@ -37,7 +44,7 @@ def cell_sums(state, cx, cy):
                 for acc, v in zip(S, (e, mx, my, np.ones_like(e))):
                     acc[:a, :b] = np.where(wet, acc[:a, :b] + np.where(wet, v, 0.0), acc[:a, :b])
                 for acc, v in zip(X, (e, mx, my)):
-                    acc[:a, :b] = np.fmax(acc[:a, :b], v)
+                    acc[:a, :b] = fmax(acc[:a, :b], v)
     return S, X
 
 
@@ -51,7 +58,7 @@ def fields_of(state, cx, cy, g, r_g, names=FIELDS):
         cbar = E / (2.0 * np.sqrt(M2))
         planes = {
             "hs": 4.0 * np.sqrt(E),
-            "tp": (FOUR_PI * np.fmax(cbar / r_g, 0.1)) / g,
+            "tp": (FOUR_PI * fmax(cbar / r_g, 0.1)) / g,
             "cg_x": (MX * E) / (2.0 * M2),
             "cg_y": (MY * E) / (2.0 * M2),
             "e": E, "m_x": MX, "m_y": MY}
@@ -78,11 +85,11 @@ def partials_of(state, cx, cy):
     tpr = -(-nxc // TILE)
     cols = []
     with np.errstate(all="ignore"):
-        for a, fillv, op in [(s, 0.0, np.add) for s in S] + [(x, -np.inf, np.fmax) for x in X]:
+        for a, fillv, op in [(s, 0.0, np.add) for s in S] + [(x, -np.inf, fmax) for x in X]:
             pad = np.full((tpr * TILE, nyc), fillv)
             pad[:nxc] = a
             r = _tree(pad.reshape(tpr, TILE, nyc), op)          # [tiles, nyc]
-            if op is np.fmax:
+            if op is fmax:
                 r = r + 0.0
             cols.append(r.T.reshape(-1))                        # J outer, tile inner
     return np.stack(cols, axis=1)
@@ -96,7 +103,7 @@ def combine(partials_list, Nx, Ny):
             for k in range(4):
                 acc[k] = acc[k] + float(row[k])
             for k in range(4, 7):
-                acc[k] = float(np.fmax(acc[k], row[k]))
+                acc[k] = float(fmax(acc[k], row[k]))
     names = ("sum_e", "sum_mx", "sum_my", "n_wet", "max_e", "max_mx", "max_my")
     out = dict(zip(names, acc))
     out["mean_of_state"] = out["sum_e"] / (float(Nx) * float(Ny))

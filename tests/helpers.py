@@ -58,6 +58,33 @@ def assert_bitwise(a, b, what=""):
                              f"{a[k]!r} vs {b[k]!r}; max rel diff {rel:.3e}")
 
 
+def bits_of(a):
+    """the bit patterns of a float32 / float64 array as unsigned integers of the same width"""
+    a = np.ascontiguousarray(a)
+    if a.dtype not in (np.float32, np.float64):
+        raise TypeError(f"bits_of: float32 or float64, not {a.dtype}")
+    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+def assert_same_bits(a, b, what="", nan_payload=False):
+    """stricter than assert_bitwise: same dtype, same shape, identical bit patterns — so +0.0 is not -0.0 — except where both
+    values are NaN (the sign and payload of a computed NaN are not specified).  nan_payload=True: for plain copies, which hand
+    back the pattern they were given: NaNs must be identical too."""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.dtype == b.dtype, f"{what}: dtype {a.dtype} vs {b.dtype}"
+    assert a.shape == b.shape, f"{what}: shape {a.shape} vs {b.shape}"
+    ua, ub = bits_of(a), bits_of(b)
+    same = ua == ub
+    if not nan_payload:
+        same = same | (np.isnan(a) & np.isnan(b))
+    if not same.all():
+        bad = np.argwhere(~same)
+        k = tuple(bad[0])
+        w = 8 if a.dtype == np.float32 else 16
+        raise AssertionError(f"{what}: {len(bad)} of {a.size} bit patterns differ, first at {k}: "
+                             f"{a[k]!r} (0x{int(ua[k]):0{w}x}) vs {b[k]!r} (0x{int(ub[k]):0{w}x})")
+
+
 def free_port():
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close()

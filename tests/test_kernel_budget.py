@@ -158,3 +158,19 @@ def test_advance_kernel_argument_struct_mirrors_the_kernarg_segment():
         pos = (pos + align - 1) // align * align
         expect.append(pos); pos += size
     assert [a for a, _ in offs] == expect, (offs, expect)
+
+
+def test_the_build_keeps_ieee_arithmetic():
+    """the diagnostics and the wind sampler are held bit for bit to IEEE restatements (tests/test_gpu_diag_hostile.py,
+    tests/test_gpu_wind_sampler.py): one correctly rounded operation at a time, subnormals kept.  The product's compile line must
+    say so: no contraction, no fast-math family flag, no flushing of denormals."""
+    mk = (ROOT / "picles_amd" / "csrc" / "Makefile").read_text()
+    flags = re.search(r"^CFLAGS_\s*\?=((?:.*\\\n)*.*)$", mk, re.M).group(1).replace("\\\n", " ").split()
+    assert "-ffp-contract=off" in flags and "-fno-fast-math" in flags, flags
+    banned = ("-ffast-math", "-Ofast", "-funsafe-math-optimizations", "-fapprox-func", "-freciprocal-math", "-fassociative-math",
+              "-ffinite-math-only", "-fno-signed-zeros", "-fgpu-flush-denormals-to-zero", "-fgpu-approx-transcendentals",
+              "-fcuda-flush-denormals-to-zero", "-ffp-contract=fast", "-ffp-contract=on", "-ffp-contract=fast-honor-pragmas")
+    assert not [f for f in flags if f in banned or f.startswith(("-fdenormal-fp-math", "-ffp-model", "-mllvm"))], flags
+    # every compile line uses them
+    compiles = [ln for ln in mk.splitlines() if "$(HIPCC)" in ln and " -c " in ln]
+    assert len(compiles) >= 4 and all("$(CFLAGS_)" in ln for ln in compiles), compiles
