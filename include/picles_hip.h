@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 7
+#define PICLES_ABI_VERSION 8
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -351,6 +351,73 @@ int32_t picles_probe_pop(picles_ctx *ctx, int32_t max_samples, double *values, d
 int32_t picles_probe_pending(const picles_ctx *ctx);
 int32_t picles_probe_shape(const picles_ctx *ctx, int32_t *n, int32_t *every, int32_t *capacity);
 int32_t picles_probe_free(picles_ctx *ctx);
+
+/* ---- run statistics: storm-peak, mean and exceedance maps of every node, kept on the device, with the fused path kept -------------
+ * What a hindcast reports per node over a run — the maximum significant wave height and when it occurred, period and direction at
+ * that peak, mean Hs, mean direction, the share of time above a height threshold — needs State at EVERY step.  Here every node is
+ * sampled on the device behind each step, as the station probes sample a few, and folded into per-node accumulators that stay in
+ * device memory: State never crosses PCIe, and the host derives the reported variables from the accumulators at the end.
+ *
+ * THE CONTRACT (tests restate it).
+ * A context holds at most one statistics set, created by picles_stat_init(ctx, group_mask, n_thresholds, thresholds, every, first).
+ * A SAMPLE of a node is the three doubles (e, m_x, m_y) picles_get_state would return for it at that moment — bit for bit —, formed
+ * from the scatter records of a pending fused step by the pull k_scatter would run for the node, otherwise read from State: the rule
+ * of the probe contract above (freshly seeded, after a step of the plain phases, after PICLES_STEP_MOVIE — then zeros —,
+ * PICLES_STEP_ATOMIC, picles_set_state, a checkpoint load: State).  A sample carries the model clock.
+ * A sample is WET by the rule of picles_diag_*: e, m_x, m_y finite, e > 0 and m_x m_x + m_y m_y > 0.  A sample that is not wet
+ * changes nothing at that node.
+ * Per node and wet sample, in fp64, every operation one correctly rounded IEEE operation in the order written (no contraction into
+ * fused multiply-adds); all accumulators start from zero:
+ *   always               n_wet (uint32 plane) is incremented (it wraps at 2^32)
+ *   PICLES_STAT_PEAK     planes e_peak, mx_peak, my_peak, t_peak (fp64): if this is the node's first wet sample (n_wet was 0) or
+ *                        e > e_peak, all four are replaced by e, m_x, m_y and the sample's clock.  The comparison is strict: the
+ *                        first of equal maxima is kept
+ *   PICLES_STAT_MEAN     planes sum_e, sum_mx, sum_my, sum_hs (fp64): each  sum = sum + x,  with  hs = 4.0 * sqrt(e)
+ *   PICLES_STAT_EXCEED   n_thresholds in 1 ... 4 Hs thresholds, finite, positive, strictly ascending: one uint32 plane n_exc[k] per
+ *                        threshold, incremented when hs >= thr[k], hs as above
+ * The context also keeps, on the host, n_samples (updates since init / reset, wet or not) and the clocks of the first and the last
+ * of them (0.0 while there is none).
+ * Planes are column-major [i + Nx * jl] over the context's own rows, like State: per-node accumulators do not depend on the slab
+ * decomposition, and the planes of the whole grid are the slabs' planes row block after row block.
+ * THE PLANE BLOCK of get / set: the planes of the groups selected by the call's mask — a subset of the set's mask; n_wet always —
+ * back to back, the fp64 planes first: [e_peak mx_peak my_peak t_peak] [sum_e sum_mx sum_my sum_hs] as doubles, then n_wet
+ * [n_exc[0] ... n_exc[n_thresholds - 1]] as uint32: N (8 (4 [PEAK] + 4 [MEAN]) + 4 (1 + n_thresholds [EXCEED])) bytes, N = Nx (j_end -
+ * j_begin).  That is 4 + 32 + 32 + 4 n_thresholds bytes of device memory per node for the whole set.
+ *
+ * AUTOMATIC UPDATES: picles_time_step, picles_run_steps and picles_slab_run_steps update after every model step they complete
+ * (fused or plain, any flags) for which s >= first and (s - first) % every == 0, every >= 1, first >= 1; s counts the model steps
+ * the context has completed since picles_stat_init (a step completes in picles_end_fused_step or picles_scatter_remesh, whoever
+ * calls them).  The split-phase calls count steps and do not update: their caller calls picles_stat_update(ctx, stream) behind the
+ * stream that orders the step's launches and its delivered halo, and keeps the launches that overwrite the record buffer two steps
+ * later behind that stream.  Operations on the planes (update, reset, set) are ordered behind each other whatever streams they use.
+ * An update does NOT complete a pending fused step, does not synchronise the host, and leaves State, particles, counters, reach
+ * counters, dispatch order and clock untouched.
+ *
+ *   init:    refuses (context unchanged, picles_last_error set) an empty or unknown mask, n_thresholds outside 1 ... 4 or thresholds
+ *            that break the rule with EXCEED, n_thresholds != 0 without it, every < 1, first < 1, a second init without
+ *            picles_stat_free
+ *   shape:   mask, n_thresholds, thresholds (room for 4), every, number of planes and bytes of the whole set's plane block (any
+ *            pointer may be NULL; -1 without a set; no device work)
+ *   update:  one update now, on `stream` (NULL: the context stream).  Refuses: no set
+ *   get:     waits for the latest operation on the planes only — through an event, not a device synchronisation; a pending step
+ *            stays pending — and copies the plane block of `group_mask` and the three scalars out (the scalar pointers may be
+ *            NULL).  Refuses: no set, planes NULL, a mask that is no subset of the set's
+ *   set:     uploads a plane block and the three scalars, behind the updates already issued: how a picked-up run continues.
+ *            Refuses: no set, planes NULL, n_samples < 0, a mask that is no subset of the set's
+ *   reset:   planes and scalars to zero, in stream order behind the updates already issued; the step count s goes on
+ *   free:    drops the set so that a new one may be created; picles_destroy does it too
+ * The set is no part of the checkpoint blob or its fingerprint; picles_checkpoint_load leaves it as it is. */
+#define PICLES_STAT_PEAK   1
+#define PICLES_STAT_MEAN   2
+#define PICLES_STAT_EXCEED 4
+#define PICLES_STAT_ALL    7
+int32_t picles_stat_init(picles_ctx *ctx, int32_t group_mask, int32_t n_thresholds, const double *thresholds, int32_t every, int32_t first);
+int32_t picles_stat_shape(const picles_ctx *ctx, int32_t *group_mask, int32_t *n_thresholds, double *thresholds, int32_t *every, int32_t *n_planes, size_t *bytes);
+int32_t picles_stat_update(picles_ctx *ctx, void *stream);
+int32_t picles_stat_get(picles_ctx *ctx, int32_t group_mask, void *planes, int64_t *n_samples, double *t_first, double *t_last);
+int32_t picles_stat_set(picles_ctx *ctx, int32_t group_mask, const void *planes, int64_t n_samples, double t_first, double t_last);
+int32_t picles_stat_reset(picles_ctx *ctx);
+int32_t picles_stat_free(picles_ctx *ctx);
 
 /* particles (own rows; z is 5 planes: lne, c̄x, c̄y, x, y). Any pointer may be NULL.
  * The state vector of a switched-off particle (on == 0) is dead storage: its content is unspecified. */

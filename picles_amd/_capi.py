@@ -101,9 +101,11 @@ LATTICE_LINEAR, LATTICE_SMOOTH3 = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 7
+ABI_VERSION = 8
 SLAB_ID_BYTES = 128
 PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
+
+STAT_PEAK, STAT_MEAN, STAT_EXCEED, STAT_ALL = 1, 2, 4, 7      # statistics groups (include/picles_hip.h "run statistics")
 
 ROWS_ALL, ROWS_EDGE, ROWS_INTERIOR = 0, 1, 2
 
@@ -169,6 +171,13 @@ SYMBOLS = {
     "picles_probe_pending": (C.c_int32, [_VP]),
     "picles_probe_shape": (C.c_int32, [_VP, c_int32_p, c_int32_p, c_int32_p]),
     "picles_probe_free": (C.c_int32, [_VP]),
+    "picles_stat_init": (C.c_int32, [_VP, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.c_int32]),
+    "picles_stat_shape": (C.c_int32, [_VP, c_int32_p, c_int32_p, c_double_p, c_int32_p, c_int32_p, C.POINTER(C.c_size_t)]),
+    "picles_stat_update": (C.c_int32, [_VP, _VP]),
+    "picles_stat_get": (C.c_int32, [_VP, C.c_int32, _VP, C.POINTER(C.c_int64), c_double_p, c_double_p]),
+    "picles_stat_set": (C.c_int32, [_VP, C.c_int32, _VP, C.c_int64, C.c_double, C.c_double]),
+    "picles_stat_reset": (C.c_int32, [_VP]),
+    "picles_stat_free": (C.c_int32, [_VP]),
     "picles_get_particles": (C.c_int32, [_VP, c_double_p, c_uint8_p, c_uint8_p, c_int32_p]),
     "picles_set_particles": (C.c_int32, [_VP, c_double_p, c_uint8_p]),
     "picles_get_counters": (C.c_int32, [_VP, C.POINTER(PiclesCounters)]),

@@ -57,6 +57,7 @@
 #include "kernels.h"
 #include "k_diag.h"
 #include "k_probe.h"
+#include "k_stat.h"
 
 /* ------------------------------------------------------------------------------------------
  * k_seed — init_particles! / SeedParticle / InitParticleValues / init_z0_to_State!
@@ -514,6 +515,20 @@ struct picles_ctx {
     std::vector<hipEvent_t> probe_ready, probe_done;
     std::vector<double> probe_time;
     std::vector<long long> probe_step;
+    /* run statistics (picles_stat_*): one device block of accumulator planes — the fp64 planes of the selected groups first (PEAK,
+     * then MEAN), then the uint32 planes (n_wet, then n_exc[k]) —, the host-side scalars, and the event behind the latest
+     * operation on the planes (update, reset, upload): operations on another stream wait for it, and so does picles_stat_get */
+    bool stat_on = false;
+    StatP stat{};
+    int stat_every = 1, stat_first = 1;
+    long long stat_steps = 0;                      /* model steps completed since picles_stat_init */
+    long long stat_samples = 0;
+    double stat_t_first = 0.0, stat_t_last = 0.0;
+    unsigned char *stat_dev = nullptr;
+    size_t stat_bytes = 0;
+    hipEvent_t stat_ev = nullptr;
+    hipStream_t stat_stream = nullptr;             /* the stream stat_ev was recorded on */
+    bool stat_ev_live = false;
     /* gridded winds */
     bool wind_grid_on = false;
     WindGrid wg{};
@@ -622,6 +637,13 @@ static int probe_room(picles_ctx *c, long long n_steps, const char *who);
 static int probe_take(picles_ctx *c, hipStream_t s);
 static bool probe_due(const picles_ctx *c, long long s);
 static void probe_release(picles_ctx *c);
+/* run statistics (defined behind the station probes) */
+static int stat_update(picles_ctx *c, hipStream_t s);
+static void stat_release(picles_ctx *c);
+static inline bool stat_due(const picles_ctx *c, long long s)
+{
+    return s >= c->stat_first && (s - c->stat_first) % c->stat_every == 0;
+}
 
 /* scatter + remesh of the last fused step, if still outstanding */
 static int flush(picles_ctx *c)
@@ -849,6 +871,8 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     for (auto e : c->diag_ready) hipEventDestroy(e);
     for (auto e : c->diag_done) hipEventDestroy(e);
     probe_release(c);
+    if (c->stat_on) hipDeviceSynchronize();     /* updates issued on caller streams read and write the planes about to go */
+    stat_release(c);
     if (c->ck_dev) hipFree(c->ck_dev);
     if (c->ck_host) hipHostFree(c->ck_host);
     if (c->ck_ready) hipEventDestroy(c->ck_ready);
@@ -1495,6 +1519,7 @@ PX_EXPORT int32_t picles_end_fused_step(picles_ctx *c)
     c->edge_pending = false;
     c->clock += c->step_dt;
     c->probe_steps++;
+    c->stat_steps++;
     return 0;
 }
 
@@ -1552,6 +1577,7 @@ PX_EXPORT int32_t picles_scatter_remesh(picles_ctx *c, void *stream)
     if (rc) return rc;
     c->clock += c->step_dt;
     c->probe_steps++;
+    c->stat_steps++;
     return 0;
 }
 
@@ -1582,7 +1608,9 @@ PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
     if (rc) return rc;
     /* the sample of this step: directly behind its launch on the context stream.  The next step's launch reads the record buffer
      * the probe reads and writes the other one: stream order is all the ordering there is */
-    if (c->probe_n && probe_due(c, c->probe_steps)) return probe_take(c, c->stream);
+    if (c->probe_n && probe_due(c, c->probe_steps)) { if ((rc = probe_take(c, c->stream))) return rc; }
+    /* the statistics update of this step: the same place, the same ordering */
+    if (c->stat_on && stat_due(c, c->stat_steps)) return stat_update(c, c->stream);
     return 0;
 }
 
@@ -2097,6 +2125,205 @@ PX_EXPORT int32_t picles_probe_free(picles_ctx *c)
     return 0;
 }
 
+/* ---- run statistics (the contract: include/picles_hip.h; the kernel: k_stat.h) ---- */
+static inline int stat_nf64(const StatP &S) { return ((S.mask & PICLES_STAT_PEAK) ? 4 : 0) + ((S.mask & PICLES_STAT_MEAN) ? 4 : 0); }
+static inline int stat_nu32(const StatP &S) { return 1 + ((S.mask & PICLES_STAT_EXCEED) ? S.nthr : 0); }
+
+/* the planes of the groups in `mask` (a subset of the set's; n_wet always), in the order of the device block: offset and bytes of
+ * each contiguous piece */
+static int stat_pieces(const picles_ctx *c, unsigned mask, size_t off[4], size_t len[4])
+{
+    const size_t N = (size_t)c->A.n;
+    const bool peak = c->stat.mask & PICLES_STAT_PEAK;
+    const size_t u32_0 = (size_t)stat_nf64(c->stat) * N * 8;
+    int n = 0;
+    if (mask & PICLES_STAT_PEAK) { off[n] = 0; len[n++] = 4 * N * 8; }
+    if (mask & PICLES_STAT_MEAN) { off[n] = peak ? 4 * N * 8 : 0; len[n++] = 4 * N * 8; }
+    off[n] = u32_0; len[n++] = N * 4;
+    if (mask & PICLES_STAT_EXCEED) { off[n] = u32_0 + N * 4; len[n++] = (size_t)c->stat.nthr * N * 4; }
+    return n;
+}
+
+/* an operation on the planes, on stream s: behind the latest one wherever that ran */
+static int stat_order(picles_ctx *c, hipStream_t s)
+{
+    if (c->stat_ev_live && c->stat_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->stat_ev, 0));
+    return 0;
+}
+static int stat_mark(picles_ctx *c, hipStream_t s)
+{
+    HIPCHK(c, hipEventRecord(c->stat_ev, s));
+    c->stat_stream = s;
+    c->stat_ev_live = true;
+    return 0;
+}
+
+/* one update, on stream s — the stream behind which everything the sample depends on has been ordered.  With a fused step pending
+ * the samples come from its records, with the arrays and reach indices flush() would hand k_scatter at this moment (probe_take) */
+static int stat_update(picles_ctx *c, hipStream_t s)
+{
+    { int rc = stat_order(c, s); if (rc) return rc; }
+    const size_t N = (size_t)c->A.n;
+    double *f64 = (double *)c->stat_dev;
+    double *peak = (c->stat.mask & PICLES_STAT_PEAK) ? f64 : nullptr;
+    double *mean = (c->stat.mask & PICLES_STAT_MEAN) ? f64 + (peak ? 4 * N : 0) : nullptr;
+    unsigned int *n_wet = (unsigned int *)(c->stat_dev + (size_t)stat_nf64(c->stat) * N * 8);
+    unsigned int *n_exc = (c->stat.mask & PICLES_STAT_EXCEED) ? n_wet + N : nullptr;
+    const dim3 grid(nblocks(c->A.n, PICLES_BLOCK)), block(PICLES_BLOCK);
+    if (c->pending)
+        hipLaunchKernelGGL(k_stat<true>, grid, block, 0, s, c->G, arrays_for(c, c->cur, c->cur), c->stat, c->clock, n_wet, peak, mean, n_exc);
+    else
+        hipLaunchKernelGGL(k_stat<false>, grid, block, 0, s, c->G, c->A, c->stat, c->clock, n_wet, peak, mean, n_exc);
+    HIPCHK(c, hipGetLastError());
+    { int rc = stat_mark(c, s); if (rc) return rc; }
+    if (c->stat_samples == 0) c->stat_t_first = c->clock;
+    c->stat_t_last = c->clock;
+    c->stat_samples++;
+    return 0;
+}
+
+static void stat_release(picles_ctx *c)
+{
+    if (c->stat_dev) hipFree(c->stat_dev);
+    if (c->stat_ev) hipEventDestroy(c->stat_ev);
+    c->stat_dev = nullptr; c->stat_ev = nullptr; c->stat_stream = nullptr; c->stat_ev_live = false;
+    c->stat_on = false; c->stat = StatP{}; c->stat_bytes = 0;
+    c->stat_every = 1; c->stat_first = 1; c->stat_steps = 0;
+    c->stat_samples = 0; c->stat_t_first = 0.0; c->stat_t_last = 0.0;
+}
+
+PX_EXPORT int32_t picles_stat_init(picles_ctx *c, int32_t group_mask, int32_t n_thresholds, const double *thresholds, int32_t every,
+                                   int32_t first)
+{
+    if (!c) return -1;
+    if (c->stat_on) return fail(c, -2, "picles_stat_init: a statistics set exists (picles_stat_free first)");
+    if (group_mask <= 0 || (group_mask & ~PICLES_STAT_ALL)) return fail(c, -2, "picles_stat_init: empty or unknown group mask");
+    if (every < 1 || first < 1) return fail(c, -2, "picles_stat_init: every and first must be >= 1");
+    if (group_mask & PICLES_STAT_EXCEED) {
+        if (n_thresholds < 1 || n_thresholds > STAT_MAX_THR || !thresholds)
+            return fail(c, -2, "picles_stat_init: PICLES_STAT_EXCEED takes 1 ... 4 thresholds");
+        for (int k = 0; k < n_thresholds; k++)
+            if (!std::isfinite(thresholds[k]) || !(thresholds[k] > 0.0) || (k > 0 && !(thresholds[k] > thresholds[k - 1])))
+                return fail(c, -2, "picles_stat_init: thresholds must be finite, positive and strictly ascending");
+    } else if (n_thresholds != 0) {
+        return fail(c, -2, "picles_stat_init: thresholds given without PICLES_STAT_EXCEED");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    StatP S{};
+    S.mask = (unsigned)group_mask;
+    S.nthr = n_thresholds;
+    for (int k = 0; k < n_thresholds; k++) S.thr[k] = thresholds[k];
+    const size_t bytes = (size_t)c->A.n * ((size_t)stat_nf64(S) * 8 + (size_t)stat_nu32(S) * 4);
+    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) stat_release(c); } } undo{c, true};
+    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    HIPCHK(c, hipMalloc(&c->stat_dev, bytes));
+    HIPCHK(c, hipEventCreateWithFlags(&c->stat_ev, hipEventDisableTiming));
+    HIPCHK(c, hipMemsetAsync(c->stat_dev, 0, bytes, c->stream));
+    c->stat = S; c->stat_bytes = bytes;
+    { int rc = stat_mark(c, c->stream); if (rc) return rc; }
+    c->stat_every = every; c->stat_first = first; c->stat_steps = 0;
+    c->stat_samples = 0; c->stat_t_first = 0.0; c->stat_t_last = 0.0;
+    c->stat_on = true;
+    undo.armed = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_stat_shape(const picles_ctx *c, int32_t *group_mask, int32_t *n_thresholds, double *thresholds, int32_t *every,
+                                    int32_t *n_planes, size_t *bytes)
+{
+    if (!c || !c->stat_on) return -1;
+    if (group_mask) *group_mask = (int32_t)c->stat.mask;
+    if (n_thresholds) *n_thresholds = c->stat.nthr;
+    if (thresholds) for (int k = 0; k < c->stat.nthr; k++) thresholds[k] = c->stat.thr[k];
+    if (every) *every = c->stat_every;
+    if (n_planes) *n_planes = stat_nf64(c->stat) + stat_nu32(c->stat);
+    if (bytes) *bytes = c->stat_bytes;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_stat_update(picles_ctx *c, void *stream)
+{
+    if (!c) return -1;
+    if (!c->stat_on) return fail(c, -2, "picles_stat_init first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (stream) c->ext_streams = true;
+    return stat_update(c, stream ? (hipStream_t)stream : c->stream);
+}
+
+static int stat_mask_ok(picles_ctx *c, int32_t group_mask, const char *who)
+{
+    if (group_mask < 0 || (group_mask & ~(int32_t)c->stat.mask))
+        return fail(c, -2, std::string(who) + ": group mask is no subset of the set's");
+    return 0;
+}
+
+PX_EXPORT int32_t picles_stat_get(picles_ctx *c, int32_t group_mask, void *planes, int64_t *n_samples, double *t_first, double *t_last)
+{
+    if (!c) return -1;
+    if (!c->stat_on) return fail(c, -2, "picles_stat_init first");
+    if (!planes) return fail(c, -2, "picles_stat_get: planes must be given");
+    { int rc = stat_mask_ok(c, group_mask, "picles_stat_get"); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    /* the latest operation on the planes alone: the copy rides the store stream behind its event; a pending step stays pending */
+    HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->stat_ev, 0));
+    size_t off[4], len[4], at = 0;
+    const int n = stat_pieces(c, (unsigned)group_mask, off, len);
+    for (int k = 0; k < n; k++) {
+        HIPCHK(c, hipMemcpyAsync((unsigned char *)planes + at, c->stat_dev + off[k], len[k], hipMemcpyDeviceToHost, c->store_stream));
+        at += len[k];
+    }
+    HIPCHK(c, hipStreamSynchronize(c->store_stream));      /* the caller's (pageable) buffer is complete and released */
+    if (n_samples) *n_samples = (int64_t)c->stat_samples;
+    if (t_first) *t_first = c->stat_t_first;
+    if (t_last) *t_last = c->stat_t_last;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_stat_set(picles_ctx *c, int32_t group_mask, const void *planes, int64_t n_samples, double t_first, double t_last)
+{
+    if (!c) return -1;
+    if (!c->stat_on) return fail(c, -2, "picles_stat_init first");
+    if (!planes) return fail(c, -2, "picles_stat_set: planes must be given");
+    if (n_samples < 0) return fail(c, -2, "picles_stat_set: n_samples must be >= 0");
+    { int rc = stat_mask_ok(c, group_mask, "picles_stat_set"); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = stat_order(c, c->stream); if (rc) return rc; }
+    size_t off[4], len[4], at = 0;
+    const int n = stat_pieces(c, (unsigned)group_mask, off, len);
+    for (int k = 0; k < n; k++) {
+        HIPCHK(c, hipMemcpyAsync(c->stat_dev + off[k], (const unsigned char *)planes + at, len[k], hipMemcpyHostToDevice, c->stream));
+        at += len[k];
+    }
+    { int rc = stat_mark(c, c->stream); if (rc) return rc; }
+    HIPCHK(c, hipEventSynchronize(c->stat_ev));            /* the caller's buffer has been read to its last byte */
+    c->stat_samples = (long long)n_samples; c->stat_t_first = t_first; c->stat_t_last = t_last;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_stat_reset(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->stat_on) return fail(c, -2, "picles_stat_init first");
+    HIPCHK(c, hipSetDevice(c->device));
+    /* in stream order behind the updates already issued, wherever they ran; no host synchronisation */
+    hipStream_t s = c->stream;
+    { int rc = stat_order(c, s); if (rc) return rc; }
+    HIPCHK(c, hipMemsetAsync(c->stat_dev, 0, c->stat_bytes, s));
+    { int rc = stat_mark(c, s); if (rc) return rc; }
+    c->stat_samples = 0; c->stat_t_first = 0.0; c->stat_t_last = 0.0;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_stat_free(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->stat_on) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());       /* updates in flight read and write the planes about to go */
+    stat_release(c);
+    return 0;
+}
+
 /* ---- halo blocks ---- */
 PX_EXPORT int32_t picles_halo_rows(const picles_ctx *c) { return c ? c->G.R : -1; }
 
@@ -2363,7 +2590,7 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
     if (flags & PICLES_STEP_ATOMIC) return fail(c, -5, "PICLES_STEP_ATOMIC is single-slab only");
     { int rc = probe_room(c, n_steps, "picles_slab_run_steps"); if (rc) return rc; }      /* up front: nothing has changed yet */
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->probe_n && !R->sP) {
+    if ((c->probe_n || c->stat_on) && !R->sP) {
         HIPCHK(c, hipStreamCreateWithFlags(&R->sP, hipStreamNonBlocking));
         for (hipEvent_t *e : {&R->evPx, &R->evPm, &R->evP[0], &R->evP[1]}) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
@@ -2426,7 +2653,9 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
         rc = (fused == 0) ? picles_step_rows(c, PICLES_ROWS_INTERIOR, R->sM) : picles_advance_rows(c, PICLES_ROWS_INTERIOR, R->sM);
         if (rc) return rc;
         if (phases) { HIPCHK(c, hipEventRecord(pe.m1, R->sM)); R->ph_used.push_back(pe); }
-        const bool sample = c->probe_n && probe_due(c, c->probe_steps + 1);
+        const bool probe = c->probe_n && probe_due(c, c->probe_steps + 1);
+        const bool stat = c->stat_on && stat_due(c, c->stat_steps + 1);      /* the statistics update: ordered exactly as a probe */
+        const bool sample = probe || stat;
         if (sample && fused == 0) {      /* what the probe of a fused step waits for: the interior launch and the delivered halo */
             HIPCHK(c, hipEventRecord(R->evPm, R->sM));
             HIPCHK(c, hipEventRecord(R->evPx, R->sE));
@@ -2449,11 +2678,13 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
              * — on the side stream, so that stream M never waits for the exchange */
             HIPCHK(c, hipStreamWaitEvent(R->sP, R->evPm, 0));
             HIPCHK(c, hipStreamWaitEvent(R->sP, R->evPx, 0));
-            if ((rc = probe_take(c, R->sP))) return rc;
+            if (probe && (rc = probe_take(c, R->sP))) return rc;
+            if (stat && (rc = stat_update(c, R->sP))) return rc;
             HIPCHK(c, hipEventRecord(R->evP[c->cur], R->sP));
             R->evP_live[c->cur] = true;
         } else if (sample) {
-            if ((rc = probe_take(c, R->sM))) return rc;      /* State is in memory: gathered on the stream that ran the scatter */
+            if (probe && (rc = probe_take(c, R->sM))) return rc;      /* State is in memory: gathered on the stream that ran the scatter */
+            if (stat && (rc = stat_update(c, R->sM))) return rc;
         }
         R->steps++;
     }

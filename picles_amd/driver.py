@@ -67,6 +67,77 @@ def combine_partials(list_of_partials, Nx, Ny) -> dict:
 
 SCALAR_NAMES = K.DIAG_PARTIAL + ("mean_of_state",)
 
+# ---- run statistics: the plane block of picles_stat_get / picles_stat_set (include/picles_hip.h "run statistics") ----
+STAT_GROUPS = {"peak": K.STAT_PEAK, "mean": K.STAT_MEAN, "exceed": K.STAT_EXCEED}
+STAT_PEAK_PLANES = ("e_peak", "mx_peak", "my_peak", "t_peak")
+STAT_MEAN_PLANES = ("sum_e", "sum_mx", "sum_my", "sum_hs")
+
+
+def stat_mask(groups, allow_empty=False) -> int:
+    """group names (or a ready bit mask) -> PICLES_STAT_* bit mask; refuses what the library would refuse"""
+    if isinstance(groups, (int, np.integer)):
+        mask = int(groups)
+    else:
+        if isinstance(groups, str):
+            groups = (groups,)
+        unknown = [g for g in groups if g not in STAT_GROUPS]
+        if unknown:
+            raise ValueError(f"unknown statistics groups {unknown}: choose from {tuple(STAT_GROUPS)}")
+        mask = 0
+        for g in groups:
+            mask |= STAT_GROUPS[g]
+    if mask < 0 or (mask & ~K.STAT_ALL) or (mask == 0 and not allow_empty):
+        raise ValueError(f"empty or unknown statistics group mask {mask}")
+    return mask
+
+
+def stat_layout(mask, n_thresholds):
+    """[(name, dtype, planes)] of the plane block for `mask`, in its order: the fp64 planes first, then the uint32 ones"""
+    lay = []
+    if mask & K.STAT_PEAK:
+        lay += [(n, np.float64, 1) for n in STAT_PEAK_PLANES]
+    if mask & K.STAT_MEAN:
+        lay += [(n, np.float64, 1) for n in STAT_MEAN_PLANES]
+    lay.append(("n_wet", np.uint32, 1))
+    if mask & K.STAT_EXCEED:
+        lay.append(("n_exc", np.uint32, int(n_thresholds)))
+    return lay
+
+
+def stat_mask_of(acc) -> int:
+    return ((K.STAT_PEAK if "e_peak" in acc else 0) | (K.STAT_MEAN if "sum_e" in acc else 0) | (K.STAT_EXCEED if "n_exc" in acc else 0))
+
+
+def stat_unpack(buf, lay, Nx, ny):
+    """plane block (bytes) -> {name: (Nx, ny) plane, "n_exc": (Nx, ny, n_thresholds)}, column-major like State"""
+    out, at, N = {}, 0, Nx * ny
+    for name, dt, k in lay:
+        nb = np.dtype(dt).itemsize * N * k
+        a = np.frombuffer(buf, dtype=dt, count=N * k, offset=at).copy()
+        out[name] = a.reshape((Nx, ny) + ((k,) if name == "n_exc" else ()), order="F")
+        at += nb
+    return out
+
+
+def stat_pack(acc, lay, Nx, ny):
+    parts = []
+    for name, dt, k in lay:
+        a = np.asarray(acc[name], dtype=dt)
+        if a.shape != (Nx, ny) + ((k,) if name == "n_exc" else ()):
+            raise ValueError(f"statistics plane {name}: shape {a.shape}, expected {(Nx, ny) + ((k,) if name == 'n_exc' else ())}")
+        parts.append(np.ascontiguousarray(a.reshape(-1, order="F")).view(np.uint8))
+    return np.ascontiguousarray(np.concatenate(parts))
+
+
+def stat_concat(list_of_acc):
+    """the accumulators of the whole grid from those of its slabs, in rank order: per-node values do not depend on the
+    decomposition, so the gather is a concatenation of row blocks; the scalars are every slab's (taken from the first)"""
+    first = list_of_acc[0]
+    out = {}
+    for k, v in first.items():
+        out[k] = np.concatenate([a[k] for a in list_of_acc], axis=1) if isinstance(v, np.ndarray) and v.ndim >= 2 else v
+    return out
+
 _live = weakref.WeakSet()
 
 
@@ -436,6 +507,56 @@ class HipModel:
 
     def probe_free(self):
         self._ck(self.lib.picles_probe_free(self.h), "picles_probe_free")
+
+    # ---- run statistics (picles_stat_*: per-node peak / mean / exceedance accumulators kept on the device, the fused path kept) ----
+    def stat_init(self, groups=K.STAT_ALL, thresholds=(), every=1, first=1):
+        """groups: PICLES_STAT_* bits or names ("peak", "mean", "exceed"); thresholds: 1 ... 4 ascending Hs values with "exceed";
+        an update follows every model step s (counted from here) with s >= first and (s - first) % every == 0"""
+        mask = stat_mask(groups)
+        thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).ravel())
+        self._ck(self.lib.picles_stat_init(self.h, mask, int(thr.size), K.dptr(thr) if thr.size else None, int(every), int(first)),
+                 "picles_stat_init")
+
+    def stat_shape(self):
+        """(mask, thresholds, every, n_planes, bytes) of the statistics set; no device work"""
+        m, nt, ev, npl = (C.c_int32() for _ in range(4))
+        thr = (C.c_double * 4)()
+        b = C.c_size_t()
+        if self.lib.picles_stat_shape(self.h, C.byref(m), C.byref(nt), thr, C.byref(ev), C.byref(npl), C.byref(b)) != 0:
+            raise K.PiclesError("picles_stat_shape failed: stat_init first")
+        return m.value, tuple(thr[k] for k in range(nt.value)), ev.value, npl.value, b.value
+
+    def stat_update(self, stream=None):
+        """one update now (the seeded state; callers of the split-phase API, on the stream their step is ordered on)"""
+        self._ck(self.lib.picles_stat_update(self.h, stream), "picles_stat_update")
+
+    def stat_get(self, groups=None):
+        """the accumulators of the selected groups (all of the set's when None) as a dict of (Nx, ny_loc) planes — "n_exc" is
+        (Nx, ny_loc, n_thresholds) — with "n_samples", "t_first", "t_last"; a pending fused step stays pending"""
+        set_mask, thr, _, _, _ = self.stat_shape()
+        mask = set_mask if groups is None else stat_mask(groups, allow_empty=True)
+        lay = stat_layout(mask, len(thr))
+        buf = np.empty(sum(np.dtype(dt).itemsize * k for _, dt, k in lay) * self.N, dtype=np.uint8)
+        n, t0, t1 = C.c_int64(), C.c_double(), C.c_double()
+        self._ck(self.lib.picles_stat_get(self.h, mask, buf.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(t0), C.byref(t1)),
+                 "picles_stat_get")
+        out = stat_unpack(buf, lay, self.Nx, self.ny_loc)
+        out.update(n_samples=int(n.value), t_first=float(t0.value), t_last=float(t1.value), thresholds=np.asarray(thr), mask=mask)
+        return out
+
+    def stat_set(self, acc):
+        """upload what stat_get returned (the groups it holds): how a picked-up run continues its open window"""
+        _, thr, _, _, _ = self.stat_shape()
+        mask = int(acc["mask"]) if "mask" in acc else stat_mask_of(acc)
+        buf = stat_pack(acc, stat_layout(mask, len(thr)), self.Nx, self.ny_loc)
+        self._ck(self.lib.picles_stat_set(self.h, mask, buf.ctypes.data_as(C.c_void_p), int(acc["n_samples"]), float(acc["t_first"]),
+                                          float(acc["t_last"])), "picles_stat_set")
+
+    def stat_reset(self):
+        self._ck(self.lib.picles_stat_reset(self.h), "picles_stat_reset")
+
+    def stat_free(self):
+        self._ck(self.lib.picles_stat_free(self.h), "picles_stat_free")
 
     # ---- exact restart (picles_checkpoint_*) ----
     def checkpoint_size(self) -> int:

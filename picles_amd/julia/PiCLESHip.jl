@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(7)
+const PICLES_ABI_VERSION = Int32(8)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -489,6 +489,77 @@ function probe_pop!(model::WaveGrowth2DHIP; max_samples::Integer=typemax(Int32))
 end
 
 probe_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_probe_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_probe_free")
+
+const PICLES_STAT_PEAK, PICLES_STAT_MEAN, PICLES_STAT_EXCEED = Int32(1), Int32(2), Int32(4)
+
+"""
+    stat_init!(model; peak=true, mean=true, thresholds=Float64[], every=1, first=1)
+
+Run statistics (`picles_stat_*`, the contract is in include/picles_hip.h): per-node accumulators of every node, kept in device
+memory and updated behind every model step `s` with `s >= first` and `(s - first) % every == 0` — from the scatter records of the
+pending fused step, which stays pending.  `thresholds` (1 ... 4 ascending Hs values) selects the exceedance counts.  `stat_get`
+returns the planes as a `Dict` of `Nx x Ny` arrays (`:n_exc` is `Nx x Ny x length(thresholds)`) with `:n_samples`, `:t_first`,
+`:t_last`; `stat_set!` uploads such a `Dict` (a picked-up run continues its window); `stat_reset!` zeroes; `stat_free!` drops the set.
+"""
+function stat_init!(model::WaveGrowth2DHIP; peak::Bool=true, mean::Bool=true, thresholds=Float64[], every::Integer=1, first::Integer=1)
+    thr = Vector{Float64}(thresholds)
+    mask = (peak ? PICLES_STAT_PEAK : Int32(0)) | (mean ? PICLES_STAT_MEAN : Int32(0)) | (isempty(thr) ? Int32(0) : PICLES_STAT_EXCEED)
+    check(model.ctx, ccall((:picles_stat_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int32, Int32), model.ctx, mask, length(thr), thr, every, first), "picles_stat_init")
+    nothing
+end
+
+function stat_shape(model::WaveGrowth2DHIP)
+    mask, nthr, every, npl = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    thr = zeros(Float64, 4)
+    bytes = Ref{Csize_t}(0)
+    ccall((:picles_stat_shape, libpicles), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ptr{Float64}, Ref{Int32}, Ref{Int32}, Ref{Csize_t}), model.ctx, mask, nthr, thr, every, npl, bytes) == 0 ||
+        error("picles_stat_shape failed: stat_init! first")
+    (mask = mask[], thresholds = thr[1:nthr[]], every = every[], n_planes = npl[], bytes = Int(bytes[]))
+end
+
+stat_update!(model::WaveGrowth2DHIP) =
+    check(model.ctx, ccall((:picles_stat_update, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), model.ctx, C_NULL), "picles_stat_update")
+
+# the plane block of picles_stat_get / picles_stat_set: fp64 planes first, then the uint32 ones
+function stat_layout(mask::Integer, nthr::Integer)
+    lay = Tuple{Symbol,DataType,Int}[]
+    mask & PICLES_STAT_PEAK != 0 && append!(lay, [(s, Float64, 1) for s in (:e_peak, :mx_peak, :my_peak, :t_peak)])
+    mask & PICLES_STAT_MEAN != 0 && append!(lay, [(s, Float64, 1) for s in (:sum_e, :sum_mx, :sum_my, :sum_hs)])
+    push!(lay, (:n_wet, UInt32, 1))
+    mask & PICLES_STAT_EXCEED != 0 && push!(lay, (:n_exc, UInt32, Int(nthr)))
+    lay
+end
+
+function stat_get(model::WaveGrowth2DHIP)
+    sh = stat_shape(model)
+    Nx, Ny = size(model.State, 1), size(model.State, 2)
+    buf = Vector{UInt8}(undef, sh.bytes)
+    n, t0, t1 = Ref{Int64}(0), Ref{Float64}(0.0), Ref{Float64}(0.0)
+    check(model.ctx, ccall((:picles_stat_get, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ref{Int64}, Ref{Float64}, Ref{Float64}), model.ctx, sh.mask, buf, n, t0, t1), "picles_stat_get")
+    out = Dict{Symbol,Any}(:n_samples => n[], :t_first => t0[], :t_last => t1[], :thresholds => sh.thresholds, :mask => sh.mask)
+    at = 0
+    for (name, T, k) in stat_layout(sh.mask, length(sh.thresholds))
+        nb = sizeof(T) * Nx * Ny * k
+        a = collect(reinterpret(T, view(buf, at + 1:at + nb)))
+        out[name] = name == :n_exc ? reshape(a, Nx, Ny, k) : reshape(a, Nx, Ny)
+        at += nb
+    end
+    out
+end
+
+function stat_set!(model::WaveGrowth2DHIP, acc::Dict{Symbol,Any})
+    sh = stat_shape(model)
+    buf = UInt8[]
+    for (name, T, k) in stat_layout(sh.mask, length(sh.thresholds))
+        append!(buf, reinterpret(UInt8, vec(Array{T}(acc[name]))))
+    end
+    length(buf) == sh.bytes || error("stat_set!: the planes do not fill the set's plane block")
+    check(model.ctx, ccall((:picles_stat_set, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Float64, Float64), model.ctx, sh.mask, buf, Int64(acc[:n_samples]), Float64(acc[:t_first]), Float64(acc[:t_last])), "picles_stat_set")
+    nothing
+end
+
+stat_reset!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_stat_reset, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_stat_reset")
+stat_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_stat_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_stat_free")
 
 """
     checkpoint!(model, path; iteration = model.clock.iteration)

@@ -405,6 +405,7 @@ class SlabModel:
         self.clock += dt
         self._steps_done += 1
         self._probe_after_steps(1, split_phase=not self.native and self.ex is not None)
+        self._stat_after_steps(1, split_phase=not self.native and self.ex is not None)
         if self.auto_halo_every > 0 and self.world > 1 and self._steps_done % self.auto_halo_every == 0:
             self.grow_halo_if_needed()
 
@@ -428,6 +429,7 @@ class SlabModel:
         self.clock += n * dt
         self._steps_done += n
         self._probe_after_steps(n, split_phase=False)
+        self._stat_after_steps(n, split_phase=False)
 
     def check_overflow(self):
         """raise if any particle travelled beyond the ghost rows (it was not scattered: the State is incomplete)"""
@@ -598,6 +600,56 @@ class SlabModel:
         parts = [None] * self.world
         dist.all_gather_object(parts, part)
         return assemble_probes(self._probe["n"], parts)
+
+    # ---- run statistics: every rank accumulates over its own rows (picles_stat_*) ----
+    def stat_init(self, groups=("peak", "mean", "exceed"), thresholds=(), every=1, first=1):
+        """the same set on every rank.  The native ring, picles_run_steps and picles_time_step update by themselves; the
+        Python-driven split-phase loop calls picles_stat_update behind the halo exchange of every due step."""
+        if every < 1 or first < 1:
+            raise ValueError("stat_init: every and first must be >= 1")
+        self.backend.stat_init(groups, thresholds, every=every, first=first)
+        self._stat = dict(every=int(every), first=int(first), steps=0)
+
+    def _stat_after_steps(self, n, split_phase):
+        p = getattr(self, "_stat", None)
+        if p is None:
+            return
+        p["steps"] += n
+        s = p["steps"]
+        if split_phase and s >= p["first"] and (s - p["first"]) % p["every"] == 0:
+            # the step's launches and its delivered halo are ordered on the interior stream (or on the context stream)
+            self.backend.stat_update(self.s_main.cuda_stream if self.use_streams else None)
+
+    def stat_update(self):
+        """one update now on every rank (the seeded state)"""
+        self.sync()
+        self.backend.stat_update()
+
+    def stat_get(self, groups=None):
+        return self.backend.stat_get(groups)
+
+    def stat_set(self, acc):
+        self.backend.stat_set(acc)
+
+    def stat_reset(self):
+        self.backend.stat_reset()
+
+    def stat_free(self):
+        if getattr(self, "_stat", None) is not None:
+            self.backend.stat_free()
+        self._stat = None
+
+    def gather_stats(self, groups=None):
+        """this rank's accumulators and all ranks', concatenated along y in rank order.  Per-node accumulators involve no
+        arithmetic across nodes: the result is bitwise what a whole-grid context gives, whatever the decomposition."""
+        from .driver import stat_concat
+        part = self.backend.stat_get(groups)
+        if self.world == 1:
+            return part
+        import torch.distributed as dist
+        parts = [None] * self.world
+        dist.all_gather_object(parts, part)
+        return stat_concat(parts)
 
     def gather_state(self):
         """all ranks' slabs concatenated along y (host; for tests)"""

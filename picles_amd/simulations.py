@@ -95,13 +95,20 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
     if store and not isinstance(sim.store, (StateStore, NpyStateStore)):
         raise ValueError("call init_state_store(sim, path) before run(sim, store=True)")
     ring = store and hasattr(sim.model.backend, "store_init")
+    from .run_statistics import find_statistics_writer
+    stw = find_statistics_writer(sim)
+    if stw is not None and not hasattr(sim.model.backend, "stat_init"):
+        raise NotImplementedError("a StatisticsWriter needs a backend with stat_init / stat_get / stat_reset (the HIP library)")
     if pickup is not False and pickup is not None:
         from .checkpointing import load_checkpoint, resolve_pickup
-        load_checkpoint(sim.model, resolve_pickup(sim, pickup), sim.Δt)
+        picked = resolve_pickup(sim, pickup)
+        load_checkpoint(sim.model, picked, sim.Δt)
         sim.initialized = True
+        if stw is not None:
+            stw.load_sidecar(picked)           # the open window of the run that wrote the checkpoint (uploaded by begin_run)
     if not sim.initialized:
         initialize_simulation(sim)
-    from .checkpointing import find_checkpointer
+    from .checkpointing import checkpoint_path, find_checkpointer
     ckpt = find_checkpointer(sim)
     if ckpt is not None and not hasattr(sim.model.backend, "checkpoint_begin"):
         raise NotImplementedError("a Checkpointer needs a backend with checkpoint_begin / checkpoint_end (the HIP library)")
@@ -130,8 +137,8 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         # nothing observes State between the steps: enqueue the whole loop from C in one call
         import math
         n = int(math.floor((sim.stop_time - m.clock.time) / sim.Δt)) + 1 if sim.running else 0   # run.jl:113: one step past stop_time
-        if n > 0 and (ckpt is not None or fw is not None or sw is not None):
-            # chunks that end on the next output or checkpoint iteration or where the probe ring would fill, whichever is first:
+        if n > 0 and (ckpt is not None or fw is not None or sw is not None or stw is not None):
+            # chunks that end on the next output, checkpoint or statistics-window iteration or where the probe ring would fill, whichever is first:
             # the snapshot of chunk k is copied out and written — and the station samples of chunk k-1 are — while chunk k+1 runs
             m.upload_winds(m.clock.time, sim.Δt)
             time0, it0, done = m.clock.time, m.clock.iteration, 0
@@ -139,10 +146,14 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
                 fw.begin_run(m, n)                      # the record of the first iteration
             if sw is not None:
                 sw.begin_run(m, n)
+            if stw is not None:
+                stw.begin_run(m, n)
             while done < n:
                 k = n - done
                 if ckpt is not None or fw is not None:
                     k = min(k, min(w.schedule.next_after(it0 + done) for w in (ckpt, fw) if w is not None) - (it0 + done))
+                if stw is not None:
+                    k = min(k, stw.next_after(it0 + done) - (it0 + done))
                 earlier = 0
                 if sw is not None:
                     if sw.steps_allowed(m.backend, it0 + done) < 1:
@@ -157,8 +168,12 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
                 done += k
                 m.clock.time = time0 + done * sim.Δt
                 m.clock.iteration = it0 + done
+                if stw is not None:
+                    stw.after_steps(m.backend, m.clock.iteration)      # a window that ends here: get, write, reset
                 if ckpt is not None and ckpt.schedule(m.clock.iteration):
                     ckpt.begin(m.backend, m.clock.time, m.clock.iteration)
+                    if stw is not None:
+                        stw.save_sidecar(m.backend, checkpoint_path(ckpt.dir, ckpt.prefix, m.clock.iteration, ckpt.rank))
                 if fw is not None and fw.schedule(m.clock.iteration):
                     fw.push(m.backend, m.clock.iteration)
             if ckpt is not None:
@@ -169,16 +184,18 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
             m.clock.time += n * sim.Δt
             m.clock.iteration += n
         sim.running = False
-    if (fw is not None or sw is not None) and sim.running:
+    if (fw is not None or sw is not None or stw is not None) and sim.running:
         # the per-step loop (time-varying winds, stores): the writers need the number of steps for the size of their files
         import math
         if sim.stop_time == float("inf"):
-            raise ValueError("a FieldWriter or StationWriter needs a finite stop_time (its file is sized for the run)")
+            raise ValueError("a FieldWriter, StationWriter or StatisticsWriter needs a finite stop_time (its file is sized for the run)")
         n_loop = int(math.floor((sim.stop_time - sim.model.clock.time) / sim.Δt)) + 1
         if fw is not None:
             fw.begin_run(sim.model, n_loop)
         if sw is not None:
             sw.begin_run(sim.model, n_loop)
+        if stw is not None:
+            stw.begin_run(sim.model, n_loop)
     while sim.running:
         if sw is not None:
             sw.make_room(sim.model.backend)     # the library samples inside time_step and refuses a full ring
@@ -195,10 +212,14 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         if cash_store:
             sim.store.store.append(sim.model.State.copy())
             sim.store.iteration += 1
+        if stw is not None:
+            stw.after_steps(sim.model.backend, sim.model.clock.iteration)       # (the library updates inside time_step)
         if ckpt is not None:
             ckpt.finish(sim.model.backend)           # the previous step's snapshot: its copy-out ran beside this step
             if ckpt.schedule(sim.model.clock.iteration):
                 ckpt.begin(sim.model.backend, sim.model.clock.time, sim.model.clock.iteration)
+                if stw is not None:
+                    stw.save_sidecar(sim.model.backend, checkpoint_path(ckpt.dir, ckpt.prefix, sim.model.clock.iteration, ckpt.rank))
         if fw is not None and fw.schedule(sim.model.clock.iteration):
             fw.push(sim.model.backend, sim.model.clock.iteration)
         sim.running = sim.stop_time >= sim.model.clock.time
@@ -208,6 +229,8 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         fw.finish(sim.model.backend)
     if sw is not None:
         sw.finish(sim.model.backend)
+    if stw is not None:
+        stw.finish(sim.model.backend, sim.model.clock.iteration)
     if store:
         if ring:
             b = sim.model.backend
