@@ -3,8 +3,14 @@
 #include "k_step.inc"
 
 #define LAUNCH_STEP(F, T, S, M) hipLaunchKernelGGL((k_step<F, T, S, M, false>), L.grid, L.block, 0, L.stream, *L.P, *L.G, *L.A, L.t_prev, L.DT_prev, L.t_start, L.DT, L.r0, L.n0, L.r1, L.n1)
+#define LAUNCH_WROW(T, S) hipLaunchKernelGGL((k_step_waverow<true, T, S, false, false>), L.grid, L.block, 0, L.stream, *L.P, *L.G, *L.A, L.t_prev, L.DT_prev, L.t_start, L.DT, L.r0, L.n0, L.r1, L.n1)
 void launch_k_step_explicit(const StepLaunch &L, bool fast, int solver, bool wind_static, bool metric)
 {
+    if (L.waverow && waverow_flavour(fast, metric)) {     /* the wave-per-row form: DP5 and Tsit5, static and time-varying winds */
+        if (solver) { if (wind_static) LAUNCH_WROW(true, true); else LAUNCH_WROW(true, false); }
+        else { if (wind_static) LAUNCH_WROW(false, true); else LAUNCH_WROW(false, false); }
+        return;
+    }
     if (!fast) {     /* general physics: static winds, Cartesian (step_fusable) */
         if (solver) LAUNCH_STEP(false, true, true, false);
         else LAUNCH_STEP(false, false, true, false);

@@ -12,6 +12,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/picles_hip.h"
 #include "physics.h"
@@ -268,10 +269,15 @@ __device__ __forceinline__ KStepArgsPtr kargs_reload(void)      /* k_advance cas
 
 /* scatter record of one advanced particle (ParticleToNode! inputs): charge, upper-node weights and
  * the packed (list, cell offset) code, into the OUT buffer */
-__device__ __forceinline__ void write_record(const GridP &G, const Arrays &A, int i, int jl, unsigned char pf, int on,
-                                             const Vec5 &z, StepStats &S)
+/* rr: the particle's row of the OUT buffer, i: its column — or (k_step_waverow) rr: that row from the wave's first column on, a scalar,
+ * and i: the lane number, unsigned: each plane's base is then formed on the scalar unit and the lane's offset rides in the store */
+template <class IDX>
+__device__ __forceinline__ void write_record_at(const GridP &G, double *rr, IDX i, unsigned char pf, int on, const Vec5 &z, StepStats &S)
 {
-    double *rr = rec_row_out(A, G, jl + G.R);
+    auto at = [&](int plane) -> double & {
+        if constexpr (std::is_unsigned<IDX>::value) return (rr + (size_t)plane * (size_t)G.Nx)[i];
+        else return rr[plane * G.Nx + i];
+    };
     double code = 0.0;
     if (on && !(pm_isfinite(z.x) && pm_isfinite(z.y))) {
         S.nonfinite = 1;         /* the reference would throw in Int(floor(NaN)) (ParticleInCell.jl:58-71): dropped and counted */
@@ -288,18 +294,25 @@ __device__ __forceinline__ void write_record(const GridP &G, const Arrays &A, in
         int ry = (by < 0) ? -by : by + 1;
         S.reach = (r > ry) ? r : ry;
         if (S.reach <= ((G.Rp > 0) ? G.Rp : REACH_CAP)) {
-            rr[i] = e; rr[G.Nx + i] = mx; rr[2 * G.Nx + i] = my; rr[3 * G.Nx + i] = wx; rr[4 * G.Nx + i] = wy;
+            at(0) = e; at(1) = mx; at(2) = my; at(3) = wx; at(4) = wy;
             code = rec_encode((pf & PF_GROUP2) ? 2 : 1, bx, by);
         }
         else { S.overflow = 1; S.reach = 0; }     /* not scattered, not part of the reach the pull follows */
     }
-    rr[5 * G.Nx + i] = code;
+    at(5) = code;
+}
+__device__ __forceinline__ void write_record(const GridP &G, const Arrays &A, int i, int jl, unsigned char pf, int on,
+                                             const Vec5 &z, StepStats &S)
+{
+    write_record_at(G, rec_row_out(A, G, jl + G.R), i, pf, on, z, S);
 }
 
 /* statistics: one atomic per wave into the wave's slot.  The 0/1 flags are counted with a ballot +
  * scalar popcount (no cross-lane traffic), the step counters with two 64-bit butterfly sums
  * (accepted and rejected steps share one word), the reach with a ballot ladder. */
 /* rtile: the reach-map tile (t >> 6) of a lane whose particle left a record this step, -1 otherwise */
+/* WROW (k_step_waverow): the wave covers exactly one tile, the same in every lane that has one */
+template <bool WROW = false>
 __device__ __forceinline__ void flush_stats(const Arrays &A, const StepStats &S, int rtile = -1)
 {
     unsigned long long s_rhs = wave_sum_u64(S.st.rhs);
@@ -321,8 +334,14 @@ __device__ __forceinline__ void flush_stats(const Arrays &A, const StepStats &S,
         /* the wave's reach into the map entry of its tile.  A wave covers 64 consecutive particles: one tile when the launch is
          * aligned with the tiles (the row length a multiple of 64), two otherwise — the loop runs once or twice */
         int *const rm = A.rmap + (size_t)((A.mr_idx >> 4) & 15) * (size_t)A.ntile;
-        int mine = (S.reach > 0) ? rtile : -1;
-        unsigned long long todo = __ballot(mine >= 0);
+        if constexpr (WROW) {
+            /* one tile, and its reach is the wave's: the first lane with a record names the tile and writes */
+            const int lead = __ffsll((long long)__ballot(S.reach > 0)) - 1;
+            const int tile0 = __builtin_amdgcn_readlane(rtile, lead);
+            if ((int)(threadIdx.x & 63) == lead) atomicMax(rm + tile0, m_reach);
+        }
+        int mine = (!WROW && S.reach > 0) ? rtile : -1;
+        unsigned long long todo = WROW ? 0ull : __ballot(mine >= 0);
         while (todo) {
             const int lead = __ffsll((long long)todo) - 1;
             const int tile0 = __builtin_amdgcn_readlane(mine, lead);
@@ -595,6 +614,9 @@ __device__ __forceinline__ void pull_window_2p(const double *__restrict__ rec, u
     }
     /* under a locally uniform flow every lane of the wave has the same set of matching candidates: the walk is then done once, on
      * scalars (which candidate, its offset), and only the corner bits and the values stay per lane */
+    /* (the walk below — four matches at a time, value loads back to back, sums in candidate order — is written out four times: here on
+     * scalars, here per lane, in pull_walk_lanes and in pull_window_waverow.  Bit identity between k_step and k_step_waverow rests on
+     * the four staying in step; sharing one function was tried and changes this kernel's instruction stream, which must stay) */
     const unsigned int m0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)m);
     if (!__ballot(m != m0)) {
         unsigned int mu = m0;
@@ -851,6 +873,209 @@ __device__ __forceinline__ int pull_reach_local(const GridP &G, const Arrays &A,
     return m;
 }
 
+/* ------------------------------------------------------------------------------------------
+ * The wave-per-row forms (k_step_waverow, k_step.inc).  The launch is one range of whole 64-column strips, four rows per workgroup,
+ * one wave per row (the strip branch of rows_index), so everything that depends on the row and the column block is the same in all
+ * lanes of a wave and is computed once, on the scalar unit; a lane contributes its lane number, as the 32-bit offset of an address.
+ * Arithmetic, candidate order and summation order are those of the per-lane forms above: the same bits.
+ * ---------------------------------------------------------------------------------------- */
+struct WaveRow {
+    int jl, i0;          /* the wave's local row and its first column (a multiple of 64) */
+    long long t0;        /* index of its first particle: jl * Nx + i0, a multiple of 64 */
+};
+/* (the caller knows that the block is inside the launch) */
+__device__ __forceinline__ WaveRow waverow_of(const GridP &G, int r0, unsigned int lblock)
+{
+    const unsigned int nbx = (unsigned int)G.Nx >> 6;
+    const unsigned int by = lblock / nbx, bx = lblock - by * nbx;
+    WaveRow w;
+    /* (the thread index through an opaque copy: the wave number is formed where it is used, before the RK loop and again behind it,
+     * and not kept in a scalar register across the loop, which has none to spare) */
+    unsigned int tid = threadIdx.x;
+    __asm__ volatile("" : "+v"(tid));
+    w.jl = r0 + 4 * (int)by + __builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    w.i0 = (int)(64u * bx);
+    w.t0 = (long long)w.jl * G.Nx + w.i0;
+    return w;
+}
+__device__ __forceinline__ bool rows_index_waverow(const GridP &G, int r0, int n0, unsigned int lblock, WaveRow &w)
+{
+    const unsigned int nbx = (unsigned int)G.Nx >> 6;
+    if (lblock / nbx >= ((unsigned int)n0 >> 2)) return false;
+    w = waverow_of(G, r0, lblock);
+    return true;
+}
+/* the per-node arrays from the wave's first particle on: a lane indexes them with its lane number.  The result is for INDEXING only:
+ * planes that do not exist (u1, v1 under static winds, uP, vP, vm, asw) come out as non-null garbage and are never dereferenced, so no
+ * code may ask a member of the result whether it is there — ask the original.  The one exception is um, which load_wind tests and
+ * which therefore stays null when it is null.  (Guarding them all was built first: the null tests pull every pointer into scalar
+ * registers at the head of the kernel, 52 of them spilled at once and reloaded inside the RK loop.) */
+__device__ __forceinline__ Arrays arrays_at(const Arrays &A, long long t0)
+{
+    Arrays B = A;
+    B.qold += t0; B.asw += t0; B.pflags += t0; B.status += t0;
+    B.u0 += t0; B.v0 += t0; B.u1 += t0; B.v1 += t0; B.uP += t0; B.vP += t0;      /* (absent planes are never dereferenced) */
+    B.um = A.um ? A.um + t0 : nullptr; B.vm += t0;                                 /* (load_wind asks whether um is there) */
+    return B;
+}
+__device__ __forceinline__ void rmap_clear_ahead_waverow(const Arrays &A, const WaveRow &w, unsigned int lane)
+{
+    if (lane == 0u) A.rmap[(size_t)((A.mr_idx >> 8) & 15) * (size_t)A.ntile + (size_t)(w.t0 >> 6)] = 0;
+}
+
+/* pull_reach_local for a wave whose windows all lie inside the grid: a window row of the wave touches the wave's own tile of that row
+ * and its two neighbours (lane 0 reaches into the left one, lane 63 into the right one), so the wave's maximum is the maximum over
+ * those three per row — read through a uniform pointer, no ballot ladder.  The map read here (buffer mr_idx & 15) was written by the
+ * previous step's launches and is written by nobody during this one.  Any other wave takes the per-lane form. */
+__device__ __forceinline__ int pull_reach_local_waverow(const GridP &G, const Arrays &A, const WaveRow &w, unsigned int lane, int Rg)
+{
+    if (Rg < 2) return Rg;
+    const int jl = w.jl, j = jl + G.j_begin;
+    const bool edge_row = G.Rp > 0 && (jl < G.R || jl >= G.ny_loc - G.R);
+    if (Rg <= 31 && !edge_row && w.i0 - Rg >= 0 && w.i0 + 63 + Rg < G.Nx && jl - Rg >= 0 && jl + Rg < G.ny_loc && j - Rg >= 0 && j + Rg < G.Ny) {
+        const int *const rm = A.rmap + (size_t)(A.mr_idx & 15) * (size_t)A.ntile;
+        const long long nbx = G.Nx >> 6;
+        long long tile = ((long long)(jl - Rg) * G.Nx + w.i0) >> 6;
+        int m = 0;
+        for (int dj = -Rg; dj <= Rg; dj++, tile += nbx) m = max(m, max(rm[tile - 1], max(rm[tile], rm[tile + 1])));
+        return __builtin_amdgcn_readfirstlane(min(m, Rg));
+    }
+    return pull_reach_local(G, A, w.i0 + (int)lane, jl, Rg);
+}
+
+/* the per-lane walk of pull_window_2p over the matches of a lane (bit masks m, ax, ay over the window's candidates), for the waves of
+ * pull_window_waverow whose lanes do not all match the same candidates: the same loop, the same order.  A COPY of the last loop of
+ * pull_window_2p (see the note there): change one, change all four */
+template <int R>
+__device__ __forceinline__ void pull_walk_lanes(const double *__restrict__ rec, unsigned int base, unsigned int pl, unsigned int rowlen,
+                                                unsigned int m, unsigned int ax, unsigned int ay, double &s0, double &s1, double &s2)
+{
+    constexpr int W = 2 * R + 1;
+    while (__ballot(m != 0u)) {
+        double e[4], mx[4], my[4], wx[4], wy[4];
+        bool on[4], hx[4], hy[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            on[k] = (m != 0u);
+            const int c = on[k] ? __builtin_ctz(m) : 0;
+            m &= m - 1u;
+            hx[k] = (ax >> c) & 1u; hy[k] = (ay >> c) & 1u;
+            const unsigned int off = base + (unsigned int)((c / W - R) * (int)rowlen + (c % W - R));
+            e[k] = mx[k] = my[k] = wx[k] = wy[k] = 0.0;
+            if (on[k]) {
+                wx[k] = rec[off + 3u * pl]; wy[k] = rec[off + 4u * pl];
+                e[k] = rec[off]; mx[k] = rec[off + pl]; my[k] = rec[off + 2u * pl];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (on[k]) {
+                const double w = (hx[k] ? wx[k] : 1.0 - wx[k]) * (hy[k] ? wy[k] : 1.0 - wy[k]);
+                s0 += w * e[k];
+                s1 += w * mx[k];
+                s2 += w * my[k];
+            }
+        }
+    }
+}
+
+/* pull_window_2p for a wave of interior nodes.  rec0: plane 0 of the wave's first node (scalar); every candidate's address is a scalar
+ * base — window row, plane and column offset folded on the scalar unit — plus the lane's offset.  Phase 1: a candidate's match is a
+ * compare into a wave mask; "every lane matches the same candidates" is each mask being empty or full, tested on scalars, and the
+ * set of matches is a scalar bit mask from the start.  What stays per lane is the corner a match lands on: bits 2 and 14 of the code
+ * difference, kept packed.  Phase 2 walks the matches four at a time exactly as pull_window_2p does. */
+template <int R>
+__device__ __forceinline__ void pull_window_waverow(const double *__restrict__ rec, const double *__restrict__ rec0, unsigned int lane,
+                                                    unsigned int base, unsigned int pl, unsigned int rowlen, int grp,
+                                                    double &s0, double &s1, double &s2)
+{
+    constexpr int W = 2 * R + 1, NC = W * W;
+    static_assert(NC <= 25, "corner bits of all candidates in two words");
+    const double *const codes = rec0 + 5u * (size_t)pl;
+    /* one byte offset per plane and lane, formed once: a value load is a match's scalar base plus one of these */
+    unsigned int vo[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) vo[k] = 8u * ((unsigned int)k * pl + lane);
+    int d[NC];
+    /* (counts, not booleans: a candidate that all 64 lanes match has count 64, one that some match leaves bits below bit 6 in `some`;
+     * plain integer arithmetic on the scalar unit, where a boolean would be kept as a 64-bit lane mask each) */
+    unsigned int m0 = 0u, some = 0u, px = 0u, py = 0u;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const int di = c % W - R, dj = c / W - R;
+        d[c] = (int)(codes + ((long long)dj * (long long)rowlen + di))[lane] - (grp + 4 * (REC_BIAS - 1 - di) + 4 * 4096 * (REC_BIAS - 1 - dj));
+        const unsigned int n = (unsigned int)__builtin_popcountll(__ballot((d[c] & ~(4 | 16384)) == 0));
+        m0 |= (n >> 6) << c;
+        some |= n & 63u;
+        px |= ((unsigned int)d[c] & 4u) << c;                   /* bit c + 2 SET: the lower x node */
+        py |= (((unsigned int)d[c] >> 14) & 1u) << c;           /* bit c SET: the lower y node */
+    }
+    if constexpr (R >= 2) {
+        /* (the 25 differences of the reach-2 window kept alive for this case cost the kernel registers it does not have: more spill
+         * code around the RK loop, two instructions more inside it; such a wave reads its codes again, from the cache) */
+        if (some != 0u) { pull_window_2p<R>(rec, base, pl, rowlen, grp, s0, s1, s2); return; }
+    } else if (some != 0u) {
+        unsigned int m = 0u, ax = 0u, ay = 0u;
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            m |= ((d[c] & ~(4 | 16384)) == 0 ? 1u : 0u) << c;
+            ax |= ((d[c] & 4) ? 0u : 1u) << c;
+            ay |= ((d[c] & 16384) ? 0u : 1u) << c;
+        }
+        pull_walk_lanes<R>(rec, base, pl, rowlen, m, ax, ay, s0, s1, s2);
+        return;
+    }
+    /* (the scalar walk of pull_window_2p with scalar bases: one of the four copies named there) */
+    unsigned int mu = m0;
+    while (mu != 0u) {
+        double e[4], mx[4], my[4], wx[4], wy[4];
+        bool on[4], hx[4], hy[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            on[k] = (mu != 0u);
+            const int c = on[k] ? __builtin_ctz(mu) : 0;
+            mu &= mu - 1u;
+            hx[k] = !((px >> (c + 2)) & 1u); hy[k] = !((py >> c) & 1u);
+            const double *const p = rec0 + ((long long)(c / W - R) * (long long)rowlen + (c % W - R));
+            e[k] = mx[k] = my[k] = wx[k] = wy[k] = 0.0;
+            if (on[k]) {
+                const char *const pb = (const char *)p;
+                wx[k] = *(const double *)(pb + vo[3]); wy[k] = *(const double *)(pb + vo[4]);
+                e[k] = *(const double *)(pb + vo[0]); mx[k] = *(const double *)(pb + vo[1]); my[k] = *(const double *)(pb + vo[2]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (on[k]) {
+                const double w = (hx[k] ? wx[k] : 1.0 - wx[k]) * (hy[k] ? wy[k] : 1.0 - wy[k]);
+                s0 += w * e[k];
+                s1 += w * mx[k];
+                s2 += w * my[k];
+            }
+        }
+    }
+}
+
+/* pull_any for the wave: reach 1 and 2 with every window of the wave inside the grid — the interior column blocks of the interior
+ * rows — take the scalar-addressed window; the first and last column block of a row, rows whose window wraps or leaves the grid
+ * (with them the tripolar band and aliased small grids: both imply such a row or block) and wider reaches take pull_any as it is */
+__device__ __forceinline__ void pull_waverow(const GridP &G, const Arrays &A, const WaveRow &w, unsigned int lane, int R,
+                                             double &s0, double &s1, double &s2)
+{
+    const int j = w.jl + G.j_begin;
+    if ((R == 1 || R == 2) && w.i0 - R >= 0 && w.i0 + 63 + R < G.Nx && j - R >= 0 && j + R < G.Ny) {
+        const unsigned int pl = (unsigned int)G.Nx, rowlen = 6u * pl;
+        const double *const rec0 = A.rec + ((size_t)(w.jl + G.R) * (size_t)rowlen + (size_t)w.i0);
+        const unsigned int base = (unsigned int)(w.jl + G.R) * rowlen + ((unsigned int)w.i0 + lane);
+        for (int grp = 1; grp <= G.ngroups; grp++) {
+            if (R == 1) pull_window_waverow<1>(A.rec, rec0, lane, base, pl, rowlen, grp, s0, s1, s2);
+            else pull_window_waverow<2>(A.rec, rec0, lane, base, pl, rowlen, grp, s0, s1, s2);
+        }
+        return;
+    }
+    pull_any(G, A, w.i0 + (int)lane, w.jl, R, s0, s1, s2);
+}
+
 /* launchers of the kernel families that live in their own translation units (k_step_*.hip, k_advance.hip) */
 struct StepLaunch {
     dim3 grid, block;
@@ -860,7 +1085,12 @@ struct StepLaunch {
     const Arrays *A;
     double t_prev, DT_prev, t_start, DT;
     int r0, n0, r1, n1;
+    bool waverow;            /* fused step: launch k_step_waverow (the caller has checked waverow_geometry and waverow_flavour) */
 };
+/* k_step_waverow covers the launches for which rows_index takes its strip branch: one row range of whole 64-column strips, four rows
+ * at a time; it exists for the specialised physics without the per-node metric */
+static inline bool waverow_geometry(int Nx, int n0, int n1) { return n1 == 0 && (Nx & 63) == 0 && (n0 & 3) == 0; }
+static inline bool waverow_flavour(bool fast, bool metric) { return fast && !metric; }
 /* fused step: fast = specialised physics; solver 0 DP5, 1 Tsit5, 2 auto-switching; wind_static; metric */
 void launch_k_step_explicit(const StepLaunch &L, bool fast, int solver, bool wind_static, bool metric);
 void launch_k_step_auto(const StepLaunch &L, bool wind_static, bool metric);

@@ -471,6 +471,11 @@ struct picles_ctx {
     int cur = 0;
     /* fused stepping: the last advance's records still await their scatter + remesh */
     bool fuse_steps = true;
+    /* k_step_waverow (k_step.inc) for the fused launches whose geometry qualifies; PICLES_WAVEROW, read once at create:
+     * 0 never; 1 (default) where it qualifies AND the flavour is the one whose speed has been measured against k_step on the hardware
+     * (DP5 under static winds, the BASELINE launch: waverow_measured); 2 ("require") every flavour, and a fused step with a launch
+     * that does not qualify is refused */
+    int waverow_mode = 1;
     bool pending = false;
     double pend_t = 0.0, pend_dt = 0.0;
     signed char *d_mask = nullptr;
@@ -695,6 +700,7 @@ PX_EXPORT int32_t picles_create(const picles_grid *g, const picles_phys *p, cons
     if ((e = hipSetDevice(device_id)) != hipSuccess) { g_create_error = hipGetErrorString(e); return -4; }
 
     picles_ctx *c = new picles_ctx();
+    if (const char *wr = getenv("PICLES_WAVEROW")) c->waverow_mode = !strcmp(wr, "0") ? 0 : (!strcmp(wr, "require") ? 2 : 1);
     memset(&c->A, 0, sizeof(c->A));
     c->stream = nullptr;
     c->ev_edge = nullptr;
@@ -1334,9 +1340,15 @@ PX_EXPORT int32_t picles_begin_step(picles_ctx *c, double dt, int32_t flags)
     return 0;
 }
 
-static int select_rows(picles_ctx *c, int which, int &r0, int &n0, int &r1, int &n1)
+/* the specialised variant of the step kernels: every physics switch on, n = 2, p = 3/4, no dead band (all reference scripts) */
+static bool physics_fast(const KParams &P)
 {
-    const GridP &G = c->G;
+    return P.propagation && P.input && P.dissipation && P.peak_shift && P.direction && P.n_is_2 && P.p_is_075 && P.deadband2 == 0.0;
+}
+
+/* the row ranges of a selector; false: no such selector */
+static bool rows_of(const GridP &G, int which, int &r0, int &n0, int &r1, int &n1)
+{
     int R = G.R;
     r0 = n0 = r1 = n1 = 0;
     bool small = G.ny_loc <= 2 * R;
@@ -1346,8 +1358,12 @@ static int select_rows(picles_ctx *c, int which, int &r0, int &n0, int &r1, int 
         else { n0 = R; r1 = G.ny_loc - R; n1 = R; }
     } else if (which == PICLES_ROWS_INTERIOR) {
         if (!small) { r0 = R; n0 = G.ny_loc - 2 * R; }
-    } else return fail(c, -2, "bad row selector");
-    return 0;
+    } else return false;
+    return true;
+}
+static int select_rows(picles_ctx *c, int which, int &r0, int &n0, int &r1, int &n1)
+{
+    return rows_of(c->G, which, r0, n0, r1, n1) ? 0 : fail(c, -2, "bad row selector");
 }
 
 /* Launches of one step may come on caller-provided streams.  Whatever the library enqueued on its own stream before (the
@@ -1379,7 +1395,7 @@ PX_EXPORT int32_t picles_advance_rows(picles_ctx *c, int32_t which, void *stream
     timing_begin(c, s, 0);
     {
         const KParams &P = c->P;
-        bool fast = P.propagation && P.input && P.dissipation && P.peak_shift && P.direction && P.n_is_2 && P.p_is_075 && P.deadband2 == 0.0;
+        bool fast = physics_fast(P);
         if (!P.wind_static && P.wind_nk > 1) fast = false;     /* a polyline window: the general flavours carry it (same bits: the oracle's one arithmetic) */
         Arrays A = arrays_for(c, c->cur, c->cur);
         StepLaunch L = {dim3(nblocks(nt, 256)), dim3(256), s, &c->P, &c->G, &A, 0.0, 0.0, c->clock, c->step_dt, r0, n0, r1, n1};
@@ -1403,13 +1419,27 @@ static bool step_fusable(const picles_ctx *c, int flags, double dt)
      * phases: only the general flavours of the stand-alone advance evaluate one */
     if (c->wind_grid_on ? (c->wind_grid_mode != PICLES_LATTICE_SMOOTH3 && picles_lattice_knot_times(c->wg_t0, c->wg_dt, c->clock, dt, nullptr, 0) >= 2)
                         : (!P.wind_static && P.wind_nk > 1)) return false;
-    const bool fast = P.propagation && P.input && P.dissipation && P.peak_shift && P.direction && P.n_is_2 && P.p_is_075 && P.deadband2 == 0.0;
+    const bool fast = physics_fast(P);
     /* the time-varying-wind and per-node-metric flavours of the fused kernel exist for the specialised physics */
     if (c->wind_grid_on) return fast;
     if (c->A.pc) return fast && P.wind_static != 0;
     if (P.solver == 2) return fast && P.wind_static != 0;   /* the auto-switching flavour exists for the specialised physics */
     return P.wind_static != 0;
 }
+
+/* does the fused launch of these rows take k_step_waverow? */
+static bool step_rows_waverow(const picles_ctx *c, int which)
+{
+    int r0, n0, r1, n1;
+    if (!rows_of(c->G, which, r0, n0, r1, n1)) return false;
+    if (n0 + n1 == 0) return true;             /* (nothing is launched) */
+    return waverow_flavour(physics_fast(c->P), c->A.pc != nullptr) && waverow_geometry(c->G.Nx, n0, n1);
+}
+
+/* the flavours the default mode hands to k_step_waverow: those timed against k_step, same session, and found faster.
+ * The Tsit5, time-varying-wind and default-solver flavours give the same bits (tests/test_gpu_waverow.py) but have not been timed:
+ * they stay on k_step unless PICLES_WAVEROW=require asks for them */
+static bool waverow_measured(const KParams &P) { return P.solver == 0 && P.wind_static != 0; }
 
 /* fused phase launcher: scatter+remesh of the pending step and advance of the current one for the
  * selected rows (records of the pending step: rec_buf[1-cur], of this step: rec_buf[cur]) */
@@ -1424,7 +1454,7 @@ static int launch_step_rows(picles_ctx *c, int which, hipStream_t s)
     const KParams &P = c->P;
     Arrays A = arrays_for(c, c->cur ^ 1, c->cur);
     /* specialised variant: every physics switch on and n = 2 (all reference scripts) */
-    bool fast = P.propagation && P.input && P.dissipation && P.peak_shift && P.direction && P.n_is_2 && P.p_is_075 && P.deadband2 == 0.0;
+    bool fast = physics_fast(P);
     /* cost-ordered dispatch (kernels.h): the launch that covers (nearly) everything — the whole grid of a plain context, the interior
      * rows of a slab — files an order over ITS workgroups and follows the one its predecessor of the same shape filed.  The edge
      * launch of a slab (a handful of workgroups, on the other stream) neither reads nor files one and leaves the chain alone; a
@@ -1443,7 +1473,8 @@ static int launch_step_rows(picles_ctx *c, int which, hipStream_t s)
     }
     timing_begin(c, s, 0);
     {
-        StepLaunch L = {dim3(nblocks(nt, 256)), dim3(256), s, &c->P, &c->G, &A, c->pend_t, c->pend_dt, c->clock, c->step_dt, r0, n0, r1, n1};
+        StepLaunch L = {dim3(nblocks(nt, 256)), dim3(256), s, &c->P, &c->G, &A, c->pend_t, c->pend_dt, c->clock, c->step_dt, r0, n0, r1, n1,
+                        (c->waverow_mode == 2 || (c->waverow_mode == 1 && waverow_measured(P))) && step_rows_waverow(c, which)};
         if (fast && P.solver == 2) launch_k_step_auto(L, P.wind_static != 0, c->A.pc != nullptr);          /* k_step_auto.hip */
         else launch_k_step_explicit(L, fast, P.solver, P.wind_static != 0, c->A.pc != nullptr);             /* k_step_explicit.hip */
     }
@@ -1461,6 +1492,12 @@ PX_EXPORT int32_t picles_begin_fused_step(picles_ctx *c, double dt)
     if (!c) return -1;
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     if (!step_fusable(c, PICLES_STEP_ZERO_FIRST, dt)) return 1;
+    /* PICLES_WAVEROW=require: every launch of the step — the whole grid, or a slab's edge and interior rows — must take k_step_waverow;
+     * refused here, before the step has changed anything */
+    if (c->waverow_mode == 2 && !(c->G.single_slab ? step_rows_waverow(c, PICLES_ROWS_ALL)
+                                                   : step_rows_waverow(c, PICLES_ROWS_EDGE) && step_rows_waverow(c, PICLES_ROWS_INTERIOR)))
+        return fail(c, -5, "PICLES_WAVEROW=require: a fused launch of this step does not qualify for k_step_waverow (one row range, "
+                           "Nx a multiple of 64, rows a multiple of 4, specialised physics without the per-node metric)");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->wind_grid_on) {
         /* device-sampled winds.  With a step pending, its remesh (done by this step's launches) needs the wind

@@ -5,6 +5,7 @@ separately so that they can be left out).
 
     python scripts/isa_budget.py k_step_explicit.hip _Z6k_stepILb1ELb0ELb1ELb0ELb0E        # the BASELINE kernel
     python scripts/isa_budget.py k_step_auto.hip     _Z6k_stepILb1ELb1ELb1ELb0ELb1E        # the default solver, static winds
+    python scripts/isa_budget.py k_step_explicit.hip _Z14k_step_waverowILb1ELb0ELb1ELb0ELb0E  # the wave-per-row form of the BASELINE kernel
 """
 import re
 import subprocess
@@ -61,9 +62,14 @@ def kernels(unit):
     return [m.group(1) for m in re.finditer(r"^(_Z\d+k_(?:step|advance)I\w*):\s*;", assembly(unit), re.M)]
 
 
+def waverow_kernels(unit):
+    """the k_step_waverow flavours of a unit (kernels() keeps listing the k_step / k_advance ones alone)"""
+    return [m.group(1) for m in re.finditer(r"^(_Z\d+k_step_waverowI\w*):\s*;", assembly(unit), re.M)]
+
+
 def budget(unit, prefix, verbose=False):
     asm = assembly(unit)
-    heads = list(re.finditer(r"^(_Z\d+k_(?:step|advance)I\w*):\s*;", asm, re.M))
+    heads = list(re.finditer(r"^(_Z\d+k_(?:step|step_waverow|advance)I\w*):\s*;", asm, re.M))
     sel = [(m, nxt) for m, nxt in zip(heads, heads[1:] + [None]) if m.group(1).startswith(prefix)]
     assert len(sel) == 1, [m.group(1) for m, _ in sel]
     m, nxt = sel[0]
