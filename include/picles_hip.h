@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 8
+#define PICLES_ABI_VERSION 9
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -444,6 +444,12 @@ int32_t picles_get_timing_samples(picles_ctx *ctx, int32_t kind, double *out_ms,
  * workgroups of that launch when a complete order was filed (out[0] + out[1] == n), 0 when none was (the run is not mixed; a slab reports
  * the order of the launch over its interior rows), < 0 on error.  Syncs and completes a pending fused step, like every getter.  No counterpart in the reference. */
 int32_t picles_get_dispatch_order(picles_ctx *ctx, int32_t *out, int32_t cap);
+/* Diagnostic: the pull scatter of the wave-per-row fused step skips the candidate codes of a wave whose whole neighbourhood carries one
+ * record code (the tile class map; PICLES_PULL_CLASS=0 turns it off).  out[0] = waves that took that path since
+ * picles_seed / picles_reset_counters, out[1] = those among them whose neighbourhood held no record at all.  Speed only: results never
+ * depend on the path.  Syncs the device; does NOT complete a pending fused step (it can be asked after every step of a fused run).
+ * No counterpart in the reference. */
+int32_t picles_get_pull_class_counts(picles_ctx *ctx, int64_t *out);
 int32_t picles_sync(picles_ctx *ctx);
 
 /* ---- split phases for the slab-partitioned (multi-GPU) step -------------------

@@ -101,7 +101,7 @@ LATTICE_LINEAR, LATTICE_SMOOTH3 = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 8
+ABI_VERSION = 9
 SLAB_ID_BYTES = 128
 PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
 
@@ -186,6 +186,7 @@ SYMBOLS = {
     "picles_get_timing": (C.c_int32, [_VP, C.POINTER(PiclesTiming)]),
     "picles_get_timing_samples": (C.c_int32, [_VP, C.c_int32, c_double_p, C.c_int32]),
     "picles_get_dispatch_order": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int32]),
+    "picles_get_pull_class_counts": (C.c_int32, [_VP, C.POINTER(C.c_int64)]),
     "picles_sync": (C.c_int32, [_VP]),
     "picles_begin_step": (C.c_int32, [_VP, C.c_double, C.c_int32]),
     "picles_advance_rows": (C.c_int32, [_VP, C.c_int32, _VP]),

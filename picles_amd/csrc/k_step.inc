@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(256, (FAST && !AUTO) ? 4 : (FAST ? 3 : 2)) K_S
     if constexpr (WROW) { active = rows_index_waverow(G, r0, n0, lblock, wr); t = wr.t0 + lane; }
     else active = rows_index(G, r0, n0, r1, n1, t, lblock);
     StepStats S = {{0u, 0u, 0u, 0}, 0u, 0u, 0u, 0u, 0u, 0u, 0};
-    int rtile = -1;
+    int rtile = -1, ccode = -1;
     if (active) {
         int i, jl;
         if constexpr (WROW) { i = wr.i0 + (int)lane; jl = wr.jl; }
@@ -103,7 +103,11 @@ __global__ void __launch_bounds__(256, (FAST && !AUTO) ? 4 : (FAST ? 3 : 2)) K_S
              * calm region — asks for it behind the pull otherwise, one more round trip in a wave that consists of round trips */
             if (!STATIC) { uP_pre = Av.uP[tx]; vP_pre = Av.vP[tx]; }
         }
-        if constexpr (WROW) pull_waverow(G, A, wr, lane, pull_reach_local_waverow(G, A, wr, lane, pull_reach(G, A, jl, mr_early)), s0, s1, s2);
+        if constexpr (WROW) {
+            int cls;
+            const int Rl = pull_reach_local_waverow(G, A, wr, lane, pull_reach(G, A, jl, mr_early), cls);
+            pull_waverow(G, A, wr, lane, Rl, cls, s0, s1, s2);
+        }
         else pull_any(G, A, i, jl, pull_reach_local(G, A, i, jl, pull_reach(G, A, jl, mr_early)), s0, s1, s2);
 #ifdef PICLES_PHASE_CLOCK
         __asm__ volatile("" : "+v"(s0), "+v"(s1), "+v"(s2));
@@ -175,7 +179,7 @@ __global__ void __launch_bounds__(256, (FAST && !AUTO) ? 4 : (FAST ? 3 : 2)) K_S
             S.reseeds += (unsigned int)(pr_ >> 8);
             Abv.qold[tbx] = qold;
             Abv.status[tbx] = status;
-            if constexpr (WROW) write_record_at(Gb, rec_row_out(Ab, Gb, wrb.jl + Gb.R) + wrb.i0, threadIdx.x & 63u, pfb, on, z, S);
+            if constexpr (WROW) write_record_at(Gb, rec_row_out(Ab, Gb, wrb.jl + Gb.R) + wrb.i0, threadIdx.x & 63u, pfb, on, z, S, &ccode);
             else write_record(Gb, Ab, ib, jlb, pfb, on, z, S);
             rtile = WROW ? (int)(wrb.t0 >> 6) : (int)(tb >> 6);
         }
@@ -183,7 +187,7 @@ __global__ void __launch_bounds__(256, (FAST && !AUTO) ? 4 : (FAST ? 3 : 2)) K_S
     {
         KStepArgsPtr K = kargs_reload();
         const Arrays Ab = K->A;
-        flush_stats<WROW>(Ab, S, rtile);
+        flush_stats<WROW>(Ab, S, rtile, ccode);
         if (Ab.ord && order_wanted(Ab)) order_file(Ab, lblock, __ballot(S.adv != 0 || S.reseeds != 0) != 0);
 #ifdef PICLES_WAVE_LOG
         if ((threadIdx.x & 63) == 0) {

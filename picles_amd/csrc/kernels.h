@@ -36,8 +36,10 @@ struct GridP {
 #define NSLOTS 1024
 struct DevCounters {
     unsigned long long rhs, acc, rej, reseeds, clamps, maxit, adv, overflow;
-    unsigned long long nonfinite, wslots, pad_[6];     /* two 64-B lines per slot; wslots: 64 x the wave's largest attempt count */
+    unsigned long long nonfinite, wslots, pad_[4];     /* two 64-B lines per slot; wslots: 64 x the wave's largest attempt count */
+    unsigned long long cls, cls_empty;                 /* waves whose pull took the class path (Arrays::rmap, the class map) / found it EMPTY */
 };
+static_assert(sizeof(DevCounters) == 128, "two 64-B lines per slot");
 
 struct Arrays {
     double *state, *movie;   /* 3 planes */
@@ -65,6 +67,11 @@ struct Arrays {
      * 1 in the calm half).  Five buffers of ntile ints rotating with the reach counters above (same three indices). */
     int ntile;
     int *rmap;
+    /* the tile class map lies behind the reach map in the same allocation (class_map below): five more buffers of ntile ints, rotating
+     * on the same three indices.  An entry is 0 (nothing known: the cleared value), a record code c > 0 (all 64 records of the tile, in the
+     * record buffer of that generation, carry the code c) or CMAP_EMPTY (all 64 carry code 0).  Only k_step_waverow writes non-zero
+     * entries, in the launch that writes the tile's records; whoever writes records by other means zeroes the map.  Bit
+     * MR_CLASS_ON of mr_idx: the pull may follow the map and the fused step files into it (PICLES_PULL_CLASS, read at create). */
     /* cost-ordered dispatch of the fused step (whole-grid launches).  Every workgroup files its 256-node block at the end of a
      * step: blocks that integrated or re-seeded somebody from the front of a permutation, blocks with nothing to do from the back.
      * The next launch hands the blocks out in that order — busy ones first, calm ones last — when at least an eighth of them was
@@ -79,6 +86,10 @@ struct Arrays {
 __device__ __forceinline__ int *order_buf(const Arrays &A, int which) { return A.ord + (size_t)which * (size_t)(2 + A.nblk); }
 
 __device__ __forceinline__ int *reach_counters(const Arrays &A) { return (int *)(A.cnt + NSLOTS); }
+
+#define CMAP_EMPTY (-1)
+#define MR_CLASS_ON 4096
+__device__ __forceinline__ int *class_map(const Arrays &A, int which) { return A.rmap + (size_t)(5 + which) * (size_t)A.ntile; }
 
 #define PF_STEPPED 1
 #define PF_GROUP2 2
@@ -272,7 +283,8 @@ __device__ __forceinline__ KStepArgsPtr kargs_reload(void)      /* k_advance cas
 /* rr: the particle's row of the OUT buffer, i: its column — or (k_step_waverow) rr: that row from the wave's first column on, a scalar,
  * and i: the lane number, unsigned: each plane's base is then formed on the scalar unit and the lane's offset rides in the store */
 template <class IDX>
-__device__ __forceinline__ void write_record_at(const GridP &G, double *rr, IDX i, unsigned char pf, int on, const Vec5 &z, StepStats &S)
+__device__ __forceinline__ void write_record_at(const GridP &G, double *rr, IDX i, unsigned char pf, int on, const Vec5 &z, StepStats &S,
+                                                int *code_out = nullptr)      /* code_out: the code the record carries, as an int */
 {
     auto at = [&](int plane) -> double & {
         if constexpr (std::is_unsigned<IDX>::value) return (rr + (size_t)plane * (size_t)G.Nx)[i];
@@ -300,6 +312,7 @@ __device__ __forceinline__ void write_record_at(const GridP &G, double *rr, IDX 
         else { S.overflow = 1; S.reach = 0; }     /* not scattered, not part of the reach the pull follows */
     }
     at(5) = code;
+    if (code_out) *code_out = (int)code;
 }
 __device__ __forceinline__ void write_record(const GridP &G, const Arrays &A, int i, int jl, unsigned char pf, int on,
                                              const Vec5 &z, StepStats &S)
@@ -312,9 +325,21 @@ __device__ __forceinline__ void write_record(const GridP &G, const Arrays &A, in
  * (accepted and rejected steps share one word), the reach with a ballot ladder. */
 /* rtile: the reach-map tile (t >> 6) of a lane whose particle left a record this step, -1 otherwise */
 /* WROW (k_step_waverow): the wave covers exactly one tile, the same in every lane that has one */
+/* ccode (WROW): the code of the record the lane wrote this step, -1 where it wrote none.  When all 64 lanes wrote the same code the
+ * tile gets its class: lane 0 files the code (CMAP_EMPTY for code 0) into the class map buffer of this step; otherwise the entry keeps
+ * the 0 it was cleared to */
 template <bool WROW = false>
-__device__ __forceinline__ void flush_stats(const Arrays &A, const StepStats &S, int rtile = -1)
+__device__ __forceinline__ void flush_stats(const Arrays &A, const StepStats &S, int rtile = -1, int ccode = -1)
 {
+    if constexpr (WROW) {
+        if (A.mr_idx & MR_CLASS_ON) {
+            const int c0 = __builtin_amdgcn_readfirstlane(ccode);
+            if (c0 >= 0 && !__ballot(ccode != c0)) {
+                const int tile0 = __builtin_amdgcn_readfirstlane(rtile);
+                if ((threadIdx.x & 63) == 0) class_map(A, (A.mr_idx >> 4) & 15)[tile0] = c0 ? c0 : CMAP_EMPTY;
+            }
+        }
+    }
     unsigned long long s_rhs = wave_sum_u64(S.st.rhs);
     unsigned long long s_ar = wave_sum_u64(((unsigned long long)S.st.acc << 32) | S.st.rej);
     unsigned long long b_adv = __ballot(S.adv != 0), b_res1 = __ballot(S.reseeds == 1), b_res2 = __ballot(S.reseeds >= 2);
@@ -614,8 +639,9 @@ __device__ __forceinline__ void pull_window_2p(const double *__restrict__ rec, u
     }
     /* under a locally uniform flow every lane of the wave has the same set of matching candidates: the walk is then done once, on
      * scalars (which candidate, its offset), and only the corner bits and the values stay per lane */
-    /* (the walk below — four matches at a time, value loads back to back, sums in candidate order — is written out four times: here on
-     * scalars, here per lane, in pull_walk_lanes and in pull_window_waverow.  Bit identity between k_step and k_step_waverow rests on
+    /* (the walk below — four matches at a time, value loads back to back, sums in candidate order — is written out five times: here on
+     * scalars, here per lane, in pull_walk_lanes, in pull_window_waverow and, for the four candidates a tile class names, with the
+     * corner selects constant, in pull_class_waverow.  Bit identity between k_step and k_step_waverow rests on
      * the four staying in step; sharing one function was tried and changes this kernel's instruction stream, which must stay) */
     const unsigned int m0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)m);
     if (!__ballot(m != m0)) {
@@ -844,6 +870,9 @@ __device__ __forceinline__ void rmap_clear_ahead(const Arrays &A, long long t)
     if ((t & 63) == 0) A.rmap[(size_t)((A.mr_idx >> 8) & 15) * (size_t)A.ntile + (size_t)(t >> 6)] = 0;
 }
 
+/* (the class map behind the reach map is cleared ahead in the same way by k_step_waverow alone, rmap_clear_ahead_waverow; k_step and
+ * k_advance keep their instruction streams: the host clears their rows' entries while any can be set, picles_hip.hip, class_map_clear_rows) */
+
 /* The reach the pull of node (i, jl) must cover: the largest reach of any particle that can land on it.  Rg (pull_reach: the
  * grid-wide maximum of the last advance, or halo_rows for the edge rows of a slab) bounds where such particles sit; among the
  * tiles that intersect that window the map knows how far particles really went.  Any reach >= the true one gives the same
@@ -920,32 +949,54 @@ __device__ __forceinline__ Arrays arrays_at(const Arrays &A, long long t0)
 }
 __device__ __forceinline__ void rmap_clear_ahead_waverow(const Arrays &A, const WaveRow &w, unsigned int lane)
 {
-    if (lane == 0u) A.rmap[(size_t)((A.mr_idx >> 8) & 15) * (size_t)A.ntile + (size_t)(w.t0 >> 6)] = 0;
+    if (lane == 0u) {
+        A.rmap[(size_t)((A.mr_idx >> 8) & 15) * (size_t)A.ntile + (size_t)(w.t0 >> 6)] = 0;
+        class_map(A, (A.mr_idx >> 8) & 15)[(size_t)(w.t0 >> 6)] = 0;
+    }
 }
 
 /* pull_reach_local for a wave whose windows all lie inside the grid: a window row of the wave touches the wave's own tile of that row
  * and its two neighbours (lane 0 reaches into the left one, lane 63 into the right one), so the wave's maximum is the maximum over
  * those three per row — read through a uniform pointer, no ballot ladder.  The map read here (buffer mr_idx & 15) was written by the
  * previous step's launches and is written by nobody during this one.  Any other wave takes the per-lane form. */
-__device__ __forceinline__ int pull_reach_local_waverow(const GridP &G, const Arrays &A, const WaveRow &w, unsigned int lane, int Rg)
+__device__ __forceinline__ int pull_reach_local_waverow(const GridP &G, const Arrays &A, const WaveRow &w, unsigned int lane, int Rg, int &cls)
 {
-    if (Rg < 2) return Rg;
+    /* cls: the class of the wave's neighbourhood — the class map entries of the same (2 Rg + 1) rows x 3 tiles, when they are all equal
+     * and not 0: every record any lane's window can see carries that one code (CMAP_EMPTY: code 0).  Asked for at every reach, 1 included */
+    cls = 0;
+    const bool klass = (A.mr_idx & MR_CLASS_ON) != 0;
+    if (Rg < 2 && !klass) return Rg;
     const int jl = w.jl, j = jl + G.j_begin;
     const bool edge_row = G.Rp > 0 && (jl < G.R || jl >= G.ny_loc - G.R);
-    if (Rg <= 31 && !edge_row && w.i0 - Rg >= 0 && w.i0 + 63 + Rg < G.Nx && jl - Rg >= 0 && jl + Rg < G.ny_loc && j - Rg >= 0 && j + Rg < G.Ny) {
+    if (Rg >= 1 && Rg <= 31 && !edge_row && w.i0 - Rg >= 0 && w.i0 + 63 + Rg < G.Nx && jl - Rg >= 0 && jl + Rg < G.ny_loc && j - Rg >= 0 && j + Rg < G.Ny) {
         const int *const rm = A.rmap + (size_t)(A.mr_idx & 15) * (size_t)A.ntile;
+        const int *const cm = class_map(A, A.mr_idx & 15);
         const long long nbx = G.Nx >> 6;
         long long tile = ((long long)(jl - Rg) * G.Nx + w.i0) >> 6;
-        int m = 0;
-        for (int dj = -Rg; dj <= Rg; dj++, tile += nbx) m = max(m, max(rm[tile - 1], max(rm[tile], rm[tile + 1])));
-        return __builtin_amdgcn_readfirstlane(min(m, Rg));
+        int m = 0, diff = 0;
+        const int c0 = klass ? cm[tile] : 0;
+        for (int dj = -Rg; dj <= Rg; dj++, tile += nbx) {
+            if (Rg >= 2) m = max(m, max(rm[tile - 1], max(rm[tile], rm[tile + 1])));
+            if (klass) diff |= (cm[tile - 1] ^ c0) | (cm[tile] ^ c0) | (cm[tile + 1] ^ c0);
+        }
+        if (diff == 0 && c0 > 0) {
+            /* (a code whose four feeding candidates lie outside the window the tests above vouch for is not followed: no address is
+             * formed from a map entry alone) */
+            int grp, bx, by;
+            rec_decode((double)c0, grp, bx, by);
+            const int rx = (bx < 0) ? -bx : bx + 1, ry = (by < 0) ? -by : by + 1;
+            if (max(rx, ry) > Rg) diff = 1;
+        }
+        cls = __builtin_amdgcn_readfirstlane(diff == 0 ? c0 : 0);
+        return Rg >= 2 ? __builtin_amdgcn_readfirstlane(min(m, Rg)) : Rg;
     }
+    if (Rg < 2) return Rg;
     return pull_reach_local(G, A, w.i0 + (int)lane, jl, Rg);
 }
 
 /* the per-lane walk of pull_window_2p over the matches of a lane (bit masks m, ax, ay over the window's candidates), for the waves of
  * pull_window_waverow whose lanes do not all match the same candidates: the same loop, the same order.  A COPY of the last loop of
- * pull_window_2p (see the note there): change one, change all four */
+ * pull_window_2p (see the note there): change one, change all five */
 template <int R>
 __device__ __forceinline__ void pull_walk_lanes(const double *__restrict__ rec, unsigned int base, unsigned int pl, unsigned int rowlen,
                                                 unsigned int m, unsigned int ax, unsigned int ay, double &s0, double &s1, double &s2)
@@ -1025,7 +1076,7 @@ __device__ __forceinline__ void pull_window_waverow(const double *__restrict__ r
         pull_walk_lanes<R>(rec, base, pl, rowlen, m, ax, ay, s0, s1, s2);
         return;
     }
-    /* (the scalar walk of pull_window_2p with scalar bases: one of the four copies named there) */
+    /* (the scalar walk of pull_window_2p with scalar bases: one of the five copies named there) */
     unsigned int mu = m0;
     while (mu != 0u) {
         double e[4], mx[4], my[4], wx[4], wy[4];
@@ -1056,13 +1107,57 @@ __device__ __forceinline__ void pull_window_waverow(const double *__restrict__ r
     }
 }
 
-/* pull_any for the wave: reach 1 and 2 with every window of the wave inside the grid — the interior column blocks of the interior
+/* the pull of a wave whose neighbourhood carries one record code (pull_reach_local_waverow, cls): every source has the cell offset
+ * (bx, by), so the candidates that feed a node are the four (di, dj) = (-bx - ax, -by - ay), ax, ay in {0, 1}, the same for every lane, at
+ * any reach; no code is loaded and none compared.  They are visited in the candidate order of the windows above (dj ascending, then di),
+ * the lower di / dj being the one whose UPPER node this is, and summed as the scalar walk of pull_window_waverow sums its matches: the
+ * same weights, the same order, the same bits. */
+__device__ __forceinline__ void pull_class_waverow(const double *__restrict__ rec0, unsigned int lane, unsigned int pl, unsigned int rowlen,
+                                                   int bx, int by, double &s0, double &s1, double &s2)
+{
+    unsigned int vo[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) vo[k] = 8u * ((unsigned int)k * pl + lane);
+    double e[4], mx[4], my[4], wx[4], wy[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int di = -bx - 1 + (k & 1), dj = -by - 1 + (k >> 1);
+        const char *const pb = (const char *)(rec0 + ((long long)dj * (long long)rowlen + di));
+        wx[k] = *(const double *)(pb + vo[3]); wy[k] = *(const double *)(pb + vo[4]);
+        e[k] = *(const double *)(pb + vo[0]); mx[k] = *(const double *)(pb + vo[1]); my[k] = *(const double *)(pb + vo[2]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const bool hx = !(k & 1), hy = !(k >> 1);
+        const double w = (hx ? wx[k] : 1.0 - wx[k]) * (hy ? wy[k] : 1.0 - wy[k]);
+        s0 += w * e[k];
+        s1 += w * mx[k];
+        s2 += w * my[k];
+    }
+}
+
+/* pull_any for the wave: a wave with a class (cls != 0) goes straight to its four value fetches, or to nothing; reach 1 and 2 with every window of the wave inside the grid — the interior column blocks of the interior
  * rows — take the scalar-addressed window; the first and last column block of a row, rows whose window wraps or leaves the grid
  * (with them the tripolar band and aliased small grids: both imply such a row or block) and wider reaches take pull_any as it is */
-__device__ __forceinline__ void pull_waverow(const GridP &G, const Arrays &A, const WaveRow &w, unsigned int lane, int R,
+__device__ __forceinline__ void pull_waverow(const GridP &G, const Arrays &A, const WaveRow &w, unsigned int lane, int R, int cls,
                                              double &s0, double &s1, double &s2)
 {
     const int j = w.jl + G.j_begin;
+    if (cls != 0) {
+        if (lane == 0u) {
+            DevCounters *const c = A.cnt + ((blockIdx.x * 4u + (threadIdx.x >> 6)) & (NSLOTS - 1));
+            atomicAdd(&c->cls, 1ull);
+            if (cls == CMAP_EMPTY) atomicAdd(&c->cls_empty, 1ull);
+        }
+        if (cls == CMAP_EMPTY) return;          /* nobody around left a record: the node value stays 0 */
+        int cgrp, bx, by;
+        rec_decode((double)cls, cgrp, bx, by);
+        const unsigned int pl = (unsigned int)G.Nx, rowlen = 6u * pl;
+        const double *const rec0 = A.rec + ((size_t)(w.jl + G.R) * (size_t)rowlen + (size_t)w.i0);
+        for (int grp = 1; grp <= G.ngroups; grp++)      /* only the class's own list has matches */
+            if (grp == cgrp) pull_class_waverow(rec0, lane, pl, rowlen, bx, by, s0, s1, s2);
+        return;
+    }
     if ((R == 1 || R == 2) && w.i0 - R >= 0 && w.i0 + 63 + R < G.Nx && j - R >= 0 && j + R < G.Ny) {
         const unsigned int pl = (unsigned int)G.Nx, rowlen = 6u * pl;
         const double *const rec0 = A.rec + ((size_t)(w.jl + G.R) * (size_t)rowlen + (size_t)w.i0);

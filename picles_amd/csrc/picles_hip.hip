@@ -465,7 +465,8 @@ struct picles_ctx {
     /* reach counters, rotating with the steps: the previous step's is read by the pull, the current one is written, the one two
      * steps ahead is cleared (five, not three: row blocks of a pipelined run may be one step apart, see run_pipelined) */
     int *mr_buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int mr_w = 0;                                      /* index of the counter the step in flight writes */
+    int mr_w = 0;                                      /* index of the counter the step in flight writes.  Whoever rotates it counts cmap_hot down, and whoever
+                                                        * launches k_step or k_advance clears the class map's rows ahead while it is positive (cmap_hot below) */
     struct Pipe *pipe = nullptr;                       /* space-time pipelined run (picles_set_pipeline) */
     int pipe_nb = 0;                                   /* requested row blocks per step (0 / 1: off) */
     int cur = 0;
@@ -476,6 +477,12 @@ struct picles_ctx {
      * (DP5 under static winds, the BASELINE launch: waverow_measured); 2 ("require") every flavour, and a fused step with a launch
      * that does not qualify is refused */
     int waverow_mode = 1;
+    /* the tile class map (kernels.h: Arrays::rmap, class_map): PICLES_PULL_CLASS=0, read once at create, turns its reader and its writer
+     * off.  cmap_hot: steps for which a buffer of the map may still hold an entry of a k_step_waverow launch (set to 4 by such a launch,
+     * counted down by every step): while it is positive, the launches of k_step and k_advance — which keep their instruction streams and
+     * clear nothing of this map themselves — have their rows' entries of the clear-ahead buffer zeroed from the host (class_map_clear_rows) */
+    bool pull_class = true;
+    int cmap_hot = 0;
     bool pending = false;
     double pend_t = 0.0, pend_dt = 0.0;
     signed char *d_mask = nullptr;
@@ -631,8 +638,32 @@ static Arrays arrays_for(picles_ctx *c, int read_buf, int write_buf)
     A.rec_out = c->rec_buf[write_buf];
     /* reach counters rotate with the steps, independently of the record pair: a launch that scatters the records it has just
      * written (read_buf == write_buf: k_scatter after k_advance) reads the counter of the step in flight */
-    A.mr_idx = (read_buf == write_buf ? c->mr_w : (c->mr_w + 4) % 5) | (c->mr_w << 4) | (((c->mr_w + 2) % 5) << 8);
+    A.mr_idx = (read_buf == write_buf ? c->mr_w : (c->mr_w + 4) % 5) | (c->mr_w << 4) | (((c->mr_w + 2) % 5) << 8) | (c->pull_class ? MR_CLASS_ON : 0);
     return A;
+}
+
+/* The invariant of the class map: a non-zero entry of the buffer a pull reads means that all 64 records of that tile, in the record
+ * buffer it reads, carry that code.  Every entry point that writes a record buffer by other means than the step kernels — seed,
+ * checkpoint load, the re-packing of picles_set_halo_rows, the particle setter — zeroes all five buffers (DESIGN.md §10 lists them). */
+static int class_map_zero(picles_ctx *c)
+{
+    c->cmap_hot = 0;
+    HIPCHK(c, hipMemsetAsync(c->A.rmap + (size_t)5 * c->A.ntile, 0, (size_t)5 * c->A.ntile * sizeof(int), c->stream));
+    return 0;
+}
+/* the clear-ahead of a k_step or k_advance launch over rows [r0, r0 + n0) and [r1, r1 + n1): every tile the rows touch (a tile shared with a
+ * neighbouring row belongs to a buffer that the whole step clears: nobody reads or writes it during this step) */
+static int class_map_clear_rows(picles_ctx *c, hipStream_t s, int r0, int n0, int r1, int n1)
+{
+    int *const cm = c->A.rmap + (size_t)(5 + (c->mr_w + 2) % 5) * c->A.ntile;
+    const int rr[2] = {r0, r1}, nn[2] = {n0, n1};
+    for (int k = 0; k < 2; k++) {
+        if (nn[k] <= 0) continue;
+        const long long a = ((long long)rr[k] * c->G.Nx) >> 6, b = ((long long)(rr[k] + nn[k]) * c->G.Nx + 63) >> 6;
+        const long long hi = b < (long long)c->A.ntile ? b : (long long)c->A.ntile;
+        if (hi > a) HIPCHK(c, hipMemsetAsync(cm + a, 0, (size_t)(hi - a) * sizeof(int), s));
+    }
+    return 0;
 }
 
 static int launch_scatter(picles_ctx *c, hipStream_t s, bool remesh);
@@ -701,6 +732,7 @@ PX_EXPORT int32_t picles_create(const picles_grid *g, const picles_phys *p, cons
 
     picles_ctx *c = new picles_ctx();
     if (const char *wr = getenv("PICLES_WAVEROW")) c->waverow_mode = !strcmp(wr, "0") ? 0 : (!strcmp(wr, "require") ? 2 : 1);
+    if (const char *pc = getenv("PICLES_PULL_CLASS")) c->pull_class = strcmp(pc, "0") != 0;
     memset(&c->A, 0, sizeof(c->A));
     c->stream = nullptr;
     c->ev_edge = nullptr;
@@ -835,8 +867,8 @@ PX_EXPORT int32_t picles_create(const picles_grid *g, const picles_phys *p, cons
     CK(hipMalloc(&A.ord, (size_t)5 * (2 + A.nblk) * sizeof(int)));      /* (a slab orders the launch over its interior rows: fewer workgroups) */
     CK(hipMemset(A.ord, 0, (size_t)5 * (2 + A.nblk) * sizeof(int)));
     A.ntile = (int)((n + 63) / 64);
-    CK(hipMalloc(&A.rmap, (size_t)5 * A.ntile * sizeof(int)));      /* local reach map, five rotating buffers (kernels.h: Arrays::rmap) */
-    CK(hipMemset(A.rmap, 0, (size_t)5 * A.ntile * sizeof(int)));
+    CK(hipMalloc(&A.rmap, (size_t)10 * A.ntile * sizeof(int)));     /* local reach map, five rotating buffers, and the tile class map behind it, five more (kernels.h: Arrays::rmap) */
+    CK(hipMemset(A.rmap, 0, (size_t)10 * A.ntile * sizeof(int)));
     CK(hipMalloc(&c->d_mask, n));
     CK(hipMemset(A.state, 0, 3 * n * 8)); CK(hipMemset(A.movie, 0, 3 * n * 8)); CK(hipMemset(A.z, 0, 5 * n * 8));
     CK(hipMemset(A.qold, 0, n * 8)); CK(hipMemset(A.dtn, 0, n * 8)); CK(hipMemset(A.on, 0, n)); CK(hipMemset(A.status, 0, n * 4));
@@ -1293,6 +1325,7 @@ PX_EXPORT int32_t picles_seed(picles_ctx *c, double t0)
     HIPCHK(c, hipMemsetAsync(c->A.cnt, 0, NSLOTS * sizeof(DevCounters), c->stream));
     HIPCHK(c, hipMemsetAsync(c->mr_buf[0] + 5, 0, 11 * sizeof(int), c->stream));      /* running maximum + the "calm waves" words (kernels.h: order_wanted) */
     HIPCHK(c, hipMemsetAsync(c->A.rmap, 0, (size_t)5 * c->A.ntile * sizeof(int), c->stream));
+    { int rc = class_map_zero(c); if (rc) return rc; }
     hipLaunchKernelGGL(k_seed, dim3(nblocks(c->A.n, 256)), dim3(256), 0, c->stream, c->P, c->G, arrays_for(c, 0, 0), c->d_mask, c->od.timestep);
     HIPCHK(c, hipGetLastError());
     c->state_zero = false;
@@ -1336,6 +1369,7 @@ PX_EXPORT int32_t picles_begin_step(picles_ctx *c, double dt, int32_t flags)
     c->edge_pending = false;
     c->cur ^= 1;            /* this step's records go to (and are scattered from) rec_buf[cur] */
     c->mr_w = (c->mr_w + 1) % 5;
+    if (c->cmap_hot > 0) c->cmap_hot--;
     c->step_fresh = true;   /* the first advance_rows of the step clears max_reach on ITS stream */
     return 0;
 }
@@ -1392,6 +1426,7 @@ PX_EXPORT int32_t picles_advance_rows(picles_ctx *c, int32_t which, void *stream
     if (nt == 0) return 0;
     if ((rc = step_prologue(c, s))) return rc;
     c->ord_valid = false;        /* the stand-alone advance files no dispatch order */
+    if (c->cmap_hot > 0 && (rc = class_map_clear_rows(c, s, r0, n0, r1, n1))) return rc;
     timing_begin(c, s, 0);
     {
         const KParams &P = c->P;
@@ -1471,10 +1506,12 @@ static int launch_step_rows(picles_ctx *c, int which, hipStream_t s)
         A.ord = nullptr;            /* (this launch neither reads nor files an order) */
         if (c->G.single_slab || which != PICLES_ROWS_EDGE) c->ord_valid = false;
     }
+    const bool waverow = (c->waverow_mode == 2 || (c->waverow_mode == 1 && waverow_measured(P))) && step_rows_waverow(c, which);
+    if (waverow && c->pull_class) c->cmap_hot = 4;       /* its entries live in buffer mr_w until the step after next but one clears them */
+    else if (!waverow && c->cmap_hot > 0 && (rc = class_map_clear_rows(c, s, r0, n0, r1, n1))) return rc;
     timing_begin(c, s, 0);
     {
-        StepLaunch L = {dim3(nblocks(nt, 256)), dim3(256), s, &c->P, &c->G, &A, c->pend_t, c->pend_dt, c->clock, c->step_dt, r0, n0, r1, n1,
-                        (c->waverow_mode == 2 || (c->waverow_mode == 1 && waverow_measured(P))) && step_rows_waverow(c, which)};
+        StepLaunch L = {dim3(nblocks(nt, 256)), dim3(256), s, &c->P, &c->G, &A, c->pend_t, c->pend_dt, c->clock, c->step_dt, r0, n0, r1, n1, waverow};
         if (fast && P.solver == 2) launch_k_step_auto(L, P.wind_static != 0, c->A.pc != nullptr);          /* k_step_auto.hip */
         else launch_k_step_explicit(L, fast, P.solver, P.wind_static != 0, c->A.pc != nullptr);             /* k_step_explicit.hip */
     }
@@ -1532,6 +1569,7 @@ PX_EXPORT int32_t picles_begin_fused_step(picles_ctx *c, double dt)
     c->edge_pending = false;
     c->cur ^= 1;
     c->mr_w = (c->mr_w + 1) % 5;
+    if (c->cmap_hot > 0) c->cmap_hot--;
     c->step_fresh = true;
     return 0;
 }
@@ -1744,6 +1782,8 @@ PX_EXPORT int32_t picles_set_particles(picles_ctx *c, const double *z, const uin
 {
     if (!c) return -1;
     int rc = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = class_map_zero(c))) return rc;
     if (z && (rc = h2d(c, c->A.z, z, 5 * c->A.n * 8))) return rc;
     if (on && (rc = h2d(c, c->A.on, on, c->A.n))) return rc;
     std::vector<double> neg(c->A.n, -1.0);   /* auto_dt_reset! on the next advance */
@@ -1777,6 +1817,19 @@ PX_EXPORT int32_t picles_get_counters(picles_ctx *c, picles_counters *out)
 #endif
     out->max_reach = mr;
     out->max_reach_seen = mrt;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_get_pull_class_counts(picles_ctx *c, int64_t *out)
+{
+    if (!c || !out) return -1;
+    std::vector<DevCounters> d(NSLOTS);
+    HIPCHK(c, hipSetDevice(c->device));
+    /* no flush: a pending fused step stays pending (asking after every step must not take the run off the fused launches it counts) */
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(d.data(), c->A.cnt, NSLOTS * sizeof(DevCounters), hipMemcpyDeviceToHost));
+    out[0] = out[1] = 0;
+    for (const DevCounters &k : d) { out[0] += (int64_t)k.cls; out[1] += (int64_t)k.cls_empty; }
     return 0;
 }
 
@@ -2389,7 +2442,7 @@ PX_EXPORT int32_t picles_set_halo_rows(picles_ctx *c, int32_t r)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipFree(old));
     }
-    return 0;
+    return class_map_zero(c);
 }
 
 PX_EXPORT int32_t picles_set_slab_mode(picles_ctx *c, int32_t on)
@@ -3100,6 +3153,7 @@ PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t 
     if (R != G.R) { int rc = picles_set_halo_rows(c, R); if (rc) return rc; }
     ckpt_launch(c, 2, S, payload);
     HIPCHK(c, hipGetLastError());
+    { int rc = class_map_zero(c); if (rc) return rc; }      /* the map is not part of a checkpoint: it changes speed, never results */
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->clock = h.clock;
     c->step_dt = h.step_dt;

@@ -620,6 +620,13 @@ class HipModel:
         self._ck(self.lib.picles_get_counters(self.h, C.byref(c)), "picles_get_counters")
         return c.as_dict()
 
+    def get_pull_class_counts(self):
+        """(class_waves, empty_waves): waves of the wave-per-row fused step whose pull followed the tile class map, and those among them
+        whose neighbourhood held no record, since the seed / reset_counters"""
+        out = (C.c_int64 * 2)()
+        self._ck(self.lib.picles_get_pull_class_counts(self.h, out), "picles_get_pull_class_counts")
+        return int(out[0]), int(out[1])
+
     def reset_counters(self):
         self._ck(self.lib.picles_reset_counters(self.h), "picles_reset_counters")
 

@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(8)
+const PICLES_ABI_VERSION = Int32(9)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -273,6 +273,16 @@ function dispatch_order(model::WaveGrowth2DHIP)
     out = Vector{Int32}(undef, 2 + n)
     ccall((:picles_get_dispatch_order, libpicles), Int32, (Ptr{Cvoid}, Ptr{Int32}, Int32), model.ctx, out, length(out)) == n || return nothing
     return (Int(out[1]), Int(out[2]), out[3:end])
+end
+
+"""
+diagnostic: `(class_waves, empty_waves)` — waves of the wave-per-row fused step whose pull skipped the candidate codes because their
+whole neighbourhood carried one record code, and those among them whose neighbourhood held no record
+"""
+function pull_class_counts(model::WaveGrowth2DHIP)
+    out = zeros(Int64, 2)
+    check(model.ctx, ccall((:picles_get_pull_class_counts, libpicles), Int32, (Ptr{Cvoid}, Ptr{Int64}), model.ctx, out), "picles_get_pull_class_counts")
+    return (out[1], out[2])
 end
 
 """
