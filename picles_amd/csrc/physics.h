@@ -222,10 +222,17 @@ PM_HD void dp_load(DPTab &T, int solver)
  * explicit pair) — the general-physics and auto-switching ones keep all their arguments live and stay with LDS. */
 typedef const __attribute__((opencl_constant)) double *dp_cptr;
 __device__ __forceinline__ dp_cptr dp_launder(dp_cptr p) { __asm__ volatile("" : "+s"(p)); return p; }
+/* The table's address is taken in a __device__ function, never in the __host__ __device__ integrator itself: a static device
+ * variable that a host-device function names counts as used by the host, is given external linkage and default visibility, and every
+ * TT_STAGE() then fetched its address from the GOT (s_getpc, s_load_dwordx2 …@gotpcrel32, a wait) before the stage's coefficients
+ * could be asked for — two dependent scalar round trips per stage for a link-time constant.  Named here alone the variable stays
+ * local: the address is pc-relative (s_getpc, s_add_u32 …@rel32, s_addc_u32), formed on the scalar unit with no memory access, and
+ * no register carries it across the loop. */
+__device__ __forceinline__ dp_cptr dp_tab_addr(int solver) { return (dp_cptr)&DPTAB_C[solver][0]; }
 #define DP_TAB_DECL(solver)                                                                                      \
     constexpr int dp_solver_ = (solver); constexpr bool dp_smem_ = TABS;                                          \
-    dp_cptr dp_ctab_ = (dp_cptr)&DPTAB_C[dp_solver_][0]; const double *const dp_ltab_ = dp_lds_tab()
-#define TT_STAGE() do { if constexpr (dp_smem_) dp_ctab_ = dp_launder((dp_cptr)&DPTAB_C[dp_solver_][0]); } while (0)
+    dp_cptr dp_ctab_ = dp_tab_addr(dp_solver_); const double *const dp_ltab_ = dp_lds_tab()
+#define TT_STAGE() do { if constexpr (dp_smem_) dp_ctab_ = dp_launder(dp_tab_addr(dp_solver_)); } while (0)
 #define TT(f) (dp_smem_ ? dp_ctab_[__builtin_offsetof(DPTab, f) / 8] : dp_ltab_[__builtin_offsetof(DPTab, f) / 8])
 #else
 #define DP_TAB_DECL(solver) DPTab T; dp_load(T, solver)
@@ -446,6 +453,13 @@ __device__ __forceinline__ const KParams &ros_params(const KParams &)
 #else
 PM_HD const KParams &ros_params(const KParams &P) { return P; }
 #endif
+/* a scalar that was loaded early, handed on behind the vector value `after`: the (empty) instruction is where the load is waited
+ * for, and it cannot stand in front of the chain that produces `after` */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PM_SCALAR_BEHIND(k, after) __asm__("" : "+s"(k) : "v"(after))
+#else
+#define PM_SCALAR_BEHIND(k, after) ((void)0)
+#endif
 
 /* RHS in kernel order: d(lne), d(c̄x), d(c̄y).  The position tendencies are c̄x/Δx, c̄y/Δy
  * (linear in the state, independent of x,y) and are folded into the stepper.
@@ -465,15 +479,27 @@ PM_HD void rhs3(const KParams &P, double lne, double cx, double cy, const WindD 
      * (wind_is_plain).  Where every lane of the wave is plain — one compare and a scalar branch — none of them is evaluated; the
      * rare path evaluates them lane by lane (a NaN y, |c̄| = 0, inf or NaN, is not plain and takes the guarded forms).  The plain
      * values are computed first and overwritten on the rare path (no copies on the common one). */
+    /* The constants of a plain evaluation of the specialised physics, from the kernarg segment like the rare paths' (ros_params), but
+     * asked for HERE, in front of the reciprocal square root, and consumed behind it: the scalar loads used to stand at the head of the
+     * plain block, each directly in front of its wait (KeT4y / KrCay twice per evaluation), and now run under the thirteen dependent
+     * instructions of the Newton chain. */
+    double kCw = P.Cw, kChrh = P.Chrh, kKeT4y = P.KeT4y, kKrCay = P.KrCay;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (FAST) {
+        const KParams &E = ros_params(P);
+        kCw = E.Cw; kChrh = E.Chrh; kKeT4y = E.KeT4y; kKrCay = E.KrCay;
+    }
+#endif
     const double y = pm_rsqrt(c2);
+    if (FAST) { PM_SCALAR_BEHIND(kCw, y); PM_SCALAR_BEHIND(kChrh, y); PM_SCALAR_BEHIND(kKeT4y, y); PM_SCALAR_BEHIND(kKrCay, y); }
     const double y2 = y * y;
     /* dot and cross products on the raw c̄; the cross product is two rounded products and one subtraction: exactly 0 for
      * c̄x = c̄y, u = v */
     const double dotc = PM_FMA(u, cx, v * cy);
     const double crsc = u * cy - v * cx;
     const bool plain = PM_WAVE_ALL(y <= W.ymaxw);
-    double wp = P.Cw * y;                    /* ω_p = (g/2) r_g min(y, ymax) */
-    double aph = (P.Chrh * dotc) * y2;       /* -α_p/2 = -(r_g/4)(c̄·u) min(y², sgmax) */
+    double wp = kCw * y;                     /* ω_p = (g/2) r_g min(y, ymax) */
+    double aph = (kChrh * dotc) * y2;       /* -α_p/2 = -(r_g/4)(c̄·u) min(y², sgmax) */
     double m2 = y2;                          /* min(y, ymax)²: k_p = (g/4) r_g² m2 */
     double m4 = y2 * y2;
     bool y_plain = true;
@@ -558,7 +584,7 @@ PM_HD void rhs3(const KParams &P, double lne, double cx, double cy, const WindD 
     double Dt = 0.0;
     if (FAST || P.dissipation) {
         if (FAST || P.n_is_2) {
-            Dt = Ek8 * P.KeT4y;
+            Dt = Ek8 * kKeT4y;
         } else {
             double ke = (P.g4rg2 * m2) * P.inv_eT;
             Dt = pm_exp(P.n * lne) * pm_pow(ke, 2.0 * P.n);
@@ -567,7 +593,7 @@ PM_HD void rhs3(const KParams &P, double lne, double cx, double cy, const WindD 
     const double IDt = PM_FMA((FAST || P.input) ? P.C_e : 0.0, aH, -Dt);
     /* ω_p r_g S_cg = ω_p r_g C_α Δ e² k_p⁴ */
     double wrS = 0.0;
-    if (FAST || P.peak_shift) wrS = (wp * D) * (Ek8 * P.KrCay);
+    if (FAST || P.peak_shift) wrS = (wp * D) * (Ek8 * kKrCay);
     if (METRIC) Sd = Sd + cx * pc;   /* great-circle term S_sphere = PC(c̄x) = c̄x·coef rides on S_dir */
     d.lne = PM_FMA(wp, IDt, wrS);
     d.cx = PM_FMA(cy, Sd, -(cx * wrS));

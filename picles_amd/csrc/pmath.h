@@ -277,16 +277,22 @@ __device__ __forceinline__ double pm_exp_plain(double a, double sh)   /* sh: the
     double kd;
     if (NEGABS) __asm__("v_fma_f64 %0, -|%1|, %2, %3" : "=v"(kd) : "v"(a), "s"(PM_EXP_RN), "v"(sh));
     else __asm__("v_fma_f64 %0, %1, %2, %3" : "=v"(kd) : "v"(a), "s"(PM_EXP_RN), "v"(sh));
+    /* the table read leaves as soon as kd exists — its address needs nothing else — and its consumer stands behind the polynomial
+     * (below): the LDS round trip runs under the six instructions that need neither the address nor the entry, where it used to be
+     * waited for at once.  The barrier holds DS instructions only (mask 0x7f: every other class may cross) */
+    const uint32_t ki = (uint32_t)pm_bits(kd);
+    const uint64_t tb = pm_bits(pm_lds_tab()[ki & (PM_EXP_N - 1)]);
+    __builtin_amdgcn_sched_barrier(0x7f);
     const double k = kd - 6755399441055744.0;
     double r;
     if (NEGABS) __asm__("v_fma_f64 %0, -%1, %2, -|%3|" : "=v"(r) : "v"(k), "s"(PM_EXP_LHI), "v"(a));   /* |a| is never a value of its own */
     else r = PM_FMA(-k, PM_EXP_LHI, x);
     r = PM_FMA(-k, PM_EXP_LLO, r);
-    const uint32_t ki = (uint32_t)pm_bits(kd);
     const double q = pm_expm1_poly(r);
-    const uint64_t tb = pm_bits(pm_lds_tab()[ki & (PM_EXP_N - 1)]);
+    /* q is an input that the instruction does not read: it orders the adjust, and with it the wait for the table entry, behind
+     * the polynomial without an instruction of its own */
     uint32_t hi;
-    __asm__("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(hi) : "v"(ki), "n"(20 - PM_EXP_SHIFT), "v"((uint32_t)(tb >> 32)));
+    __asm__("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(hi) : "v"(ki), "n"(20 - PM_EXP_SHIFT), "v"((uint32_t)(tb >> 32)), "v"(q));
     const double T = __hiloint2double((int)hi, (int)(uint32_t)tb);
     return PM_FMA(T, q, T);
 }

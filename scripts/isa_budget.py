@@ -67,7 +67,8 @@ def waverow_kernels(unit):
     return [m.group(1) for m in re.finditer(r"^(_Z\d+k_step_waverowI\w*):\s*;", assembly(unit), re.M)]
 
 
-def budget(unit, prefix, verbose=False):
+def _walk(unit, prefix):
+    """(kernel name, header of the RK loop, the kernel's basic blocks with rare stretches split off)"""
     asm = assembly(unit)
     heads = list(re.finditer(r"^(_Z\d+k_(?:step|step_waverow|advance)I\w*):\s*;", asm, re.M))
     sel = [(m, nxt) for m, nxt in zip(heads, heads[1:] + [None]) if m.group(1).startswith(prefix)]
@@ -151,6 +152,17 @@ def budget(unit, prefix, verbose=False):
         if b["hdr"] and b["hdr"][0] not in parents:
             prod[b["hdr"][0]] += sum(bool(re.match(r"v_(fma|fmac|mul)_f64", i)) for i in b["ins"])
     rk = max(prod, key=prod.get)
+    return m.group(1), rk, blocks
+
+
+def rk_common_path(unit, prefix):
+    """the instructions of the RK loop's common path in program order, one list per basic block (rare stretches left out)"""
+    _, rk, blocks = _walk(unit, prefix)
+    return [(b["label"], b["ins"]) for b in blocks if b["hdr"] and b["hdr"][0] == rk and not b["rare"]]
+
+
+def budget(unit, prefix, verbose=False):
+    name, rk, blocks = _walk(unit, prefix)
     tot = Counter()
     per_block = []
     for b in blocks:
@@ -159,7 +171,7 @@ def budget(unit, prefix, verbose=False):
             per_block.append((b["label"] + (" (rare)" if b["rare"] else ""), sum(c.values()), c))
             if not b["rare"]:
                 tot.update(c)
-    return m.group(1), rk, tot, per_block
+    return name, rk, tot, per_block
 
 
 def main():
