@@ -445,6 +445,46 @@ static uint64_t fp_bytes(uint64_t h, const void *p, size_t bytes)
 }
 template <class T> static uint64_t fp_val(uint64_t h, T v) { return fp_bytes(h, &v, sizeof v); }
 
+/* The device-to-host ring behind snapshots (picles_store_*), coarse diagnostics (picles_diag_*) and station probes (picles_probe_*):
+ * `cap` slots in ONE device block and ONE pinned host block, two events per slot.  A producer writes the slot
+ * next_slot() hands out on its own stream and ships it: the copy to the host rides the context's store stream behind the slot's
+ * `ready` event and is followed by its `done` event; a reader waits for the oldest slot's `done` alone.
+ * stride: the slot size rounded up to 16 bytes, the widest alignment a slot's contents ask for (the diagnostics slot keeps its fp64
+ * partials at a 16-byte-aligned offset behind the float32 planes; snapshots and probe samples are fp64 planes): both blocks start
+ * on a far coarser boundary, so every slot, and the partials inside it, stay aligned as in a block of their own. */
+struct OutRing {
+    struct Slot { const unsigned char *host; double time; long long step; };
+    unsigned char *dev = nullptr, *host = nullptr;
+    size_t stride = 0;
+    std::vector<hipEvent_t> ready, done;
+    std::vector<double> time;                      /* c->clock when the slot was shipped */
+    std::vector<long long> step;                   /* the producer's step count at that moment */
+    int head = 0, count = 0, cap = 0;              /* cap == 0: no ring */
+
+    int init(picles_ctx *c, int n_slots, size_t slot_bytes);      /* completes, or leaves nothing behind */
+    void release();                                               /* idempotent; the caller has drained the streams that use the slots */
+    unsigned char *next_slot() const { return count == cap ? nullptr : dev + (size_t)((head + count) % cap) * stride; }   /* nullptr: full */
+    int ship(picles_ctx *c, unsigned char *slot, hipStream_t producer, size_t bytes, long long step_tag);
+    int front(picles_ctx *c, Slot &out);                          /* waits for the oldest slot's copy alone */
+    void drop() { head = (head + 1) % cap; count--; }
+};
+
+/* a sampling schedule counted in completed model steps: step s is due when s = first + k every */
+struct Cadence {
+    int every = 1, first = 1;
+    long long steps = 0;                           /* model steps completed since the schedule was set */
+    bool due(long long s) const { return s >= first && (s - first) % every == 0; }
+    long long due_within(long long n_steps) const  /* samples the next n_steps model steps will take */
+    {
+        const long long a = steps + 1, b = steps + n_steps, f = first, e = every;
+        if (b < f || n_steps <= 0) return 0;
+        /* multiples f + k e inside [max(a, f), b] */
+        const long long lo = a > f ? a : f;
+        const long long k0 = (lo - f + e - 1) / e, k1 = (b - f) / e;
+        return k1 >= k0 ? k1 - k0 + 1 : 0;
+    }
+};
+
 struct picles_ctx {
     picles_grid g;
     picles_phys ph;
@@ -458,20 +498,17 @@ struct picles_ctx {
     hipEvent_t ev_edge;
     hipEvent_t ev_ctx = nullptr;        /* "everything enqueued on the context stream so far": caller streams wait for it */
     bool edge_pending = false;
-    bool step_fresh = false;
     struct SlabRing *ring = nullptr;    /* native RCCL slab ring (picles_slab_*) */
     /* record buffer pair: rec_buf[cur] belongs to the step in flight / last completed advance */
     double *rec_buf[2] = {nullptr, nullptr};
     /* reach counters, rotating with the steps: the previous step's is read by the pull, the current one is written, the one two
-     * steps ahead is cleared (five, not three: row blocks of a pipelined run may be one step apart, see run_pipelined) */
+     * steps ahead is cleared (five, not three: with the read one a step behind and the cleared one two ahead, three counters would
+     * have a launch clear the one it reads, and four would have the NEXT step's launch clear it; with five no launch clears what a
+     * launch of a neighbouring step reads or writes) */
     int *mr_buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     int mr_w = 0;                                      /* index of the counter the step in flight writes.  Whoever rotates it counts cmap_hot down, and whoever
                                                         * launches k_step or k_advance clears the class map's rows ahead while it is positive (cmap_hot below) */
-    struct Pipe *pipe = nullptr;                       /* space-time pipelined run (picles_set_pipeline) */
-    int pipe_nb = 0;                                   /* requested row blocks per step (0 / 1: off) */
     int cur = 0;
-    /* fused stepping: the last advance's records still await their scatter + remesh */
-    bool fuse_steps = true;
     /* k_step_waverow (k_step.inc) for the fused launches whose geometry qualifies; PICLES_WAVEROW, read once at create:
      * 0 never; 1 (default) where it qualifies AND the flavour is the one whose speed has been measured against k_step on the hardware
      * (DP5 under static winds, the BASELINE launch: waverow_measured); 2 ("require") every flavour, and a fused step with a launch
@@ -483,7 +520,7 @@ struct picles_ctx {
      * clear nothing of this map themselves — have their rows' entries of the clear-ahead buffer zeroed from the host (class_map_clear_rows) */
     bool pull_class = true;
     int cmap_hot = 0;
-    bool pending = false;
+    bool pending = false;                              /* fused stepping: the last advance's records still await their scatter + remesh */
     double pend_t = 0.0, pend_dt = 0.0;
     signed char *d_mask = nullptr;
     std::vector<signed char> h_mask;
@@ -504,36 +541,23 @@ struct picles_ctx {
     picles_timing tim{};
     std::vector<float> tim_samples[3];   /* per-launch durations by kind (advance / scatter / remesh) */
     std::string err;
-    /* snapshot ring (run! stores) */
-    int store_slots = 0, store_head = 0, store_count = 0;
-    std::vector<double *> store_dev, store_host;
-    std::vector<hipEvent_t> store_ready, store_done;
-    std::vector<double> store_time;
+    /* the stream every device-to-host copy of the output paths rides on (store_stream_get: made on first use), and the three rings
+     * (OutRing above): snapshots of State (run! stores), coarse diagnostics — a slot is the float32 planes followed by the tile
+     * partials —, station probes — a slot is one sample, 3 planes of probe_n doubles */
     hipStream_t store_stream = nullptr;
-    /* coarse diagnostics ring (picles_diag_*): a slot is the float32 planes followed by the tile partials */
-    int diag_slots = 0, diag_head = 0, diag_count = 0;
+    OutRing store, diag_ring, probe;
     DiagP diag{};
     int diag_nfields = 0, diag_npart = 0;
     size_t diag_field_bytes = 0, diag_part_off = 0, diag_slot_bytes = 0;
-    std::vector<unsigned char *> diag_dev, diag_host;
-    std::vector<hipEvent_t> diag_ready, diag_done;
-    std::vector<double> diag_time;
-    /* station probes (picles_probe_*): the node list, a ring of probe_cap samples (3 planes of probe_n doubles each) on the device
-     * and in pinned host memory, and the step counter the cadence is counted in */
-    int probe_n = 0, probe_every = 1, probe_first = 1, probe_cap = 0, probe_head = 0, probe_count = 0;
-    long long probe_steps = 0;                     /* model steps completed since picles_probe_init */
+    int probe_n = 0;
     int *probe_nodes = nullptr;                    /* device: i plane, then the LOCAL row plane */
-    double *probe_dev = nullptr, *probe_host = nullptr;
-    std::vector<hipEvent_t> probe_ready, probe_done;
-    std::vector<double> probe_time;
-    std::vector<long long> probe_step;
+    Cadence probe_cad;                             /* steps: model steps completed since picles_probe_init */
     /* run statistics (picles_stat_*): one device block of accumulator planes — the fp64 planes of the selected groups first (PEAK,
      * then MEAN), then the uint32 planes (n_wet, then n_exc[k]) —, the host-side scalars, and the event behind the latest
      * operation on the planes (update, reset, upload): operations on another stream wait for it, and so does picles_stat_get */
     bool stat_on = false;
     StatP stat{};
-    int stat_every = 1, stat_first = 1;
-    long long stat_steps = 0;                      /* model steps completed since picles_stat_init */
+    Cadence stat_cad;                              /* steps: model steps completed since picles_stat_init */
     long long stat_samples = 0;
     double stat_t_first = 0.0, stat_t_last = 0.0;
     unsigned char *stat_dev = nullptr;
@@ -575,6 +599,7 @@ struct picles_ctx {
         hipError_t e_ = (call);                                                                \
         if (e_ != hipSuccess) {                                                                \
             (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                    \
+            (void)hipGetLastError();   /* reported here: not left for the next launch check */ \
             return -10;                                                                        \
         }                                                                                      \
     } while (0)
@@ -671,14 +696,17 @@ static int launch_scatter(picles_ctx *c, hipStream_t s, bool remesh);
 /* station probes (defined behind the diagnostics ring) */
 static int probe_room(picles_ctx *c, long long n_steps, const char *who);
 static int probe_take(picles_ctx *c, hipStream_t s);
-static bool probe_due(const picles_ctx *c, long long s);
 static void probe_release(picles_ctx *c);
 /* run statistics (defined behind the station probes) */
 static int stat_update(picles_ctx *c, hipStream_t s);
 static void stat_release(picles_ctx *c);
-static inline bool stat_due(const picles_ctx *c, long long s)
+
+/* a model step has completed: the clock and the step counts the sampling schedules are counted in */
+static void step_completed(picles_ctx *c)
 {
-    return s >= c->stat_first && (s - c->stat_first) % c->stat_every == 0;
+    c->clock += c->step_dt;
+    c->probe_cad.steps++;
+    c->stat_cad.steps++;
 }
 
 /* scatter + remesh of the last fused step, if still outstanding */
@@ -900,14 +928,8 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     if (A.m11) { hipFree(A.m11); hipFree(A.m22); hipFree(A.pc); }
     for (int k = 0; k < 2; k++) hipFree(c->rec_buf[k]);
 
-    for (auto p : c->store_dev) hipFree(p);
-    for (auto p : c->store_host) hipHostFree(p);
-    for (auto e : c->store_ready) hipEventDestroy(e);
-    for (auto e : c->store_done) hipEventDestroy(e);
-    for (auto p : c->diag_dev) hipFree(p);
-    for (auto p : c->diag_host) hipHostFree(p);
-    for (auto e : c->diag_ready) hipEventDestroy(e);
-    for (auto e : c->diag_done) hipEventDestroy(e);
+    c->store.release();
+    c->diag_ring.release();
     probe_release(c);
     if (c->stat_on) hipDeviceSynchronize();     /* updates issued on caller streams read and write the planes about to go */
     stat_release(c);
@@ -1370,15 +1392,12 @@ PX_EXPORT int32_t picles_begin_step(picles_ctx *c, double dt, int32_t flags)
     c->cur ^= 1;            /* this step's records go to (and are scattered from) rec_buf[cur] */
     c->mr_w = (c->mr_w + 1) % 5;
     if (c->cmap_hot > 0) c->cmap_hot--;
-    c->step_fresh = true;   /* the first advance_rows of the step clears max_reach on ITS stream */
     return 0;
 }
 
-/* the specialised variant of the step kernels: every physics switch on, n = 2, p = 3/4, no dead band (all reference scripts) */
-static bool physics_fast(const KParams &P)
-{
-    return P.propagation && P.input && P.dissipation && P.peak_shift && P.direction && P.n_is_2 && P.p_is_075 && P.deadband2 == 0.0;
-}
+/* the specialised variant of the step kernels: every physics switch on, n = 2, p = 3/4, no dead band (all reference scripts).
+ * picles_create works it out once; nothing changes the switches afterwards */
+static bool physics_fast(const KParams &P) { return P.fast_phys != 0; }
 
 /* the row ranges of a selector; false: no such selector */
 static bool rows_of(const GridP &G, int which, int &r0, int &n0, int &r1, int &n1)
@@ -1403,7 +1422,7 @@ static int select_rows(picles_ctx *c, int which, int &r0, int &n0, int &r1, int 
 /* Launches of one step may come on caller-provided streams.  Whatever the library enqueued on its own stream before (the
  * scatter + remesh of a flushed step, a wind-lattice sample, the seed) must be complete before a caller-stream kernel reads
  * it: the caller stream waits for an event recorded on the context stream.  (The step's reach counter needs no clearing
- * here: three counters rotate and the previous step's launches cleared this one — Arrays::max_reach_next.) */
+ * here: five counters rotate and the launches of the step before last cleared this one, kernels.h: reach_counters.) */
 static int step_prologue(picles_ctx *c, hipStream_t s)
 {
     if (s != c->stream && !stream_idle(c->stream)) {     /* an idle context stream has nothing to wait for */
@@ -1448,7 +1467,7 @@ PX_EXPORT int32_t picles_advance_rows(picles_ctx *c, int32_t which, void *stream
 /* can this step ride on fused k_step launches? (run!-style: State zeroed first, static winds) */
 static bool step_fusable(const picles_ctx *c, int flags, double dt)
 {
-    if (flags != PICLES_STEP_ZERO_FIRST || !c->fuse_steps) return false;
+    if (flags != PICLES_STEP_ZERO_FIRST) return false;
     const KParams &P = c->P;
     /* a polyline window (two or more lattice knots inside the step; host levels set by picles_set_winds_polyline) takes the plain
      * phases: only the general flavours of the stand-alone advance evaluate one */
@@ -1570,7 +1589,6 @@ PX_EXPORT int32_t picles_begin_fused_step(picles_ctx *c, double dt)
     c->cur ^= 1;
     c->mr_w = (c->mr_w + 1) % 5;
     if (c->cmap_hot > 0) c->cmap_hot--;
-    c->step_fresh = true;
     return 0;
 }
 
@@ -1592,9 +1610,7 @@ PX_EXPORT int32_t picles_end_fused_step(picles_ctx *c)
     c->pend_dt = c->step_dt;
     c->state_zero = false;
     c->edge_pending = false;
-    c->clock += c->step_dt;
-    c->probe_steps++;
-    c->stat_steps++;
+    step_completed(c);
     return 0;
 }
 
@@ -1644,15 +1660,9 @@ PX_EXPORT int32_t picles_scatter_remesh(picles_ctx *c, void *stream)
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     if (c->edge_pending) { HIPCHK(c, hipStreamWaitEvent(s, c->ev_edge, 0)); c->edge_pending = false; }
-    if (s != c->stream && !stream_idle(c->stream)) {   /* ordered behind whatever the library enqueued on its own stream (see step_prologue) */
-        HIPCHK(c, hipEventRecord(c->ev_ctx, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_ctx, 0));
-    }
-    int rc = launch_scatter(c, s, true);
-    if (rc) return rc;
-    c->clock += c->step_dt;
-    c->probe_steps++;
-    c->stat_steps++;
+    int rc = step_prologue(c, s);      /* ordered behind whatever the library enqueued on its own stream */
+    if (rc || (rc = launch_scatter(c, s, true))) return rc;
+    step_completed(c);
     return 0;
 }
 
@@ -1683,9 +1693,9 @@ PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
     if (rc) return rc;
     /* the sample of this step: directly behind its launch on the context stream.  The next step's launch reads the record buffer
      * the probe reads and writes the other one: stream order is all the ordering there is */
-    if (c->probe_n && probe_due(c, c->probe_steps)) { if ((rc = probe_take(c, c->stream))) return rc; }
+    if (c->probe_n && c->probe_cad.due(c->probe_cad.steps)) { if ((rc = probe_take(c, c->stream))) return rc; }
     /* the statistics update of this step: the same place, the same ordering */
-    if (c->stat_on && stat_due(c, c->stat_steps)) return stat_update(c, c->stream);
+    if (c->stat_on && c->stat_cad.due(c->stat_cad.steps)) return stat_update(c, c->stream);
     return 0;
 }
 
@@ -1893,64 +1903,107 @@ PX_EXPORT int32_t picles_get_timing_samples(picles_ctx *c, int32_t kind, double 
     return (int32_t)v.size();
 }
 
+/* ---- the output ring (OutRing, in front of the context) ---- */
+static int store_stream_get(picles_ctx *c)      /* the store stream, made by whoever needs it first */
+{
+    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    return 0;
+}
+
+/* the hand-off every output path ends with: `bytes` at dev are complete in the order of stream `producer`; copy them to the pinned
+ * block at host on the store stream, beside whatever the producer runs next.  `done` tells a reader that the copy has landed */
+static int ship_d2h(picles_ctx *c, hipStream_t producer, hipEvent_t ready, hipEvent_t done, void *host, const void *dev, size_t bytes)
+{
+    HIPCHK(c, hipEventRecord(ready, producer));
+    HIPCHK(c, hipStreamWaitEvent(c->store_stream, ready, 0));
+    HIPCHK(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->store_stream));
+    HIPCHK(c, hipEventRecord(done, c->store_stream));
+    return 0;
+}
+
+void OutRing::release()
+{
+    if (dev) hipFree(dev);
+    if (host) hipHostFree(host);
+    for (auto *v : {&ready, &done})
+        for (hipEvent_t e : *v) if (e) hipEventDestroy(e);
+    *this = OutRing{};
+}
+
+int OutRing::init(picles_ctx *c, int n_slots, size_t slot_bytes)
+{
+    struct Undo { OutRing *r; ~Undo() { if (r) r->release(); } } undo{this};
+    { int rc = store_stream_get(c); if (rc) return rc; }
+    stride = (slot_bytes + 15) & ~(size_t)15;
+    HIPCHK(c, hipMalloc(&dev, (size_t)n_slots * stride));
+    HIPCHK(c, hipHostMalloc(&host, (size_t)n_slots * stride, hipHostMallocDefault));
+    ready.assign(n_slots, nullptr);
+    done.assign(n_slots, nullptr);
+    for (int k = 0; k < n_slots; k++) {
+        HIPCHK(c, hipEventCreateWithFlags(&ready[k], hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+    }
+    time.assign(n_slots, 0.0);
+    step.assign(n_slots, 0);
+    cap = n_slots;
+    undo.r = nullptr;
+    return 0;
+}
+
+int OutRing::ship(picles_ctx *c, unsigned char *slot, hipStream_t producer, size_t bytes, long long step_tag)
+{
+    const int k = (int)((size_t)(slot - dev) / stride);
+    { int rc = ship_d2h(c, producer, ready[k], done[k], host + (slot - dev), slot, bytes); if (rc) return rc; }
+    time[k] = c->clock;
+    step[k] = step_tag;
+    count++;
+    return 0;
+}
+
+int OutRing::front(picles_ctx *c, Slot &out)
+{
+    HIPCHK(c, hipEventSynchronize(done[head]));      /* this slot's copy alone: later work stays enqueued */
+    out = Slot{host + (size_t)head * stride, time[head], step[head]};
+    return 0;
+}
+
 /* ---- snapshot ring ---- */
 PX_EXPORT int32_t picles_store_init(picles_ctx *c, int32_t n_slots)
 {
     if (!c || n_slots < 1) return -1;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->store_slots) return fail(c, -2, "store already initialised");
-    size_t b = 3 * (size_t)c->A.n * 8;
-    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));   /* (a checkpoint may have made it) */
-    for (int k = 0; k < n_slots; k++) {
-        double *d = nullptr, *h = nullptr;
-        hipEvent_t e1, e2;
-        HIPCHK(c, hipMalloc(&d, b));
-        HIPCHK(c, hipHostMalloc(&h, b, hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-        c->store_dev.push_back(d); c->store_host.push_back(h);
-        c->store_ready.push_back(e1); c->store_done.push_back(e2);
-    }
-    c->store_time.assign(n_slots, 0.0);
-    c->store_slots = n_slots; c->store_head = 0; c->store_count = 0;
-    return 0;
+    if (c->store.cap) return fail(c, -2, "store already initialised");
+    return c->store.init(c, n_slots, 3 * (size_t)c->A.n * 8);
 }
 
-PX_EXPORT int32_t picles_store_pending(const picles_ctx *c) { return c ? c->store_count : -1; }
+PX_EXPORT int32_t picles_store_pending(const picles_ctx *c) { return c ? c->store.count : -1; }
 
 PX_EXPORT int32_t picles_store_push(picles_ctx *c)
 {
     if (!c) return -1;
-    if (!c->store_slots) return fail(c, -2, "picles_store_init first");
-    if (c->store_count == c->store_slots) return fail(c, -3, "snapshot ring full: pop first");
+    if (!c->store.cap) return fail(c, -2, "picles_store_init first");
+    unsigned char *d = c->store.next_slot();
+    if (!d) return fail(c, -3, "snapshot ring full: pop first");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = flush(c); if (rc) return rc; }
     if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* an un-fused slab step leaves its scatter on the ring's stream M */
-    int slot = (c->store_head + c->store_count) % c->store_slots;
-    size_t b = 3 * (size_t)c->A.n * 8;
+    const size_t b = 3 * (size_t)c->A.n * 8;
     /* stream-ordered behind the step that produced State; the D2H leg runs beside the next steps */
-    HIPCHK(c, hipMemcpyAsync(c->store_dev[slot], c->A.state, b, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->store_ready[slot], c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->store_ready[slot], 0));
-    HIPCHK(c, hipMemcpyAsync(c->store_host[slot], c->store_dev[slot], b, hipMemcpyDeviceToHost, c->store_stream));
-    HIPCHK(c, hipEventRecord(c->store_done[slot], c->store_stream));
-    c->store_time[slot] = c->clock;
-    c->store_count++;
-    return 0;
+    HIPCHK(c, hipMemcpyAsync(d, c->A.state, b, hipMemcpyDeviceToDevice, c->stream));
+    return c->store.ship(c, d, c->stream, b, 0);
 }
 
 PX_EXPORT int32_t picles_store_pop(picles_ctx *c, double *state, double *time)
 {
     if (!c || !state) return -1;
-    if (!c->store_count) return fail(c, -3, "no snapshot pending");
+    if (!c->store.count) return fail(c, -3, "no snapshot pending");
     HIPCHK(c, hipSetDevice(c->device));
-    int slot = c->store_head;
-    HIPCHK(c, hipEventSynchronize(c->store_done[slot]));
-    memcpy(state, c->store_host[slot], 3 * (size_t)c->A.n * 8);
-    if (time) *time = c->store_time[slot];
-    c->store_head = (c->store_head + 1) % c->store_slots;
-    c->store_count--;
+    OutRing::Slot s;
+    { int rc = c->store.front(c, s); if (rc) return rc; }
+    memcpy(state, s.host, 3 * (size_t)c->A.n * 8);
+    if (time) *time = s.time;
+    c->store.drop();
     return 0;
 }
 
@@ -1961,7 +2014,7 @@ PX_EXPORT int32_t picles_diag_init(picles_ctx *c, int32_t cx, int32_t cy, int32_
     if (cx < 1 || cx > 16 || cy < 1 || cy > 16) return fail(c, -2, "picles_diag_init: coarsening factors must be 1 ... 16");
     if (field_mask <= 0 || (field_mask & ~PICLES_DIAG_ALL)) return fail(c, -2, "picles_diag_init: empty or unknown field mask");
     if (n_slots < 1) return fail(c, -2, "picles_diag_init: n_slots must be >= 1");
-    if (c->diag_slots) return fail(c, -2, "picles_diag_init: diagnostics already initialised");
+    if (c->diag_ring.cap) return fail(c, -2, "picles_diag_init: diagnostics already initialised");
     if (c->G.j_begin % cy != 0) return fail(c, -2, "picles_diag_init: the slab's j_begin must be a multiple of cy (coarse cells are global)");
     HIPCHK(c, hipSetDevice(c->device));
     DiagP D{};
@@ -1971,29 +2024,15 @@ PX_EXPORT int32_t picles_diag_init(picles_ctx *c, int32_t cx, int32_t cy, int32_
     D.mask = (unsigned)field_mask; D.g = c->ph.g; D.r_g = c->ph.r_g; D.plane = c->A.n;
     const int nf = __builtin_popcount((unsigned)field_mask), np = D.nyc_loc * D.tiles_per_row;
     const size_t fb = (size_t)4 * D.Nxc * D.nyc_loc * nf, po = (fb + 15) & ~(size_t)15, sb = po + (size_t)np * 7 * 8;
-    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
-    for (int k = 0; k < n_slots; k++) {
-        unsigned char *d = nullptr, *h = nullptr;
-        hipEvent_t e1, e2;
-        HIPCHK(c, hipMalloc(&d, sb));
-        c->diag_dev.push_back(d);
-        HIPCHK(c, hipHostMalloc(&h, sb, hipHostMallocDefault));
-        c->diag_host.push_back(h);
-        HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-        c->diag_ready.push_back(e1);
-        HIPCHK(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-        c->diag_done.push_back(e2);
-    }
+    { int rc = c->diag_ring.init(c, n_slots, sb); if (rc) return rc; }
     c->diag = D; c->diag_nfields = nf; c->diag_npart = np;
     c->diag_field_bytes = fb; c->diag_part_off = po; c->diag_slot_bytes = sb;
-    c->diag_time.assign(n_slots, 0.0);
-    c->diag_slots = n_slots; c->diag_head = 0; c->diag_count = 0;
     return 0;
 }
 
 PX_EXPORT int32_t picles_diag_shape(const picles_ctx *c, int32_t *nxc, int32_t *nyc_loc, int32_t *n_fields, int32_t *n_partials, size_t *bytes)
 {
-    if (!c || !c->diag_slots) return -1;
+    if (!c || !c->diag_ring.cap) return -1;
     if (nxc) *nxc = c->diag.Nxc;
     if (nyc_loc) *nyc_loc = c->diag.nyc_loc;
     if (n_fields) *n_fields = c->diag_nfields;
@@ -2002,7 +2041,7 @@ PX_EXPORT int32_t picles_diag_shape(const picles_ctx *c, int32_t *nxc, int32_t *
     return 0;
 }
 
-PX_EXPORT int32_t picles_diag_pending(const picles_ctx *c) { return c ? c->diag_count : -1; }
+PX_EXPORT int32_t picles_diag_pending(const picles_ctx *c) { return c ? c->diag_ring.count : -1; }
 
 template <int CX, bool VEC>
 static void diag_launch(picles_ctx *c, unsigned char *slot)
@@ -2014,13 +2053,12 @@ static void diag_launch(picles_ctx *c, unsigned char *slot)
 PX_EXPORT int32_t picles_diag_push(picles_ctx *c)
 {
     if (!c) return -1;
-    if (!c->diag_slots) return fail(c, -2, "picles_diag_init first");
-    if (c->diag_count == c->diag_slots) return fail(c, -3, "diagnostics ring full: pop first");
+    if (!c->diag_ring.cap) return fail(c, -2, "picles_diag_init first");
+    unsigned char *d = c->diag_ring.next_slot();
+    if (!d) return fail(c, -3, "diagnostics ring full: pop first");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = flush(c); if (rc) return rc; }
     if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* an un-fused slab step leaves its scatter on the ring's stream M */
-    const int slot = (c->diag_head + c->diag_count) % c->diag_slots;
-    unsigned char *d = c->diag_dev[slot];
     const bool vec = (c->diag.Nx & 1) == 0;                  /* every cell's row segment then starts on a 16-byte boundary */
     timing_begin(c, c->stream, 4);
     switch (c->diag.cx) {
@@ -2032,55 +2070,32 @@ PX_EXPORT int32_t picles_diag_push(picles_ctx *c)
     timing_end(c, c->stream);
     HIPCHK(c, hipGetLastError());
     /* stream-ordered behind the step that produced State; the D2H leg runs beside the next steps */
-    HIPCHK(c, hipEventRecord(c->diag_ready[slot], c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->diag_ready[slot], 0));
-    HIPCHK(c, hipMemcpyAsync(c->diag_host[slot], d, c->diag_slot_bytes, hipMemcpyDeviceToHost, c->store_stream));
-    HIPCHK(c, hipEventRecord(c->diag_done[slot], c->store_stream));
-    c->diag_time[slot] = c->clock;
-    c->diag_count++;
-    return 0;
+    return c->diag_ring.ship(c, d, c->stream, c->diag_slot_bytes, 0);
 }
 
 PX_EXPORT int32_t picles_diag_pop(picles_ctx *c, void *fields, double *partials, double *time)
 {
     if (!c || !fields) return -1;
-    if (!c->diag_count) return fail(c, -3, "no diagnostics snapshot pending");
+    if (!c->diag_ring.count) return fail(c, -3, "no diagnostics snapshot pending");
     HIPCHK(c, hipSetDevice(c->device));
-    const int slot = c->diag_head;
-    HIPCHK(c, hipEventSynchronize(c->diag_done[slot]));
-    memcpy(fields, c->diag_host[slot], c->diag_field_bytes);
-    if (partials) memcpy(partials, c->diag_host[slot] + c->diag_part_off, (size_t)c->diag_npart * 7 * 8);
-    if (time) *time = c->diag_time[slot];
-    c->diag_head = (c->diag_head + 1) % c->diag_slots;
-    c->diag_count--;
+    OutRing::Slot s;
+    { int rc = c->diag_ring.front(c, s); if (rc) return rc; }
+    memcpy(fields, s.host, c->diag_field_bytes);
+    if (partials) memcpy(partials, s.host + c->diag_part_off, (size_t)c->diag_npart * 7 * 8);
+    if (time) *time = s.time;
+    c->diag_ring.drop();
     return 0;
 }
 
 /* ---- station probes (the contract: include/picles_hip.h; the kernel: k_probe.h) ---- */
-static bool probe_due(const picles_ctx *c, long long s)
-{
-    return s >= c->probe_first && (s - c->probe_first) % c->probe_every == 0;
-}
-
-/* samples the next n_steps model steps will take */
-static long long probe_due_within(const picles_ctx *c, long long n_steps)
-{
-    const long long a = c->probe_steps + 1, b = c->probe_steps + n_steps, f = c->probe_first, e = c->probe_every;
-    if (b < f || n_steps <= 0) return 0;
-    /* multiples f + k e inside [max(a, f), b] */
-    const long long lo = a > f ? a : f;
-    const long long k0 = (lo - f + e - 1) / e, k1 = (b - f) / e;
-    return k1 >= k0 ? k1 - k0 + 1 : 0;
-}
-
 /* would the samples of the next n_steps steps overrun the ring?  Asked by the step entry points before they change anything */
 static int probe_room(picles_ctx *c, long long n_steps, const char *who)
 {
     if (!c->probe_n) return 0;
-    const long long due = probe_due_within(c, n_steps);
-    if (due && c->probe_count + due > c->probe_cap)
-        return fail(c, PICLES_PROBE_E_FULL, std::string(who) + ": probe ring full (" + std::to_string(c->probe_count) + " samples pending, " +
-                                            std::to_string(due) + " due, capacity " + std::to_string(c->probe_cap) + "): picles_probe_pop first");
+    const long long due = c->probe_cad.due_within(n_steps);
+    if (due && c->probe.count + due > c->probe.cap)
+        return fail(c, PICLES_PROBE_E_FULL, std::string(who) + ": probe ring full (" + std::to_string(c->probe.count) + " samples pending, " +
+                                            std::to_string(due) + " due, capacity " + std::to_string(c->probe.cap) + "): picles_probe_pop first");
     return 0;
 }
 
@@ -2089,37 +2104,25 @@ static int probe_room(picles_ctx *c, long long n_steps, const char *who)
  * point; otherwise from State.  Neither the pending step nor any plane of the model is touched; the host does not wait. */
 static int probe_take(picles_ctx *c, hipStream_t s)
 {
-    if (c->probe_count == c->probe_cap) return fail(c, PICLES_PROBE_E_FULL, "probe ring full: picles_probe_pop first");
-    const int slot = (c->probe_head + c->probe_count) % c->probe_cap;
-    const size_t sample = (size_t)3 * c->probe_n;
-    double *d = c->probe_dev + (size_t)slot * sample;
+    unsigned char *slot = c->probe.next_slot();
+    if (!slot) return fail(c, PICLES_PROBE_E_FULL, "probe ring full: picles_probe_pop first");
+    double *d = (double *)slot;
     const dim3 grid(nblocks(c->probe_n, PROBE_BLOCK)), block(PROBE_BLOCK);
     if (c->pending)
         hipLaunchKernelGGL(k_probe<true>, grid, block, 0, s, c->G, arrays_for(c, c->cur, c->cur), c->probe_n, (const int *)c->probe_nodes, d);
     else
         hipLaunchKernelGGL(k_probe<false>, grid, block, 0, s, c->G, c->A, c->probe_n, (const int *)c->probe_nodes, d);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->probe_ready[slot], s));
-    HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->probe_ready[slot], 0));
-    HIPCHK(c, hipMemcpyAsync(c->probe_host + (size_t)slot * sample, d, sample * sizeof(double), hipMemcpyDeviceToHost, c->store_stream));
-    HIPCHK(c, hipEventRecord(c->probe_done[slot], c->store_stream));
-    c->probe_time[slot] = c->clock;
-    c->probe_step[slot] = c->probe_steps;
-    c->probe_count++;
-    return 0;
+    return c->probe.ship(c, slot, s, (size_t)3 * c->probe_n * sizeof(double), c->probe_cad.steps);
 }
 
 static void probe_release(picles_ctx *c)
 {
     if (c->probe_nodes) hipFree(c->probe_nodes);
-    if (c->probe_dev) hipFree(c->probe_dev);
-    if (c->probe_host) hipHostFree(c->probe_host);
-    for (auto e : c->probe_ready) hipEventDestroy(e);
-    for (auto e : c->probe_done) hipEventDestroy(e);
-    c->probe_nodes = nullptr; c->probe_dev = nullptr; c->probe_host = nullptr;
-    c->probe_ready.clear(); c->probe_done.clear(); c->probe_time.clear(); c->probe_step.clear();
-    c->probe_n = 0; c->probe_cap = 0; c->probe_head = 0; c->probe_count = 0; c->probe_steps = 0;
-    c->probe_every = 1; c->probe_first = 1;
+    c->probe_nodes = nullptr;
+    c->probe.release();
+    c->probe_n = 0;
+    c->probe_cad = Cadence{};
 }
 
 PX_EXPORT int32_t picles_probe_init(picles_ctx *c, int32_t n, const int32_t *ij, int32_t every, int32_t first, int32_t capacity)
@@ -2139,24 +2142,11 @@ PX_EXPORT int32_t picles_probe_init(picles_ctx *c, int32_t n, const int32_t *ij,
         loc[(size_t)n + k] = j - G.j_begin;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t ring = (size_t)capacity * 3 * (size_t)n * sizeof(double);
     struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) probe_release(c); } } undo{c, true};
-    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    { int rc = c->probe.init(c, capacity, (size_t)3 * n * sizeof(double)); if (rc) return rc; }
     HIPCHK(c, hipMalloc(&c->probe_nodes, (size_t)2 * n * sizeof(int)));
-    HIPCHK(c, hipMalloc(&c->probe_dev, ring));
-    HIPCHK(c, hipHostMalloc(&c->probe_host, ring, hipHostMallocDefault));
-    for (int k = 0; k < capacity; k++) {
-        hipEvent_t e1, e2;
-        HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-        c->probe_ready.push_back(e1);
-        HIPCHK(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-        c->probe_done.push_back(e2);
-    }
     HIPCHK(c, hipMemcpy(c->probe_nodes, loc.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice));     /* blocking: loc dies here */
-    c->probe_time.assign(capacity, 0.0);
-    c->probe_step.assign(capacity, 0);
-    c->probe_every = every; c->probe_first = first; c->probe_cap = capacity;
-    c->probe_head = 0; c->probe_count = 0; c->probe_steps = 0;
+    c->probe_cad = Cadence{every, first, 0};
     c->probe_n = n;
     undo.armed = false;
     return 0;
@@ -2166,18 +2156,18 @@ PX_EXPORT int32_t picles_probe_shape(const picles_ctx *c, int32_t *n, int32_t *e
 {
     if (!c || !c->probe_n) return -1;
     if (n) *n = c->probe_n;
-    if (every) *every = c->probe_every;
-    if (capacity) *capacity = c->probe_cap;
+    if (every) *every = c->probe_cad.every;
+    if (capacity) *capacity = c->probe.cap;
     return 0;
 }
 
-PX_EXPORT int32_t picles_probe_pending(const picles_ctx *c) { return c ? c->probe_count : -1; }
+PX_EXPORT int32_t picles_probe_pending(const picles_ctx *c) { return c ? c->probe.count : -1; }
 
 PX_EXPORT int32_t picles_probe_sample(picles_ctx *c, void *stream)
 {
     if (!c) return -1;
     if (!c->probe_n) return fail(c, -2, "picles_probe_init first");
-    if (c->probe_count == c->probe_cap) return fail(c, PICLES_PROBE_E_FULL, "picles_probe_sample: probe ring full: picles_probe_pop first");
+    if (!c->probe.next_slot()) return fail(c, PICLES_PROBE_E_FULL, "picles_probe_sample: probe ring full: picles_probe_pop first");
     HIPCHK(c, hipSetDevice(c->device));
     return probe_take(c, stream ? (hipStream_t)stream : c->stream);
 }
@@ -2188,18 +2178,17 @@ PX_EXPORT int32_t picles_probe_pop(picles_ctx *c, int32_t max_samples, double *v
     if (n_out) *n_out = 0;
     if (!c->probe_n) return fail(c, -2, "picles_probe_init first");
     if (max_samples < 1 || !values || !n_out) return fail(c, -2, "picles_probe_pop: max_samples must be >= 1, values and n_out given");
-    if (!c->probe_count) return fail(c, -3, "no probe sample pending");
+    if (!c->probe.count) return fail(c, -3, "no probe sample pending");
     HIPCHK(c, hipSetDevice(c->device));
-    const int m = max_samples < c->probe_count ? max_samples : c->probe_count;
+    const int m = max_samples < c->probe.count ? max_samples : c->probe.count;
     const size_t sample = (size_t)3 * c->probe_n;
     for (int k = 0; k < m; k++) {
-        const int slot = c->probe_head;
-        HIPCHK(c, hipEventSynchronize(c->probe_done[slot]));      /* this sample's copy alone: later steps stay enqueued */
-        memcpy(values + (size_t)k * sample, c->probe_host + (size_t)slot * sample, sample * sizeof(double));
-        if (times) times[k] = c->probe_time[slot];
-        if (steps) steps[k] = (int64_t)c->probe_step[slot];
-        c->probe_head = (c->probe_head + 1) % c->probe_cap;
-        c->probe_count--;
+        OutRing::Slot s;
+        { int rc = c->probe.front(c, s); if (rc) return rc; }      /* this sample's copy alone: later steps stay enqueued */
+        memcpy(values + (size_t)k * sample, s.host, sample * sizeof(double));
+        if (times) times[k] = s.time;
+        if (steps) steps[k] = (int64_t)s.step;
+        c->probe.drop();
         *n_out = k + 1;
     }
     return 0;
@@ -2278,7 +2267,7 @@ static void stat_release(picles_ctx *c)
     if (c->stat_ev) hipEventDestroy(c->stat_ev);
     c->stat_dev = nullptr; c->stat_ev = nullptr; c->stat_stream = nullptr; c->stat_ev_live = false;
     c->stat_on = false; c->stat = StatP{}; c->stat_bytes = 0;
-    c->stat_every = 1; c->stat_first = 1; c->stat_steps = 0;
+    c->stat_cad = Cadence{};
     c->stat_samples = 0; c->stat_t_first = 0.0; c->stat_t_last = 0.0;
 }
 
@@ -2305,13 +2294,13 @@ PX_EXPORT int32_t picles_stat_init(picles_ctx *c, int32_t group_mask, int32_t n_
     for (int k = 0; k < n_thresholds; k++) S.thr[k] = thresholds[k];
     const size_t bytes = (size_t)c->A.n * ((size_t)stat_nf64(S) * 8 + (size_t)stat_nu32(S) * 4);
     struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) stat_release(c); } } undo{c, true};
-    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    { int rc = store_stream_get(c); if (rc) return rc; }
     HIPCHK(c, hipMalloc(&c->stat_dev, bytes));
     HIPCHK(c, hipEventCreateWithFlags(&c->stat_ev, hipEventDisableTiming));
     HIPCHK(c, hipMemsetAsync(c->stat_dev, 0, bytes, c->stream));
     c->stat = S; c->stat_bytes = bytes;
     { int rc = stat_mark(c, c->stream); if (rc) return rc; }
-    c->stat_every = every; c->stat_first = first; c->stat_steps = 0;
+    c->stat_cad = Cadence{every, first, 0};
     c->stat_samples = 0; c->stat_t_first = 0.0; c->stat_t_last = 0.0;
     c->stat_on = true;
     undo.armed = false;
@@ -2325,7 +2314,7 @@ PX_EXPORT int32_t picles_stat_shape(const picles_ctx *c, int32_t *group_mask, in
     if (group_mask) *group_mask = (int32_t)c->stat.mask;
     if (n_thresholds) *n_thresholds = c->stat.nthr;
     if (thresholds) for (int k = 0; k < c->stat.nthr; k++) thresholds[k] = c->stat.thr[k];
-    if (every) *every = c->stat_every;
+    if (every) *every = c->stat_cad.every;
     if (n_planes) *n_planes = stat_nf64(c->stat) + stat_nu32(c->stat);
     if (bytes) *bytes = c->stat_bytes;
     return 0;
@@ -2743,8 +2732,8 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
         rc = (fused == 0) ? picles_step_rows(c, PICLES_ROWS_INTERIOR, R->sM) : picles_advance_rows(c, PICLES_ROWS_INTERIOR, R->sM);
         if (rc) return rc;
         if (phases) { HIPCHK(c, hipEventRecord(pe.m1, R->sM)); R->ph_used.push_back(pe); }
-        const bool probe = c->probe_n && probe_due(c, c->probe_steps + 1);
-        const bool stat = c->stat_on && stat_due(c, c->stat_steps + 1);      /* the statistics update: ordered exactly as a probe */
+        const bool probe = c->probe_n && c->probe_cad.due(c->probe_cad.steps + 1);
+        const bool stat = c->stat_on && c->stat_cad.due(c->stat_cad.steps + 1);      /* the statistics update: ordered exactly as a probe */
         const bool sample = probe || stat;
         if (sample && fused == 0) {      /* what the probe of a fused step waits for: the interior launch and the delivered halo */
             HIPCHK(c, hipEventRecord(R->evPm, R->sM));
@@ -3008,7 +2997,7 @@ static uint64_t ckpt_fingerprint(const picles_ctx *c)
 static int ckpt_buffers(picles_ctx *c, unsigned long long payload)
 {
     const size_t need = (size_t)payload + 16;
-    if (!c->store_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->store_stream, hipStreamNonBlocking));
+    { int rc = store_stream_get(c); if (rc) return rc; }
     if (!c->ck_ready) {
         HIPCHK(c, hipEventCreateWithFlags(&c->ck_ready, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ck_done, hipEventDisableTiming));
@@ -3061,10 +3050,7 @@ PX_EXPORT int32_t picles_checkpoint_begin(picles_ctx *c)
     timing_end(c, c->stream);
     HIPCHK(c, hipGetLastError());
     /* stream-ordered behind the pack; the D2H leg runs beside whatever the caller enqueues next (as picles_store_push) */
-    HIPCHK(c, hipEventRecord(c->ck_ready, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->ck_ready, 0));
-    HIPCHK(c, hipMemcpyAsync(c->ck_host, c->ck_dev, (size_t)payload + 8, hipMemcpyDeviceToHost, c->store_stream));
-    HIPCHK(c, hipEventRecord(c->ck_done, c->store_stream));
+    { int rc = ship_d2h(c, c->stream, c->ck_ready, c->ck_done, c->ck_host, c->ck_dev, (size_t)payload + 8); if (rc) return rc; }
     CkptHeader h;
     memset(&h, 0, sizeof h);
     h.magic = CKPT_MAGIC; h.format = CKPT_FORMAT; h.abi = PICLES_ABI_VERSION;
@@ -3105,9 +3091,9 @@ PX_EXPORT int32_t picles_checkpoint_end(picles_ctx *c, void *buf, size_t bytes)
 PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t bytes)
 {
     if (!c || !buf) return -1;
-    if (c->probe_count > 0)
+    if (c->probe.count > 0)
         return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_load: probe samples of this context are pending (picles_probe_pop first)");
-    if (c->ck_inflight || c->store_count > 0 || c->diag_count > 0)
+    if (c->ck_inflight || c->store.count > 0 || c->diag_ring.count > 0)
         return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_load: a checkpoint or store snapshot of this context is in flight (end / pop it first)");
     CkptHeader h;
     if (bytes < sizeof h) return fail(c, PICLES_CKPT_E_SHORT, "picles_checkpoint_load: buffer shorter than a checkpoint header");
@@ -3163,7 +3149,6 @@ PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t 
     c->state_zero = h.state_zero != 0;
     c->seeded = true;
     c->edge_pending = false;
-    c->step_fresh = false;
     c->ord_valid = false;     /* the dispatch order is scheduling only: the first fused step after a load runs in natural order */
     c->wind_t1_valid = false; /* a lattice window is sampled afresh (the same bits: the sampler is a function of the time alone) */
     return 0;

@@ -1,7 +1,10 @@
 """The host side of the station-probe ring (picles_probe_*) under AddressSanitizer + UBSan on the CPU box: the four translation
 units host-only against the fake HIP runtime, as tests/test_host_asan.py builds them (same Makefile, same objects), driven by
 tests/native/host_asan/probe_harness.cpp — exact-size buffers for every pop, wrap-around of the ring, every refusal, a full ring's
-refusal followed by a pop and the same call again, whole-grid and slab contexts, free and destroy with samples pending."""
+refusal followed by a pop and the same call again, whole-grid and slab contexts, free and destroy with samples pending.  Its second kind
+of program puts a snapshot ring, a diagnostics ring, a probe set and a checkpoint in flight on one context at once (they share the
+store stream and the ring code), and sets each ring up through every allocation failure its init can meet: a failed init leaves
+nothing behind and the next one works."""
 import os
 import shutil
 import subprocess
