@@ -20,6 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _capi as K
+from .output_writers import OutputWriter, find_writer
 
 FILE_MAGIC = b"PICLESCF"
 FILE_VERSION = 1
@@ -38,8 +39,21 @@ class IterationInterval:
     def __call__(self, iteration: int) -> bool:
         return iteration > 0 and iteration % self.interval == 0
 
+    @classmethod
+    def of(cls, schedule):
+        """a schedule given as an IterationInterval or as an int (every that many iterations)"""
+        return schedule if isinstance(schedule, cls) else cls(int(schedule))
+
     def next_after(self, iteration: int) -> int:
         return (iteration // self.interval + 1) * self.interval
+
+    def records_of(self, it0: int, n_steps: int) -> int:
+        """records a run of n_steps from iteration it0 writes: the first iteration's and one per scheduled iteration after it"""
+        return 1 + (it0 + n_steps) // self.interval - it0 // self.interval
+
+    def first_step(self, it0: int) -> int:
+        """the library's step counter (steps since a set was created at iteration it0) of the first scheduled iteration"""
+        return self.interval - it0 % self.interval
 
 
 def checkpoint_path(dir, prefix: str, iteration: int, rank=None) -> Path:
@@ -121,15 +135,19 @@ def latest_checkpoint(dir, prefix: str = "checkpoint", rank=None, world=None):
     return per[int(rank)][max(common)] if common else None
 
 
-class Checkpointer:
+class Checkpointer(OutputWriter):
     """Checkpointer(model; schedule, dir, prefix) of Oceananigans: attach with `sim.output_writers["checkpointer"] = ...`.
     `schedule` is an IterationInterval or an int (every that many iterations).  `rank`: a slab model's rank (file per rank)."""
+
+    kind = "checkpointer"
+    needs = "checkpoint_begin"
+    refusal = "a Checkpointer needs a backend with checkpoint_begin / checkpoint_end (the HIP library)"
 
     def __init__(self, model=None, *, schedule=None, dir=".", prefix: str = "checkpoint", rank=None):
         if schedule is None:
             raise ValueError("Checkpointer needs a schedule (IterationInterval(N) or N)")
         self.model = model
-        self.schedule = schedule if isinstance(schedule, IterationInterval) else IterationInterval(int(schedule))
+        self.schedule = IterationInterval.of(schedule)
         self.dir = Path(dir)
         self.prefix = prefix
         self.rank = rank
@@ -146,7 +164,19 @@ class Checkpointer:
         backend.checkpoint_begin()
         self._inflight = (checkpoint_path(self.dir, self.prefix, iteration, self.rank), float(time), int(iteration))
 
-    def finish(self, backend):
+    def steps_allowed(self, backend, iteration: int) -> int:
+        return self.schedule.next_after(iteration) - iteration
+
+    def at_iteration(self, model, writers):
+        """the file of the previous snapshot, then — on a scheduled iteration — the next snapshot, and word of it to every writer"""
+        it = model.clock.iteration
+        self.finish(model.backend)
+        if self.schedule(it):
+            self.begin(model.backend, model.clock.time, it)
+            for w in writers:
+                w.checkpoint_begun(model.backend, self._inflight[0])
+
+    def finish(self, backend, iteration=None):
         if self._inflight is None:
             return None
         path, time, iteration = self._inflight
@@ -156,21 +186,16 @@ class Checkpointer:
         self.written.append(path)
         return path
 
+    after_chunk = finish                 # the snapshot taken before the chunk: its copy-out ran beside the chunk's kernels
+
     def latest(self, world=None):
         return latest_checkpoint(self.dir, self.prefix, self.rank, world)
-
-
-def find_checkpointer(sim):
-    for w in getattr(sim, "output_writers", {}).values():
-        if isinstance(w, Checkpointer):
-            return w
-    return None
 
 
 def resolve_pickup(sim, pickup):
     """pickup=True: the latest file of the simulation's Checkpointer; a path: that file"""
     if pickup is True:
-        ck = find_checkpointer(sim)
+        ck = find_writer(sim, Checkpointer)
         if ck is None:
             raise K.CheckpointError(0, "run(sim, pickup=True) needs a Checkpointer in sim.output_writers (or pass pickup=<path>)")
         path = ck.latest()

@@ -30,6 +30,8 @@ import numpy as np
 from . import _capi as K
 from .checkpointing import IterationInterval
 from .driver import SCALAR_NAMES, combine_partials, diag_field_mask
+from .output_writers import OutputWriter
+from .storing import H5File, choose_format
 
 
 def coarse_coordinate(x, c: int):
@@ -68,78 +70,57 @@ class NpyFieldStore:
 
 
 class H5FieldStore:
-    """the HDF5 form, through the ctypes binding of picles_amd/storing.py"""
+    """the HDF5 form, through the file layer of picles_amd/storing.py"""
 
     format = "hdf5"
 
     def __init__(self, path, name, time, x, y, var_names):
-        from . import storing as S
-        L = self.L = S.hdf5()
-        self.S = S
-        self.dir = Path(path)
-        self.dir.mkdir(parents=True, exist_ok=True)
-        self.path = self.dir / f"{name}.h5"
-        if self.path.exists():
-            self.path.unlink()
-        self.f32 = S._hid.in_dll(L, "H5T_NATIVE_FLOAT_g").value
+        h = self.h5 = H5File(path, name, "waves")
+        self.dir, self.path = h.dir, h.path
         nt, nx, ny, nf = self.shape = (len(time), len(x), len(y), len(var_names))
-        self.file = S._ok(L.H5Fcreate(str(self.path).encode(), S._H5F_ACC_TRUNC, 0, 0), f"H5Fcreate({self.path})")
-        self.group = S._ok(L.H5Gcreate2(self.file, b"waves", 0, 0, 0), "H5Gcreate2(waves)")
-        self.fspace = S._ok(L.H5Screate_simple(4, S._dims((nf, ny, nx, nt)), None), "H5Screate_simple")
-        self.data = S._ok(L.H5Dcreate2(self.group, b"data", self.f32, self.fspace, 0, 0, 0), "H5Dcreate2(data)")
-        self.mspace = S._ok(L.H5Screate_simple(4, S._dims((nf, ny, nx, 1)), None), "H5Screate_simple")
-        full = np.full((nf, ny, nx, nt), np.nan, dtype=np.float32)
-        S._ok(L.H5Dwrite(self.data, self.f32, 0, 0, 0, full.ctypes.data), "H5Dwrite(data)")
-        S._write_strings(L, self.group, "dims", ["time", "x", "y", "field"], attribute=True)
-        S._write_f64(L, self.group, "x", x)
-        S._write_f64(L, self.group, "y", y)
-        S._write_strings(L, self.group, "var_names", list(var_names))
-        S._write_strings(L, self.group, "scalar_names", list(SCALAR_NAMES))
+        self.data = h.sliced("data", (nf, ny, nx, nt), np.float32)
+        self.data.fill(np.nan)
+        h.strings("dims", ["time", "x", "y", "field"], attribute=True)
+        h.f64("x", x)
+        h.f64("y", y)
+        h.strings("var_names", list(var_names))
+        h.strings("scalar_names", list(SCALAR_NAMES))
         self.times = np.full(nt, np.nan)
         self.scalars = np.full((nt, len(SCALAR_NAMES)), np.nan)
 
     def write(self, i, fields, scalars, time):
-        L, S = self.L, self.S
-        nt, nx, ny, nf = self.shape
-        plane = np.ascontiguousarray(np.asarray(fields, dtype=np.float32).transpose(0, 2, 1))      # (field, y, x): a no-op for the planes as popped
-        S._ok(L.H5Sselect_hyperslab(self.fspace, S._H5S_SELECT_SET, S._dims((0, 0, 0, i)), None, S._dims((nf, ny, nx, 1)), None),
-              "H5Sselect_hyperslab")
-        S._ok(L.H5Dwrite(self.data, self.f32, self.mspace, self.fspace, 0, plane.ctypes.data), "H5Dwrite(data)")
+        # (field, y, x): a no-op for the planes as popped
+        self.data.write(i, np.ascontiguousarray(np.asarray(fields, dtype=np.float32).transpose(0, 2, 1)))
         self.scalars[i] = scalars
         self.times[i] = time
 
     def close(self):
-        if self.file is None:
+        if self.h5.file is None:
             return
-        L, S = self.L, self.S
-        S._write_f64(L, self.group, "time", self.times)
-        S._write_f64(L, self.group, "scalars", self.scalars)
-        L.H5Sclose(self.mspace); L.H5Sclose(self.fspace); L.H5Dclose(self.data); L.H5Gclose(self.group)
-        S._ok(L.H5Fclose(self.file), "H5Fclose")
-        self.file = None
+        self.h5.f64("time", self.times)
+        self.h5.f64("scalars", self.scalars)
+        self.h5.close()
 
 
 def make_field_store(path, name, time, x, y, var_names, format="auto"):
-    if format not in ("auto", "hdf5", "npy"):
-        raise ValueError(f"unknown field output format {format!r}")
-    if format != "npy":
-        try:
-            return H5FieldStore(path, name, time, x, y, var_names)
-        except OSError:
-            if format == "hdf5":
-                raise
-    return NpyFieldStore(path, name, time, x, y, var_names)
+    return choose_format(format, "field output", lambda: H5FieldStore(path, name, time, x, y, var_names),
+                         lambda: NpyFieldStore(path, name, time, x, y, var_names))
 
 
-class FieldWriter:
+class FieldWriter(OutputWriter):
     """FieldWriter(model, schedule=IterationInterval(N) | N, path=..., coarsen=(cx, cy), fields=("hs", "tp", "cg_x", "cg_y"))"""
+
+    kind = "fields"
+    needs = "diag_init"
+    refusal = "a FieldWriter needs a backend with diag_init / diag_push / diag_pop (the HIP library)"
+    sized_for_run = True
 
     def __init__(self, model=None, *, schedule=None, path=".", name="fields", coarsen=(4, 4), fields=("hs", "tp", "cg_x", "cg_y"),
                  format="auto", slots=3):
         if schedule is None:
             raise ValueError("FieldWriter needs a schedule (IterationInterval(N) or N)")
         self.model = model
-        self.schedule = schedule if isinstance(schedule, IterationInterval) else IterationInterval(int(schedule))
+        self.schedule = IterationInterval.of(schedule)
         self.path, self.name, self.format = Path(path), name, format
         self.coarsen = (int(coarsen), int(coarsen)) if np.isscalar(coarsen) else (int(coarsen[0]), int(coarsen[1]))
         mask = diag_field_mask(fields)
@@ -150,11 +131,6 @@ class FieldWriter:
         self.iterations = []          # the iteration of every record pushed, in order
         self._initialised = None      # the backend whose ring was set up
 
-    def records_of(self, it0: int, n_steps: int) -> int:
-        """records a run of n_steps from iteration it0 writes: the first iteration's and one per scheduled iteration after it"""
-        N = self.schedule.interval
-        return 1 + (it0 + n_steps) // N - it0 // N
-
     def begin_run(self, model, n_steps: int):
         """set the ring up (once per backend), open the file for this run and push the record of the current iteration"""
         b = model.backend
@@ -163,12 +139,19 @@ class FieldWriter:
             self._initialised = b
         g = model.grid
         self.Nx, self.Ny = int(g.stats.Nx), int(g.stats.Ny)
-        nt = self.records_of(model.clock.iteration, n_steps)
+        nt = self.schedule.records_of(model.clock.iteration, n_steps)
         x, y = coarse_coordinate(g.data.x[:, 0], self.coarsen[0]), coarse_coordinate(g.data.y[0, :], self.coarsen[1])
         self.store = make_field_store(self.path, self.name, np.zeros(nt), x, y, self.fields, format=self.format)
         self.written = 0
         self.iterations = []
         self.push(b, model.clock.iteration)
+
+    def steps_allowed(self, backend, iteration: int) -> int:
+        return self.schedule.next_after(iteration) - iteration
+
+    def at_iteration(self, model, writers):
+        if self.schedule(model.clock.iteration):
+            self.push(model.backend, model.clock.iteration)
 
     def push(self, backend, iteration: int):
         """snapshot now; a full ring first gives up its oldest snapshot (waited for and written)"""
@@ -187,20 +170,13 @@ class FieldWriter:
             if count is not None:
                 count -= 1
 
-    def finish(self, backend):
+    def finish(self, backend, iteration=None):
         """end of the run: write what is pending and close the file"""
         if self.store is None:
             return
         self.drain(backend)
         self.store.close()
         self.last_store, self.store = self.store, None
-
-
-def find_field_writer(sim):
-    for w in getattr(sim, "output_writers", {}).values():
-        if isinstance(w, FieldWriter):
-            return w
-    return None
 
 
 def read_field_output(path, name="fields"):

@@ -1,0 +1,67 @@
+"""OutputWriter: what run() (picles_amd/simulations.py) asks of the entries of `sim.output_writers` — Checkpointer, FieldWriter,
+StationWriter, StatisticsWriter.  run() names none of them: it calls the hooks below, each phase in the order PHASE_ORDER gives
+(by kind of writer, not by the dict's order), and a writer overrides the hooks it has work for.  DESIGN.md §16 says why the
+orders are what they are."""
+from __future__ import annotations
+
+NO_LIMIT = 2**62          # steps_allowed of a writer that ends no chunk
+
+# the visiting order of each phase, by `kind`; a kind a phase does not list has no work in it (and is visited last)
+PHASE_ORDER = {
+    "begin_run": ("fields", "stations", "statistics"),
+    "after_chunk": ("stations", "checkpointer"),
+    "at_iteration": ("statistics", "checkpointer", "fields"),
+    "finish": ("checkpointer", "fields", "stations", "statistics"),
+}
+
+
+class OutputWriter:
+    kind = None             # the name PHASE_ORDER knows the class by
+    needs = None            # a backend method the writer cannot do without ...
+    refusal = None          # ... and what run() says of a backend that lacks it
+    sized_for_run = False   # begin_run sizes a file for the run: a finite stop_time is needed
+
+    def load_pickup(self, checkpoint_file):
+        """run(sim, pickup=...) has loaded `checkpoint_file`: take what this writer stored next to it"""
+
+    def begin_run(self, model, n_steps: int):
+        """`n_steps` steps from the model's iteration are about to run"""
+
+    def steps_allowed(self, backend, iteration: int) -> int:
+        """how many steps the next chunk of picles_run_steps may take from `iteration`"""
+        return NO_LIMIT
+
+    def after_chunk(self, backend):
+        """the chunked path only: a chunk has been enqueued (the clock does not show it yet)"""
+
+    def before_step(self, backend):
+        """the per-step loop only: a time_step is about to be taken"""
+
+    def at_iteration(self, model, writers):
+        """the clock has reached an iteration, on either path; `writers` are all the writers run() drives"""
+
+    def checkpoint_begun(self, backend, checkpoint_file):
+        """the Checkpointer has taken the snapshot that will become `checkpoint_file`"""
+
+    def finish(self, backend, iteration=None):
+        """the run is over"""
+
+
+def writers_of(sim):
+    """the writers run() drives: the first of each kind in sim.output_writers (what is no OutputWriter is left alone)"""
+    found = {}
+    for w in getattr(sim, "output_writers", {}).values():
+        if isinstance(w, OutputWriter):
+            found.setdefault(w.kind, w)
+    return list(found.values())
+
+
+def find_writer(sim, kind):
+    """the writer of that kind (a class attribute `kind`, or the class itself), or None"""
+    kind = getattr(kind, "kind", kind)
+    return next((w for w in writers_of(sim) if w.kind == kind), None)
+
+
+def in_phase(writers, phase):
+    order = PHASE_ORDER[phase]
+    return sorted(writers, key=lambda w: order.index(w.kind) if w.kind in order else len(order))

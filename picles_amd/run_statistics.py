@@ -58,8 +58,10 @@ from pathlib import Path
 import numpy as np
 
 from .checkpointing import IterationInterval
+from .output_writers import NO_LIMIT, OutputWriter
+from .station_output import FOUR_PI, peak_period          # noqa: F401  (FOUR_PI: the docstring's constant, importable from here)
+from .storing import H5File, check_format, choose_format, read_h5_group
 
-FOUR_PI = 12.566370614359172
 GROUPS = ("peak", "mean", "exceed")
 GROUP_BITS = {"peak": 1, "mean": 2, "exceed": 4}
 PEAK_VARS = ("hs_max", "tp_at_max", "dir_at_max", "t_of_max")
@@ -84,10 +86,7 @@ def check_arguments(fields, thresholds, schedule, window):
             raise ValueError("StatisticsWriter: thresholds must be finite, positive and strictly ascending")
     elif thr:
         raise ValueError("StatisticsWriter: thresholds given without 'exceed'")
-    schedule = schedule if isinstance(schedule, IterationInterval) else IterationInterval(int(schedule))
-    if window is not None:
-        window = window if isinstance(window, IterationInterval) else IterationInterval(int(window))
-    return fields, thr, schedule, window
+    return fields, thr, IterationInterval.of(schedule), (None if window is None else IterationInterval.of(window))
 
 
 def var_names(fields, n_thresholds):
@@ -108,7 +107,7 @@ def derive(acc, g, r_g):
             out["hs_max"] = 4.0 * np.sqrt(e)
             M2 = mx * mx + my * my
             cbar = e / (2.0 * np.sqrt(M2))
-            out["tp_at_max"] = (FOUR_PI * np.maximum(cbar / r_g, 0.1)) / g
+            out["tp_at_max"] = peak_period(cbar, g, r_g)
             out["dir_at_max"] = np.arctan2(my, mx)
             out["t_of_max"] = acc["t_peak"].copy()
         if "sum_e" in acc:
@@ -131,34 +130,27 @@ def _write_files(path, name, format, data, meta):
     """data (var, y, x, window); meta: names, x, y, thresholds, t_start, t_end, iteration, n_samples -> the path written"""
     d = Path(path)
     d.mkdir(parents=True, exist_ok=True)
-    if format not in ("auto", "hdf5", "npy"):
-        raise ValueError(f"unknown statistics output format {format!r}")
-    if format != "npy":
-        try:
-            from . import storing as S
-            L = S.hdf5()
-            p = d / f"{name}.h5"
-            if p.exists():
-                p.unlink()
-            f = S._ok(L.H5Fcreate(str(p).encode(), S._H5F_ACC_TRUNC, 0, 0), f"H5Fcreate({p})")
-            grp = S._ok(L.H5Gcreate2(f, b"stats", 0, 0, 0), "H5Gcreate2(stats)")
-            S._write_f64(L, grp, "data", data)
-            S._write_strings(L, grp, "dims", ["var", "y", "x", "window"], attribute=True)
-            S._write_strings(L, grp, "names", list(meta["names"]))
-            for k in ("x", "y", "thresholds", "t_start", "t_end", "iteration", "n_samples"):
-                S._write_f64(L, grp, k, np.asarray(meta[k], dtype=np.float64))
-            L.H5Gclose(grp)
-            S._ok(L.H5Fclose(f), "H5Fclose")
-            return p, "hdf5"
-        except OSError:
-            if format == "hdf5":
-                raise
-    np.save(d / f"{name}.stats.data.npy", np.ascontiguousarray(data))
-    js = {"group": "stats", "dims": ["var", "y", "x", "window"], "names": list(meta["names"])}
-    for k in ("x", "y", "thresholds", "t_start", "t_end", "iteration", "n_samples"):
-        js[k] = [float(v) for v in np.asarray(meta[k], dtype=np.float64)]
-    (d / f"{name}.json").write_text(json.dumps(js))
-    return d / f"{name}.json", "npy"
+    keys = ("x", "y", "thresholds", "t_start", "t_end", "iteration", "n_samples")
+
+    def hdf5_form():
+        h = H5File(d, name, "stats")
+        h.f64("data", data)
+        h.strings("dims", ["var", "y", "x", "window"], attribute=True)
+        h.strings("names", list(meta["names"]))
+        for k in keys:
+            h.f64(k, np.asarray(meta[k], dtype=np.float64))
+        h.close()
+        return h.path, "hdf5"
+
+    def npy_form():
+        np.save(d / f"{name}.stats.data.npy", np.ascontiguousarray(data))
+        js = {"group": "stats", "dims": ["var", "y", "x", "window"], "names": list(meta["names"])}
+        for k in keys:
+            js[k] = [float(v) for v in np.asarray(meta[k], dtype=np.float64)]
+        (d / f"{name}.json").write_text(json.dumps(js))
+        return d / f"{name}.json", "npy"
+
+    return choose_format(format, "statistics output", hdf5_form, npy_form)
 
 
 def read_statistics(path, name="statistics"):
@@ -175,8 +167,7 @@ def read_statistics(path, name="statistics"):
         for k in keys:
             out[k] = np.asarray(out[k], dtype=np.float64)
         return out
-    from . import storing as S
-    out = S.read_h5_group(d / f"{name}.h5", "stats", f64=("data",) + keys, strings=("names",), attrs=("dims",))
+    out = read_h5_group(d / f"{name}.h5", "stats", f64=("data",) + keys, strings=("names",), attrs=("dims",))
     out["names"] = list(out["names"])
     return out
 
@@ -186,14 +177,18 @@ def variable(out, var):
     return out["data"][list(out["names"]).index(var)]
 
 
-class StatisticsWriter:
+class StatisticsWriter(OutputWriter):
     """StatisticsWriter(model, fields=("peak", "mean", "exceed"), thresholds=(...), schedule=1, window=None | N, path=...,
     name="statistics")"""
 
+    kind = "statistics"
+    needs = "stat_init"
+    refusal = "a StatisticsWriter needs a backend with stat_init / stat_get / stat_reset (the HIP library)"
+    sized_for_run = True
+
     def __init__(self, model=None, *, fields=GROUPS, thresholds=(), schedule=1, window=None, path=".", name="statistics", format="auto"):
         self.fields, self.thresholds, self.schedule, self.window = check_arguments(fields, thresholds, schedule, window)
-        if format not in ("auto", "hdf5", "npy"):
-            raise ValueError(f"unknown statistics output format {format!r}")
+        check_format(format, "statistics output")
         self.model = model
         self.dir, self.name, self.format = Path(path), name, format
         self.path = self.dir
@@ -204,14 +199,9 @@ class StatisticsWriter:
         self._restore = None          # accumulators a pickup handed over, uploaded by begin_run
 
     # ---- the cadence ----
-    def first_step(self, it0: int) -> int:
-        """the library's step counter (steps since the set was created at iteration it0) of the first scheduled iteration"""
-        N = self.schedule.interval
-        return N - it0 % N
-
-    def next_after(self, iteration: int) -> int:
-        """the iteration the open window ends at (where run() must end a chunk); a run without windows never ends one"""
-        return self.window.next_after(iteration) if self.window is not None else 2**62
+    def steps_allowed(self, backend, iteration: int) -> int:
+        """the distance to the iteration the open window ends at (where run() must end a chunk); a run without windows never ends one"""
+        return self.window.next_after(iteration) - iteration if self.window is not None else NO_LIMIT
 
     # ---- the run ----
     def begin_run(self, model, n_steps: int):
@@ -220,7 +210,7 @@ class StatisticsWriter:
         if self._set_on is b:
             b.stat_free()
         it0 = int(model.clock.iteration)
-        b.stat_init(self.fields, self.thresholds, every=self.schedule.interval, first=self.first_step(it0))
+        b.stat_init(self.fields, self.thresholds, every=self.schedule.interval, first=self.schedule.first_step(it0))
         self._set_on = b
         P = model.ODEsettings.Parameters
         self._g, self._r_g = P.get("g", 9.81), P["r_g"]
@@ -241,10 +231,10 @@ class StatisticsWriter:
         self.records.append((planes, acc["t_first"], acc["t_last"], int(iteration), acc["n_samples"]))
         backend.stat_reset()
 
-    def after_steps(self, backend, iteration: int):
-        """called by run() when `iteration` has been reached"""
-        if self.window is not None and self.window(iteration):
-            self.end_window(backend, iteration)
+    def at_iteration(self, model, writers):
+        """a window that ends here: get, write, reset"""
+        if self.window is not None and self.window(model.clock.iteration):
+            self.end_window(model.backend, model.clock.iteration)
 
     def finish(self, backend, iteration: int):
         if self._set_on is None:
@@ -262,7 +252,7 @@ class StatisticsWriter:
         self._set_on = None
 
     # ---- pickup ----
-    def save_sidecar(self, backend, checkpoint_file):
+    def checkpoint_begun(self, backend, checkpoint_file):
         """the raw accumulators of the open window next to a checkpoint file (atomic, like the file itself)"""
         acc = backend.stat_get()
         path = Path(str(checkpoint_file) + SIDECAR_SUFFIX)
@@ -274,7 +264,7 @@ class StatisticsWriter:
         os.replace(tmp, path)
         return path
 
-    def load_sidecar(self, checkpoint_file):
+    def load_pickup(self, checkpoint_file):
         """remember the accumulators stored next to `checkpoint_file` for begin_run; a missing or foreign side-car starts a fresh
         window with a warning"""
         path = Path(str(checkpoint_file) + SIDECAR_SUFFIX)
@@ -296,10 +286,3 @@ class StatisticsWriter:
             acc[k] = float(acc[k])
         self._restore = acc
         return True
-
-
-def find_statistics_writer(sim):
-    for w in getattr(sim, "output_writers", {}).values():
-        if isinstance(w, StatisticsWriter):
-            return w
-    return None

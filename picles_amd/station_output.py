@@ -61,9 +61,17 @@ from pathlib import Path
 import numpy as np
 
 from .checkpointing import IterationInterval
+from .output_writers import OutputWriter
+from .storing import H5File, choose_format, read_h5_group
 
 VAR_NAMES = ("e", "m_x", "m_y", "hs", "tp", "cg_x", "cg_y", "dir")
 FOUR_PI = 12.566370614359172
+
+
+def peak_period(cbar, g, r_g):
+    """the header's tp of a mean phase-speed scale cbar = E / (2 sqrt(M2)), with its slow-wave floor; these IEEE operations in
+    this order, for station records (below) and the run statistics' tp_at_max (picles_amd/run_statistics.py) alike"""
+    return (FOUR_PI * np.maximum(cbar / r_g, 0.1)) / g
 
 
 def _axis(x, x0, xN, N, kind, what):
@@ -128,7 +136,7 @@ def station_records(values, index, weights, g, r_g):
         cgx = (MX * E) / (2.0 * M2)
         cgy = (MY * E) / (2.0 * M2)
         cbar = E / (2.0 * np.sqrt(M2))
-        tp = (FOUR_PI * np.maximum(cbar / r_g, 0.1)) / g
+        tp = peak_period(cbar, g, r_g)
         dr = np.arctan2(MY, MX)
     out = np.stack([E, MX, MY, hs, tp, cgx, cgy, dr], axis=-1)
     out[~valid] = np.nan
@@ -159,22 +167,14 @@ class NpyStationStore:
 
 
 class H5StationStore:
-    """the HDF5 form, through the ctypes binding of picles_amd/storing.py; the records are kept in memory (stations x 8 doubles
+    """the HDF5 form, through the file layer of picles_amd/storing.py; the records are kept in memory (stations x 8 doubles
     per record) and written when the file is closed"""
 
     format = "hdf5"
 
     def __init__(self, path, name, nt, x, y, names):
-        from . import storing as S
-        self.S, self.L = S, S.hdf5()
-        self.dir = Path(path)
-        self.dir.mkdir(parents=True, exist_ok=True)
-        self.path = self.dir / f"{name}.h5"
-        if self.path.exists():
-            self.path.unlink()
-        L = self.L
-        self.file = S._ok(L.H5Fcreate(str(self.path).encode(), S._H5F_ACC_TRUNC, 0, 0), f"H5Fcreate({self.path})")
-        self.group = S._ok(L.H5Gcreate2(self.file, b"stations", 0, 0, 0), "H5Gcreate2(stations)")
+        h = self.h5 = H5File(path, name, "stations")
+        self.dir, self.path = h.dir, h.path
         self.x, self.y, self.names = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64), list(names)
         self.data = np.full((len(VAR_NAMES), len(names), nt), np.nan)
         self.time = np.full(nt, np.nan)
@@ -186,48 +186,38 @@ class H5StationStore:
         self.iteration[i] = iteration
 
     def close(self):
-        if self.file is None:
+        h = self.h5
+        if h.file is None:
             return
-        S, L = self.S, self.L
-        nv, ns, nt = self.data.shape
-        f64 = L.NATIVE_DOUBLE
-        space = S._ok(L.H5Screate_simple(3, S._dims((nv, ns, nt)), None), "H5Screate_simple")
-        d = S._ok(L.H5Dcreate2(self.group, b"data", f64, space, 0, 0, 0), "H5Dcreate2(data)")
-        buf = np.ascontiguousarray(self.data)
-        S._ok(L.H5Dwrite(d, f64, 0, 0, 0, buf.ctypes.data), "H5Dwrite(data)")
-        L.H5Dclose(d); L.H5Sclose(space)
-        S._write_strings(L, self.group, "dims", ["time", "station", "var"], attribute=True)
-        S._write_strings(L, self.group, "var_names", list(VAR_NAMES))
-        S._write_strings(L, self.group, "names", self.names)
+        h.f64("data", self.data)
+        h.strings("dims", ["time", "station", "var"], attribute=True)
+        h.strings("var_names", list(VAR_NAMES))
+        h.strings("names", self.names)
         for k, a in (("x", self.x), ("y", self.y), ("time", self.time), ("iteration", self.iteration)):
-            S._write_f64(L, self.group, k, a)
-        L.H5Gclose(self.group)
-        S._ok(L.H5Fclose(self.file), "H5Fclose")
-        self.file = None
+            h.f64(k, a)
+        h.close()
 
 
 def make_station_store(path, name, nt, x, y, names, format="auto"):
-    if format not in ("auto", "hdf5", "npy"):
-        raise ValueError(f"unknown station output format {format!r}")
-    if format != "npy":
-        try:
-            return H5StationStore(path, name, nt, x, y, names)
-        except OSError:
-            if format == "hdf5":
-                raise
-    return NpyStationStore(path, name, nt, x, y, names)
+    return choose_format(format, "station output", lambda: H5StationStore(path, name, nt, x, y, names),
+                         lambda: NpyStationStore(path, name, nt, x, y, names))
 
 
-class StationWriter:
+class StationWriter(OutputWriter):
     """StationWriter(model, points=[(x, y), ...] | nodes=[(i, j), ...], names=None, schedule=1, path=..., name="stations",
     capacity=64)"""
+
+    kind = "stations"
+    needs = "probe_init"
+    refusal = "a StationWriter needs a backend with probe_init / probe_sample / probe_pop (the HIP library)"
+    sized_for_run = True
 
     def __init__(self, model=None, *, points=None, nodes=None, names=None, schedule=1, path=".", name="stations", capacity=64,
                  format="auto"):
         if (points is None) == (nodes is None):
             raise ValueError("StationWriter needs either points=[(x, y), ...] or nodes=[(i, j), ...]")
         self.model = model
-        self.schedule = schedule if isinstance(schedule, IterationInterval) else IterationInterval(int(schedule))
+        self.schedule = IterationInterval.of(schedule)
         self.path, self.name, self.format = Path(path), name, format
         self.capacity = int(capacity)
         if self.capacity < 1:
@@ -263,24 +253,29 @@ class StationWriter:
         self._grid = grid
 
     # ---- the cadence in iterations and in probe steps ----
-    def records_of(self, it0: int, n_steps: int) -> int:
-        N = self.schedule.interval
-        return 1 + (it0 + n_steps) // N - it0 // N
-
     def first_step(self, it0: int) -> int:
-        """the probe step counter (steps since the set was created at iteration it0) of the first scheduled iteration"""
-        N = self.schedule.interval
-        return N - it0 % N
+        return self.schedule.first_step(it0)
 
-    def steps_allowed(self, backend, iteration: int) -> int:
+    def allowance(self, backend, iteration: int) -> int:
         """how many steps may be enqueued from `iteration` without asking the ring for more than it holds: the samples of one
         chunk stay within half the ring (at least one), so that the samples of the chunk before can be popped while it runs.
-        0: pop first (make_room)"""
+        0: pop first"""
         N = self.schedule.interval
         allowance = min(self.capacity - backend.probe_pending, max(1, self.capacity // 2))
         if allowance <= 0:
             return 0
         return (iteration // N + allowance + 1) * N - 1 - iteration
+
+    def steps_allowed(self, backend, iteration: int) -> int:
+        """the ring's allowance, after making room where there is none; what is pending now are the samples of the chunks
+        before the next one: after_chunk pops them while that chunk runs"""
+        if self.allowance(backend, iteration) < 1:
+            self.drain(backend)
+        self._earlier = backend.probe_pending
+        return self.allowance(backend, iteration)
+
+    def after_chunk(self, backend):
+        self.drain(backend, self._earlier)
 
     def begin_run(self, model, n_steps: int):
         """(re)create the probe set with the cadence continued from the model's iteration — a picked-up run goes on where the
@@ -301,7 +296,7 @@ class StationWriter:
             x, y = [p[0] for p in self.points], [p[1] for p in self.points]
         else:
             x, y = [float("nan")] * ns, [float("nan")] * ns
-        self.store = make_station_store(self.path, self.name, self.records_of(it0, n_steps), x, y, self.names, format=self.format)
+        self.store = make_station_store(self.path, self.name, self.schedule.records_of(it0, n_steps), x, y, self.names, format=self.format)
         self.written = 0
         self.iterations = []
         b.probe_sample()
@@ -320,24 +315,17 @@ class StationWriter:
             self.iterations.append(it)
             self.written += 1
 
-    def make_room(self, backend):
-        """the per-step loop: the library samples inside time_step; a full ring gives up its older half first"""
+    def before_step(self, backend):
+        """the per-step loop: the library samples inside time_step and refuses a full ring; it gives up its older half first"""
         if backend.probe_pending >= self.capacity:
             self.drain(backend, max(1, self.capacity // 2))
 
-    def finish(self, backend):
+    def finish(self, backend, iteration=None):
         if self.store is None:
             return
         self.drain(backend)
         self.store.close()
         self.last_store, self.store = self.store, None
-
-
-def find_station_writer(sim):
-    for w in getattr(sim, "output_writers", {}).values():
-        if isinstance(w, StationWriter):
-            return w
-    return None
 
 
 def read_station_output(path, name="stations"):
@@ -349,8 +337,7 @@ def read_station_output(path, name="stations"):
         for k in ("x", "y", "time", "iteration"):
             out[k] = np.asarray(out[k], dtype=np.float64)
         return out
-    from . import storing as S
-    out = S.read_h5_group(d / f"{name}.h5", "stations", f64=("data", "x", "y", "time", "iteration"), strings=("var_names", "names"),
-                          attrs=("dims",))
+    out = read_h5_group(d / f"{name}.h5", "stations", f64=("data", "x", "y", "time", "iteration"), strings=("var_names", "names"),
+                        attrs=("dims",))
     out["data"] = out["data"].transpose(2, 1, 0)        # file (var, station, time) -> [time, station, var]
     return out

@@ -22,6 +22,7 @@ import ctypes as C
 import ctypes.util
 import json
 import os
+import warnings
 from pathlib import Path
 
 import numpy as np
@@ -97,6 +98,7 @@ def hdf5():
         raise OSError("H5open failed")
     L.H5Eset_auto2(0, None, None)          # errors come back as negative ids / return codes, checked below; no stderr stack dumps
     L.NATIVE_DOUBLE = _hid.in_dll(L, "H5T_NATIVE_DOUBLE_g").value
+    L.NATIVE_FLOAT = _hid.in_dll(L, "H5T_NATIVE_FLOAT_g").value
     L.C_S1 = _hid.in_dll(L, "H5T_C_S1_g").value
     _lib = L
     return L
@@ -119,28 +121,110 @@ def _vlen_str_type(L):
     return t
 
 
-def _write_f64(L, loc, name, a):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    sp = _ok(L.H5Screate_simple(a.ndim, _dims(a.shape), None), "H5Screate_simple")
-    d = _ok(L.H5Dcreate2(loc, name.encode(), L.NATIVE_DOUBLE, sp, 0, 0, 0), f"H5Dcreate2({name})")
-    _ok(L.H5Dwrite(d, L.NATIVE_DOUBLE, 0, 0, 0, a.ctypes.data), f"H5Dwrite({name})")
-    L.H5Dclose(d); L.H5Sclose(sp)
+class H5Sliced:
+    """a dataset written one slice of its last axis at a time (H5File.sliced): one hyperslab write per slice"""
+
+    def __init__(self, L, loc, name, dims, dtype):
+        self.L, self.name, self.dims, self.dtype = L, name, tuple(dims), np.dtype(dtype)
+        self.type = L.NATIVE_DOUBLE if self.dtype == np.float64 else L.NATIVE_FLOAT
+        self.fspace = _ok(L.H5Screate_simple(len(dims), _dims(self.dims), None), "H5Screate_simple")
+        self.data = _ok(L.H5Dcreate2(loc, name.encode(), self.type, self.fspace, 0, 0, 0), f"H5Dcreate2({name})")
+        self.mspace = _ok(L.H5Screate_simple(len(dims), _dims(self.dims[:-1] + (1,)), None), "H5Screate_simple")
+
+    def write(self, i, plane):
+        """`plane`: a contiguous array of the dataset's element type, shaped like the dataset without its last axis"""
+        L, nd = self.L, len(self.dims)
+        _ok(L.H5Sselect_hyperslab(self.fspace, _H5S_SELECT_SET, _dims((0,) * (nd - 1) + (i,)), None, _dims(self.dims[:-1] + (1,)), None),
+            "H5Sselect_hyperslab")
+        _ok(L.H5Dwrite(self.data, self.type, self.mspace, self.fspace, 0, plane.ctypes.data), f"H5Dwrite({self.name})")
+
+    def fill(self, value):
+        full = np.full(self.dims, value, dtype=self.dtype)
+        _ok(self.L.H5Dwrite(self.data, self.type, 0, 0, 0, full.ctypes.data), f"H5Dwrite({self.name})")
+
+    def close(self):
+        self.L.H5Sclose(self.mspace); self.L.H5Sclose(self.fspace); self.L.H5Dclose(self.data)
 
 
-def _write_strings(L, loc, name, strings, attribute=False):
-    t = _vlen_str_type(L)
-    sp = _ok(L.H5Screate_simple(1, _dims((len(strings),)), None), "H5Screate_simple")
-    keep = [s.encode("utf-8") for s in strings]
-    buf = (C.c_char_p * len(keep))(*keep)
-    if attribute:
-        a = _ok(L.H5Acreate2(loc, name.encode(), t, sp, 0, 0), f"H5Acreate2({name})")
-        _ok(L.H5Awrite(a, t, buf), f"H5Awrite({name})")
-        L.H5Aclose(a)
-    else:
-        d = _ok(L.H5Dcreate2(loc, name.encode(), t, sp, 0, 0, 0), f"H5Dcreate2({name})")
-        _ok(L.H5Dwrite(d, t, 0, 0, 0, buf), f"H5Dwrite({name})")
-        L.H5Dclose(d)
-    L.H5Sclose(sp); L.H5Tclose(t)
+class H5File:
+    """`<dir>/<name>.h5` with one group, as every product here writes its HDF5 form: the directory is made, a file of that name
+    replaced (the reference's replace=true: rm(...; force=true)), the file and the group created.  Datasets and attributes go
+    into the group (or into `loc`, another group of the file: add_winds_forcing).  OSError where no libhdf5 loads or a call fails."""
+
+    def __init__(self, dir, name, group):
+        L = self.L = hdf5()
+        self.dir = Path(dir)
+        self.dir.mkdir(parents=True, exist_ok=True)
+        self.path = self.dir / f"{name}.h5"
+        if self.path.exists():
+            self.path.unlink()
+        self.file = _ok(L.H5Fcreate(str(self.path).encode(), _H5F_ACC_TRUNC, 0, 0), f"H5Fcreate({self.path})")
+        self.group = _ok(L.H5Gcreate2(self.file, group.encode(), 0, 0, 0), f"H5Gcreate2({group})")
+        self._sliced = []
+
+    def sliced(self, name, dims, dtype=np.float64):
+        """a float64 or float32 dataset of shape `dims`, to be written slice by slice of its last axis; closed with the file"""
+        self._sliced.append(H5Sliced(self.L, self.group, name, dims, dtype))
+        return self._sliced[-1]
+
+    def f64(self, name, a, loc=None):
+        L = self.L
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        sp = _ok(L.H5Screate_simple(a.ndim, _dims(a.shape), None), "H5Screate_simple")
+        d = _ok(L.H5Dcreate2(self.group if loc is None else loc, name.encode(), L.NATIVE_DOUBLE, sp, 0, 0, 0), f"H5Dcreate2({name})")
+        _ok(L.H5Dwrite(d, L.NATIVE_DOUBLE, 0, 0, 0, a.ctypes.data), f"H5Dwrite({name})")
+        L.H5Dclose(d); L.H5Sclose(sp)
+
+    def strings(self, name, strings, attribute=False, loc=None):
+        """a dataset, or an attribute of the group, of variable-length UTF-8 strings"""
+        L, loc = self.L, (self.group if loc is None else loc)
+        t = _vlen_str_type(L)
+        sp = _ok(L.H5Screate_simple(1, _dims((len(strings),)), None), "H5Screate_simple")
+        keep = [s.encode("utf-8") for s in strings]
+        buf = (C.c_char_p * len(keep))(*keep)
+        if attribute:
+            a = _ok(L.H5Acreate2(loc, name.encode(), t, sp, 0, 0), f"H5Acreate2({name})")
+            _ok(L.H5Awrite(a, t, buf), f"H5Awrite({name})")
+            L.H5Aclose(a)
+        else:
+            d = _ok(L.H5Dcreate2(loc, name.encode(), t, sp, 0, 0, 0), f"H5Dcreate2({name})")
+            _ok(L.H5Dwrite(d, t, 0, 0, 0, buf), f"H5Dwrite({name})")
+            L.H5Dclose(d)
+        L.H5Sclose(sp); L.H5Tclose(t)
+
+    def flush(self):
+        if self.file is not None:
+            self.L.H5Fflush(self.file, 1)
+
+    def close(self):
+        """idempotent; an H5Fclose that fails is an OSError (the file may not be whole)"""
+        if self.file is None:
+            return
+        for d in self._sliced:
+            d.close()
+        self.L.H5Gclose(self.group)
+        _ok(self.L.H5Fclose(self.file), "H5Fclose")
+        self.file = None
+
+
+def check_format(format, product):
+    if format not in ("auto", "hdf5", "npy"):
+        raise ValueError(f"unknown {product} format {format!r}")
+
+
+def choose_format(format, product, hdf5_form, npy_form, warn=None):
+    """the one "auto" | "hdf5" | "npy" choice: `hdf5_form()` unless "npy" is asked for; its OSError (no libhdf5, a failing call)
+    is re-raised for "hdf5" and answered with `npy_form()` — after the warning `warn`, if given — for "auto" """
+    check_format(format, product)
+    if format != "npy":
+        try:
+            return hdf5_form()
+        except OSError:
+            if format == "hdf5":
+                raise
+            if warn:
+                warnings.warn(warn)
+    return npy_form()
 
 
 class StateStore:
@@ -149,33 +233,23 @@ class StateStore:
     format = "hdf5"
 
     def __init__(self, path, time, x, y, name="state", state=VAR_NAMES):
-        L = self.L = hdf5()
-        self.dir = Path(path)
-        self.dir.mkdir(parents=True, exist_ok=True)
-        self.path = self.dir / f"{name}.h5"
-        if self.path.exists():
-            self.path.unlink()                                   # replace=true: rm(...; force=true)
+        h = self.h5 = H5File(path, name, "waves")
+        self.dir, self.path = h.dir, h.path
         self.shape = (len(time), len(x), len(y), len(state))     # the reference's (Julia-order) shape
-        self.file = _ok(L.H5Fcreate(str(self.path).encode(), _H5F_ACC_TRUNC, 0, 0), f"H5Fcreate({self.path})")
-        self.group = _ok(L.H5Gcreate2(self.file, b"waves", 0, 0, 0), "H5Gcreate2(waves)")
         nt, nx, ny, ns = self.shape
-        self._fdims = (ns, ny, nx, nt)
-        self.fspace = _ok(L.H5Screate_simple(4, _dims(self._fdims), None), "H5Screate_simple")
-        self.data = _ok(L.H5Dcreate2(self.group, b"data", L.NATIVE_DOUBLE, self.fspace, 0, 0, 0), "H5Dcreate2(data)")
-        self.mspace = _ok(L.H5Screate_simple(4, _dims((ns, ny, nx, 1)), None), "H5Screate_simple")
-        _write_strings(L, self.group, "dims", ["time", "x", "y", "state"], attribute=True)
-        _write_f64(L, self.group, "time", time)
-        _write_f64(L, self.group, "x", x)
-        _write_f64(L, self.group, "y", y)
-        _write_strings(L, self.group, "state", list(state))
-        _write_strings(L, self.group, "var_names", VAR_NAMES)
+        self.data = h.sliced("data", (ns, ny, nx, nt))
+        h.strings("dims", ["time", "x", "y", "state"], attribute=True)
+        h.f64("time", time)
+        h.f64("x", x)
+        h.f64("y", y)
+        h.strings("state", list(state))
+        h.strings("var_names", VAR_NAMES)
         self.iteration = 0
 
     def write(self, state, i=None):
         """`store["data"][ii, :, :, :] = State`: one time plane.  `state` is the (Nx, Ny, 3) view the host API hands out
         (Fortran order underneath, i.e. already (3, Ny, Nx) in the file's row-major terms)"""
-        L = self.L
-        if self.file is None:
+        if self.h5.file is None:
             raise ValueError("StateStore is closed")
         ii = self.iteration if i is None else int(i)
         nt, nx, ny, ns = self.shape
@@ -184,18 +258,13 @@ class StateStore:
         a = np.asarray(state, dtype=np.float64)
         if a.shape != (nx, ny, ns):
             raise ValueError(f"state of shape {a.shape}, store expects {(nx, ny, ns)}")
-        plane = np.ascontiguousarray(a.transpose(2, 1, 0))          # a no-op for the column-major State
-        _ok(L.H5Sselect_hyperslab(self.fspace, _H5S_SELECT_SET, _dims((0, 0, 0, ii)), None, _dims((ns, ny, nx, 1)), None),
-            "H5Sselect_hyperslab")
-        _ok(L.H5Dwrite(self.data, L.NATIVE_DOUBLE, self.mspace, self.fspace, 0, plane.ctypes.data), "H5Dwrite(data)")
+        self.data.write(ii, np.ascontiguousarray(a.transpose(2, 1, 0)))          # a no-op for the column-major State
         if i is None:
             self.iteration += 1
 
     def reset(self, value=0.0):
         """reset_state_store!(sim; value) (storing.jl:127-131)"""
-        L = self.L
-        full = np.full(self._fdims, float(value))
-        _ok(L.H5Dwrite(self.data, L.NATIVE_DOUBLE, 0, 0, 0, full.ctypes.data), "H5Dwrite(data)")
+        self.data.fill(float(value))
         self.iteration = 0
 
     def add_winds_forcing(self, forcing, coords):
@@ -203,30 +272,24 @@ class StateStore:
         dataset per forcing field (`forcing` = {"u": array[time, x, y], "v": ...}; None entries are skipped), the attribute
         `dims` and the coordinate vectors (`coords` = {"time": ..., "x": ..., "y": ...}, in the fields' index order).  The
         reference creates the field datasets with `create_dataset` and never writes them (:155-157); here they are filled."""
-        L = self.L
-        g = _ok(L.H5Gcreate2(self.file, b"forcing", 0, 0, 0), "H5Gcreate2(forcing)")
+        h, L = self.h5, self.h5.L
+        g = _ok(L.H5Gcreate2(h.file, b"forcing", 0, 0, 0), "H5Gcreate2(forcing)")
         for name, f in forcing.items():
             if f is None:
                 continue
             f = np.asarray(f, dtype=np.float64)
-            _write_f64(L, g, str(name), np.ascontiguousarray(f.transpose(*range(f.ndim - 1, -1, -1))))
-        _write_strings(L, g, "dims", [str(k) for k in coords], attribute=True)
+            h.f64(str(name), np.ascontiguousarray(f.transpose(*range(f.ndim - 1, -1, -1))), loc=g)
+        h.strings("dims", [str(k) for k in coords], attribute=True, loc=g)
         for k, v in coords.items():
-            _write_f64(L, g, str(k), np.asarray(v, dtype=np.float64))
+            h.f64(str(k), np.asarray(v, dtype=np.float64), loc=g)
         L.H5Gclose(g)
 
     def flush(self):
-        if self.file is not None:
-            self.L.H5Fflush(self.file, 1)
+        self.h5.flush()
 
     def close(self):
         """close_store!(store) (storing.jl:172-180)"""
-        if self.file is None:
-            return
-        L = self.L
-        L.H5Sclose(self.mspace); L.H5Sclose(self.fspace); L.H5Dclose(self.data); L.H5Gclose(self.group)
-        _ok(L.H5Fclose(self.file), "H5Fclose")
-        self.file = None
+        self.h5.close()
 
     def __del__(self):
         try:
@@ -238,46 +301,8 @@ class StateStore:
 def read_state_store(path):
     """read a StateStore file back (tests, post-processing): dict with `data` in the reference's index order
     [time, x, y, state], the coordinate vectors, `var_names`, `state` and the group's `dims` attribute"""
-    L = hdf5()
-    f = _ok(L.H5Fopen(str(path).encode(), _H5F_ACC_RDONLY, 0), f"H5Fopen({path})")
-    g = _ok(L.H5Gopen2(f, b"waves", 0), "H5Gopen2(waves)")
-    out = {}
-
-    def shape_of(space):
-        nd = L.H5Sget_simple_extent_ndims(space)
-        d = (C.c_uint64 * nd)()
-        L.H5Sget_simple_extent_dims(space, d, None)
-        return tuple(int(v) for v in d)
-
-    def f64(name):
-        d = _ok(L.H5Dopen2(g, name.encode(), 0), f"H5Dopen2({name})")
-        sp = L.H5Dget_space(d)
-        a = np.empty(shape_of(sp), dtype=np.float64)
-        _ok(L.H5Dread(d, L.NATIVE_DOUBLE, 0, 0, 0, a.ctypes.data), f"H5Dread({name})")
-        L.H5Sclose(sp); L.H5Dclose(d)
-        return a
-
-    def strings(name, attribute=False):
-        t = _vlen_str_type(L)
-        h = _ok((L.H5Aopen(g, name.encode(), 0) if attribute else L.H5Dopen2(g, name.encode(), 0)), f"open({name})")
-        sp = L.H5Aget_space(h) if attribute else L.H5Dget_space(h)
-        n = shape_of(sp)[0]
-        buf = (C.c_char_p * n)()
-        _ok(L.H5Aread(h, t, buf) if attribute else L.H5Dread(h, t, 0, 0, 0, buf), f"read({name})")
-        res = [b.decode("utf-8") for b in buf]
-        L.H5Dvlen_reclaim(t, sp, 0, buf)
-        L.H5Sclose(sp)
-        (L.H5Aclose if attribute else L.H5Dclose)(h)
-        L.H5Tclose(t)
-        return res
-
-    out["data"] = f64("data").transpose(3, 2, 1, 0)       # file (state, y, x, time) -> [time, x, y, state]
-    for k in ("time", "x", "y"):
-        out[k] = f64(k)
-    out["var_names"] = strings("var_names")
-    out["state"] = strings("state")
-    out["dims"] = strings("dims", attribute=True)
-    L.H5Gclose(g); L.H5Fclose(f)
+    out = read_h5_group(path, "waves", f64=("data", "time", "x", "y"), strings=("var_names", "state"), attrs=("dims",))
+    out["data"] = out["data"].transpose(3, 2, 1, 0)       # file (state, y, x, time) -> [time, x, y, state]
     return out
 
 
@@ -352,15 +377,6 @@ class NpyStateStore:
 
 def make_state_store(path, time, x, y, name="state", format="auto"):
     """format: "hdf5" (the reference's file; OSError without a libhdf5), "npy", or "auto" = hdf5 where a libhdf5 loads"""
-    if format not in ("auto", "hdf5", "npy"):
-        raise ValueError(f"unknown store format {format!r}")
-    if format == "npy":
-        return NpyStateStore(path, time, x, y, name=name)
-    try:
-        return StateStore(path, time, x, y, name=name)
-    except OSError:
-        if format == "hdf5":
-            raise
-        import warnings
-        warnings.warn("no libhdf5 found: the state store is written as .npy + .json (same layout); set PICLES_HDF5_LIB")
-        return NpyStateStore(path, time, x, y, name=name)
+    return choose_format(format, "store", lambda: StateStore(path, time, x, y, name=name),
+                         lambda: NpyStateStore(path, time, x, y, name=name),
+                         warn="no libhdf5 found: the state store is written as .npy + .json (same layout); set PICLES_HDF5_LIB")

@@ -363,3 +363,40 @@ def test_statistics_writer_end_to_end(tmp_path):
             assert a.tobytes() == b_.tobytes(), (k, name)
         hs_max = out["data"][list(out["names"]).index("hs_max"), :, :, k]
         assert np.isfinite(hs_max).mean() >= 0.3 and np.array_equal(np.isnan(hs_max), (acc["n_wet"] == 0).T)
+
+
+# ---- 7. all four writers at once: every product equals that of a run with that writer alone ---------------------------------------
+def test_four_writers_at_once_write_what_each_writes_alone(tmp_path):
+    """tests/test_run_call_sequence.py pins the ORDER of run()'s calls with several writers attached; this shows the library
+    agrees that the order gives the same products: bench06_box(n=48) (no multiple of the 64-node tile), 23 steps, the schedules
+    of that test; every .npy file and every checkpoint file, byte for byte, against four runs with one writer each"""
+    from picles_amd.checkpointing import Checkpointer
+    from picles_amd.field_output import FieldWriter
+    from picles_amd.run_statistics import StatisticsWriter
+    from picles_amd.simulations import run
+    from picles_amd.station_output import StationWriter
+    make = {"ck": lambda m, d: Checkpointer(m, schedule=7, dir=d / "ck"),
+            "fields": lambda m, d: FieldWriter(m, schedule=5, path=d / "fields", slots=2, format="npy"),
+            "stations": lambda m, d: StationWriter(m, nodes=[(1, 2), (3, 4)], schedule=1, path=d / "stations", capacity=3, format="npy"),
+            "statistics": lambda m, d: StatisticsWriter(m, thresholds=(0.25,), window=10, path=d / "statistics", format="npy")}
+
+    def products(kinds, d):
+        cfg = configs.bench06_box(n=48, winds=configs.smooth_winds(10.0, 10.0, 2000.0 * 48, 2000.0 * 48))
+        m = make_model(cfg, "hip")
+        sim = Simulation(m, Δt=cfg.Δt, stop_time=cfg.Δt * 22)
+        for k in kinds:
+            sim.output_writers[k] = make[k](m, d)
+        run(sim)
+        assert m.clock.iteration == 23
+        return {p.relative_to(d).as_posix(): p.read_bytes() for p in sorted(d.rglob("*")) if p.suffix in (".npy", ".picles")}
+
+    together = products(tuple(make), tmp_path / "together")
+    assert sorted(together) == ["ck/checkpoint_iteration14.picles", "ck/checkpoint_iteration21.picles", "ck/checkpoint_iteration7.picles",
+                                "fields/fields.waves.data.npy", "fields/fields.waves.scalars.npy", "stations/stations.stations.data.npy",
+                                "statistics/statistics.stats.data.npy"]
+    alone = {}
+    for k in make:
+        alone.update(products((k,), tmp_path / k))
+    assert sorted(alone) == sorted(together)
+    for name, data in together.items():
+        assert data == alone[name], f"{name}: with all four writers attached it differs from the run with this writer alone"
