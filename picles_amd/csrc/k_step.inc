@@ -89,7 +89,15 @@ __global__ void __launch_bounds__(256, (FAST && !AUTO) ? 4 : (FAST ? 3 : 2)) K_S
          * of dependent memory round trips: a third of a wave's life, measured with the phase clock): -1 %; at four waves per SIMD the
          * registers they occupy across the pull cost more than the overlap gains (+4 %): the explicit pairs load at the point of use */
         constexpr bool PREFETCH = AUTO;
+        /* the four-wave static flavours of the wave-per-row form ask for the same values here too, by loads that hold no register: u0,
+         * v0 and ln q_old go straight into LDS (kernels.h, stage_fetch_waverow) and are read from there behind the pull; the flags
+         * byte takes one register across it */
+        constexpr bool STAGE = WROW && STATIC && !AUTO;
         unsigned char pf_pre = 0;
+        if constexpr (STAGE) {
+            stage_fetch_waverow(Av, lane);
+            pf_pre = Av.pflags[tx];
+        }
         Wind w_pre = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         double qold_pre = 0.0, uP_pre = 0.0, vP_pre = 0.0;
         int asw_pre = 0;
@@ -120,7 +128,7 @@ __global__ void __launch_bounds__(256, (FAST && !AUTO) ? 4 : (FAST ? 3 : 2)) K_S
         /* (s0, s1, s2) is State[k] of the PREVIOUS step.  It is not stored: nobody can read State while a fused step is pending —
          * every observer goes through flush(), whose k_scatter writes the State of the latest step — so the store would be dead
          * (24 B per particle and step of HBM writes, measured: 85 -> 61 B written per particle). */
-        unsigned char pf = PREFETCH ? pf_pre : Av.pflags[tx];
+        unsigned char pf = (PREFETCH || STAGE) ? pf_pre : Av.pflags[tx];
         /* What is needed again only behind the RK loop — the particle index, its node, its flags — waits in LDS instead of in
          * registers: at 128 VGPRs the compiler otherwise spills exactly these to scratch (8 dwords, 36 B per lane and step of extra
          * HBM traffic, measured 135 -> 172 B/particle); two LDS accesses per value cost the same and move nothing. */
@@ -128,10 +136,12 @@ __global__ void __launch_bounds__(256, (FAST && !AUTO) ? 4 : (FAST ? 3 : 2)) K_S
          * only the flags wait) */
         __shared__ int stash_[WROW ? 1 : 5][256];
         if (pf & PF_STEPPED) {
-            Wind w = PREFETCH ? w_pre : load_wind(P, Av, tx);
+            /* (STAGE: load_wind's result under static winds, the two planes and ln q_old read from the wave's stage) */
+            if constexpr (STAGE) stage_wait_waverow();
+            Wind w = PREFETCH ? w_pre : (STAGE ? stage_wind_waverow(lane) : load_wind(P, Av, tx));
             if constexpr (WROW) w.xi = (unsigned int)t;
             Vec5 z = {0.0, 0.0, 0.0, 0.0, 0.0};
-            double qold = PREFETCH ? qold_pre : Av.qold[tx], dtn = -1.0;
+            double qold = PREFETCH ? qold_pre : (STAGE ? (*stage_of_wave())[STAGE_QOLD][lane] : Av.qold[tx]), dtn = -1.0;
             int br = remesh_regs_lazy(P, pf, s0, s1, s2, DT_prev, z, STATIC ? &Av.u0[tx] : (PREFETCH ? &uP_pre : &Av.uP[tx]),
                                       STATIC ? &Av.v0[tx] : (PREFETCH ? &vP_pre : &Av.vP[tx]));
             int on = (br <= 1);

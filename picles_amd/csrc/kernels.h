@@ -947,11 +947,92 @@ __device__ __forceinline__ Arrays arrays_at(const Arrays &A, long long t0)
     B.um = A.um ? A.um + t0 : nullptr; B.vm += t0;                                 /* (load_wind asks whether um is there) */
     return B;
 }
+/* The node stage of the four-wave static flavours (k_step.inc, STAGE).  A wave's u0, v0 and ln q_old (64 doubles each) are asked for
+ * when its index is known and wanted behind the pull; loaded into registers they would be held across the pull, which the 128-register
+ * build cannot afford, so they are loaded straight into LDS (global_load_lds_dwordx4: no destination register): lanes 0-31 fetch two
+ * doubles per plane each, the hardware writes lane l's 16 bytes at the wave's base + 16 l, i.e. the plane's row in order.  A wave reads
+ * only what it fetched itself: it waits for its own loads (stage_wait_waverow) and needs no barrier.  16-byte loads want 16-byte-aligned
+ * rows: t0 is a multiple of 64, so the planes' bases decide (stage_aligned, asked by the host before it picks the kernel). */
+#define STAGE_U0 0
+#define STAGE_V0 1
+#define STAGE_QOLD 2
+typedef double StagePlanes[3][64];
+__device__ __forceinline__ StagePlanes *stage_of_wave()
+{
+    __shared__ __attribute__((aligned(16))) double stage_[4][3][64];
+    unsigned int tid = threadIdx.x;          /* (the wave number through an opaque copy, formed where it is used: waverow_of) */
+    __asm__ volatile("" : "+v"(tid));
+    return &stage_[__builtin_amdgcn_readfirstlane((int)(tid >> 6))];
+}
+__device__ __forceinline__ void stage_fetch_waverow(const Arrays &Av, unsigned int lane)
+{
+    typedef __attribute__((address_space(3))) void *lds_ptr;
+    StagePlanes &st = *stage_of_wave();
+    if (lane < 32u) {
+        __builtin_amdgcn_global_load_lds(Av.u0 + 2u * lane, (lds_ptr)&st[STAGE_U0][0], 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(Av.v0 + 2u * lane, (lds_ptr)&st[STAGE_V0][0], 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(Av.qold + 2u * lane, (lds_ptr)&st[STAGE_QOLD][0], 16, 0, 0);
+    }
+}
+/* every vector-memory operation of the wave has landed, the LDS writes of stage_fetch_waverow among them (s_waitcnt vmcnt(0), the other
+ * counters left alone; the compiler is not relied on to see that the read that follows depends on those loads) */
+__device__ __forceinline__ void stage_wait_waverow()
+{
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+    __asm__ volatile("" ::: "memory");
+}
+__device__ __forceinline__ Wind stage_wind_waverow(unsigned int lane)
+{
+    const StagePlanes &st = *stage_of_wave();
+    Wind w;
+    w.u0 = st[STAGE_U0][lane]; w.v0 = st[STAGE_V0][lane];
+    w.du = 0.0; w.dv = 0.0; w.bu = 0.0; w.bv = 0.0;
+    w.xi = 0u;
+    return w;
+}
+static inline bool stage_aligned(const Arrays &A) { return (((uintptr_t)A.u0 | (uintptr_t)A.v0 | (uintptr_t)A.qold) & 15u) == 0; }
+
 __device__ __forceinline__ void rmap_clear_ahead_waverow(const Arrays &A, const WaveRow &w, unsigned int lane)
 {
     if (lane == 0u) {
         A.rmap[(size_t)((A.mr_idx >> 8) & 15) * (size_t)A.ntile + (size_t)(w.t0 >> 6)] = 0;
         class_map(A, (A.mr_idx >> 8) & 15)[(size_t)(w.t0 >> 6)] = 0;
+    }
+}
+
+/* the map rows of pull_reach_local_waverow at reach 1 and 2, written out: the loads of all 2 R + 1 rows of both maps are in flight before
+ * the first value is used — one round trip, where the counted loop (its trip count is not known to the compiler, each iteration waits
+ * for its own load) makes one per row.  The reach rows are asked for last and folded at once, so that their wait is the only one.
+ * Values and the order of the folds are the loop's.  One instance per reach, each a straight line: a common text with the outer rows
+ * behind a test of the reach has to give the rows it did not load a value, fifteen register moves per wave at reach 1.  (Vector loads
+ * through the uniform pointer on purpose: read through the constant address space these become scalar loads at no cost in spilled
+ * scalars, but the compiler then waits between them at reach 2 — scalar results return out of order, a copy of the first forces
+ * lgkmcnt(0) — and three trips stand where this form has one.) */
+template <int R>
+__device__ __forceinline__ void map_rows_waverow(const int *rm, const int *cm, long long tile, long long nbx, bool klass, int &m, int &diff, int &c0)
+{
+    constexpr int W = 2 * R + 1;
+    int c[W][3];
+    c0 = 0;
+    if (klass) {
+#pragma unroll
+        for (int k = 0; k < W; k++)
+#pragma unroll
+            for (int q = 0; q < 3; q++) c[k][q] = cm[tile + k * nbx + (q - 1)];
+    }
+    if (R >= 2) {
+        int r[W][3];
+#pragma unroll
+        for (int k = 0; k < W; k++)
+#pragma unroll
+            for (int q = 0; q < 3; q++) r[k][q] = rm[tile + k * nbx + (q - 1)];
+#pragma unroll
+        for (int k = 0; k < W; k++) m = max(m, max(r[k][0], max(r[k][1], r[k][2])));
+    }
+    if (klass) {
+        c0 = c[0][1];
+#pragma unroll
+        for (int k = 0; k < W; k++) diff |= (c[k][0] ^ c0) | (c[k][1] ^ c0) | (c[k][2] ^ c0);
     }
 }
 
@@ -974,10 +1055,15 @@ __device__ __forceinline__ int pull_reach_local_waverow(const GridP &G, const Ar
         const long long nbx = G.Nx >> 6;
         long long tile = ((long long)(jl - Rg) * G.Nx + w.i0) >> 6;
         int m = 0, diff = 0;
-        const int c0 = klass ? cm[tile] : 0;
-        for (int dj = -Rg; dj <= Rg; dj++, tile += nbx) {
-            if (Rg >= 2) m = max(m, max(rm[tile - 1], max(rm[tile], rm[tile + 1])));
-            if (klass) diff |= (cm[tile - 1] ^ c0) | (cm[tile] ^ c0) | (cm[tile + 1] ^ c0);
+        int c0;
+        if (Rg == 1) map_rows_waverow<1>(rm, cm, tile, nbx, klass, m, diff, c0);
+        else if (Rg == 2) map_rows_waverow<2>(rm, cm, tile, nbx, klass, m, diff, c0);
+        else {
+            c0 = klass ? cm[tile] : 0;
+            for (int dj = -Rg; dj <= Rg; dj++, tile += nbx) {
+                m = max(m, max(rm[tile - 1], max(rm[tile], rm[tile + 1])));
+                if (klass) diff |= (cm[tile - 1] ^ c0) | (cm[tile] ^ c0) | (cm[tile + 1] ^ c0);
+            }
         }
         if (diff == 0 && c0 > 0) {
             /* (a code whose four feeding candidates lie outside the window the tests above vouch for is not followed: no address is

@@ -1525,7 +1525,11 @@ static int launch_step_rows(picles_ctx *c, int which, hipStream_t s)
         A.ord = nullptr;            /* (this launch neither reads nor files an order) */
         if (c->G.single_slab || which != PICLES_ROWS_EDGE) c->ord_valid = false;
     }
-    const bool waverow = (c->waverow_mode == 2 || (c->waverow_mode == 1 && waverow_measured(P))) && step_rows_waverow(c, which);
+    /* (the four-wave static flavours of k_step_waverow fetch u0, v0 and ln q_old sixteen bytes at a time: kernels.h, stage_aligned;
+     * planes that are not so aligned take k_step, same bits) */
+    const bool staged = P.wind_static != 0 && !(fast && P.solver == 2);
+    const bool waverow = (c->waverow_mode == 2 || (c->waverow_mode == 1 && waverow_measured(P))) && step_rows_waverow(c, which) &&
+                         (!staged || stage_aligned(A));
     if (waverow && c->pull_class) c->cmap_hot = 4;       /* its entries live in buffer mr_w until the step after next but one clears them */
     else if (!waverow && c->cmap_hot > 0 && (rc = class_map_clear_rows(c, s, r0, n0, r1, n1))) return rc;
     timing_begin(c, s, 0);
