@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 9
+#define PICLES_ABI_VERSION 10
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -418,6 +418,52 @@ int32_t picles_stat_get(picles_ctx *ctx, int32_t group_mask, void *planes, int64
 int32_t picles_stat_set(picles_ctx *ctx, int32_t group_mask, const void *planes, int64_t n_samples, double t_first, double t_last);
 int32_t picles_stat_reset(picles_ctx *ctx);
 int32_t picles_stat_free(picles_ctx *ctx);
+
+/* ---- open-boundary forcing: prescribed sea state at the rim (swell from a parent model, a storm outside the box, a buoy
+ * spectrum at the mouth of a basin).  No counterpart in the reference: its `boundary_defaults` is a constant and its rim nodes are
+ * as dead as this library's are without a set. ----
+ * THE NODES.  On a model without periodic_boundary the grid-boundary nodes (mask class 3) carry no particle: energy that reaches
+ * them is dropped and nothing enters.  A forcing set names n of them, ij = the i plane then the j plane (global, 0-based), each
+ * once.  At every such node and every model step a particle is BORN from the prescribed (e, m_x, m_y) at the step's start time t
+ * (the model clock before the tick, the time the remesh uses), advanced over the step with the model's solver under the node's
+ * wind, and scattered with all other particles; it is reborn the next step, so a forced node carries nothing from step to step.
+ * THE VALUE.  Levels are 3 planes of n doubles (e, then m_x, then m_y, node k of the list at [k]).  One level (v1 == NULL): v = v0.
+ * Two levels at t0 < t1: per component, each operation one IEEE operation,
+ *     s = (t - t0) / (t1 - t0);    v = v0 + s * (v1 - v0)
+ * THE BIRTH.  If e, m_x, m_y are finite, e >= minimal_state[0] and m_x² + m_y² >= minimal_state[1] (NodeToParticle!'s test of a
+ * node value): lne = log e, c̄ = m e / (2 |m|²), x = y = 0, with the step-size memory of a freshly seeded particle — every step,
+ * so the result does not depend on how the model got here.  Otherwise no particle is born at that node this step (on = 0, an
+ * empty scatter record); nothing is re-seeded from the wind there.  The guards of the advance (NaN / Inf re-seed, energy cap,
+ * maxiters, reach cap) treat and count a forced particle like any other; picles_get_particles shows it at its node.
+ * WHERE IT RUNS.  One small kernel behind the launch that writes a step's records, on its stream, in picles_time_step,
+ * picles_run_steps and picles_advance alike: fused steps stay fused, and probes, statistics, snapshots and checkpoints taken
+ * behind a step see its forced particles.  The sum order of the scatter is the plain column-major one over all records (a forced
+ * record is on the ocean list: there is no second list).
+ * THE WINDOW.  With two levels every step must START inside [t0, t1] (an end is met within 1e-9 of t1 - t0, the rule of
+ * picles_lattice_knots).  picles_run_steps checks all n start times before it enqueues anything; picles_time_step, picles_advance
+ * and picles_begin_fused_step check theirs.  A refused call has changed nothing: set the next pair and call again.
+ *
+ *   init:       refuses (context unchanged, picles_last_error set) n < 1, a node outside the grid, a node that is not mask class 3,
+ *               a node given twice, a model with periodic_boundary (its rim is stepped), a tripolar grid, a slab context, slab
+ *               mode or a native ring, a second init without picles_bforce_free.  The set has no levels yet: steps are refused
+ *               until picles_bforce_set_levels
+ *   set_levels: uploads one or two levels in stream order behind the steps already enqueued (they keep the levels they were
+ *               enqueued under; a pending fused step stays pending); the caller's arrays are free on return.  Refuses: no set,
+ *               v0 NULL, two levels without finite t0 < t1
+ *   info:       n, levels held (0, 1 or 2), t0, t1 (any pointer may be NULL; -1 without a set; no device work)
+ *   free:       completes a pending step, empties the forced nodes' scatter records, switches their particles off (on = 0,
+ *               status = 0: what a rim node shows without a set) and drops the set; picles_destroy drops it too
+ * SLABS ARE OUT OF SCOPE: the edge rows' records are exchanged before a kernel behind the launch could run.  With a set,
+ * picles_set_slab_mode, picles_slab_comm_init / _run_steps / _exchange and picles_begin_step fail (-5) and change nothing;
+ * picles_bforce_init fails likewise on a slab.  A picles_advance_rows / picles_step_rows of less than all rows fails (-5) and
+ * launches nothing; a step that picles_begin_fused_step had opened on a whole-grid context stays open, and picles_step_rows of
+ * all rows followed by picles_end_fused_step completes it.
+ * The set is no part of the checkpoint blob or its fingerprint (a forced particle carries nothing across a step boundary);
+ * picles_checkpoint_load leaves it as it is, and the host sets the levels that bracket the restored clock. */
+int32_t picles_bforce_init(picles_ctx *ctx, int32_t n, const int32_t *ij);
+int32_t picles_bforce_set_levels(picles_ctx *ctx, double t0, const double *v0, double t1, const double *v1);
+int32_t picles_bforce_info(const picles_ctx *ctx, int32_t *n, int32_t *levels, double *t0, double *t1);
+int32_t picles_bforce_free(picles_ctx *ctx);
 
 /* particles (own rows; z is 5 planes: lne, c̄x, c̄y, x, y). Any pointer may be NULL.
  * The state vector of a switched-off particle (on == 0) is dead storage: its content is unspecified. */

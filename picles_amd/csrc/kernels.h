@@ -5,6 +5,7 @@
  *   picles_hip.hip      k_seed, k_scatter, k_remesh, k_push_tiles, the cell list, k_wind_sample + the host side / C ABI
  *   k_step_explicit.hip  the fused step, DP5 and Tsit5 flavours          k_step_auto.hip   ... AutoTsit5(Rosenbrock23())
  *   k_advance.hip        the stand-alone advance
+ *   k_bforce.hip         open-boundary forcing: the particles of the forced rim nodes
  * (split so that the flavours compile in parallel: `make -j`).
  */
 #ifndef PICLES_KERNELS_H
@@ -1276,5 +1277,18 @@ static inline bool waverow_flavour(bool fast, bool metric) { return fast && !met
 void launch_k_step_explicit(const StepLaunch &L, bool fast, int solver, bool wind_static, bool metric);
 void launch_k_step_auto(const StepLaunch &L, bool wind_static, bool metric);
 void launch_k_advance(const StepLaunch &L, bool fast, int solver, bool wind_static, bool metric);
+
+/* open-boundary forcing (k_bforce.hip): the forced nodes' local indices i + Nx jl, the two levels of the prescribed (e, m_x, m_y) —
+ * 3 planes of n doubles each; v1 == nullptr: constant — and s = (t - t0) / (t1 - t0) of the step's start time, formed on the host */
+struct BForceP {
+    int n;
+    const int *nodes;
+    const double *v0, *v1;
+    double s;
+};
+/* behind the launch that writes the step's records, same stream (L.grid, L.block and the row ranges are not read).  A weak reference:
+ * a build that links the host side without this unit (the host-only sanitizer harness links the four older ones) still links, and
+ * picles_bforce_init refuses there — a missing kernel is an error, never a detour */
+__attribute__((weak)) void launch_k_bforce(const StepLaunch &L, const BForceP &B, int solver, bool metric);
 
 #endif /* PICLES_KERNELS_H */

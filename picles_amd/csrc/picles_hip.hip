@@ -2,7 +2,7 @@
  * picles_hip.hip — the C ABI of include/picles_hip.h (host side) and the HIP kernels (gfx950 / CDNA4) that are not
  * flavoured: k_seed, k_scatter, k_remesh, k_push_tiles, the cell list, k_wind_sample.  The flavoured kernel families live in
  * their own translation units so that they compile in parallel — k_step_explicit.hip, k_step_auto.hip (template in
- * k_step.inc), k_advance.hip — and kernels.h holds the device code all of them share.
+ * k_step.inc), k_advance.hip, k_bforce.hip — and kernels.h holds the device code all of them share.
  *
  * One context = one GPU = one y-slab of the 2D Cartesian mesh.  Particles are born at and
  * return to their node every model step (mapping_2D.jl:279-356), so particle k IS node k:
@@ -32,6 +32,8 @@
  *   k_push_tiles     PUSH scatter: LDS-staged grid tile + apron, ds_add_f64 inside the tile,
  *                    one global fp64 atomic per touched tile node. HBM/atomic bound.
  *   k_remesh         stand-alone NodeToParticle! (split API).
+ *   k_bforce         (k_bforce.hip) open-boundary forcing: behind the launch that writes a step's records, one lane per forced rim
+ *                    node bears a particle from the prescribed sea state, advances it and leaves its record.  Latency bound.
  *   k_ckpt           checkpoint payload: packs / verifies / unpacks the planes of a restart blob in one pass. HBM bound.
  *   k_diag           (k_diag.h) coarse wave diagnostics: float32 Hs / Tp / cg planes + one partial of sums and maxima per tile of
  *                    256 coarse cells, one pass over State. HBM bound.
@@ -565,6 +567,13 @@ struct picles_ctx {
     hipEvent_t stat_ev = nullptr;
     hipStream_t stat_stream = nullptr;             /* the stream stat_ev was recorded on */
     bool stat_ev_live = false;
+    /* open-boundary forcing (picles_bforce_*): the forced nodes' local indices, and one device block of 6 planes of bf_n doubles —
+     * level 0 (e, m_x, m_y), then level 1.  bf_levels: 0 none set yet, 1 constant, 2 a pair over [bf_t0, bf_t1] */
+    int bf_n = 0;
+    int *bf_nodes = nullptr;
+    double *bf_lv = nullptr;
+    int bf_levels = 0;
+    double bf_t0 = 0.0, bf_t1 = 0.0;
     /* gridded winds */
     bool wind_grid_on = false;
     WindGrid wg{};
@@ -700,6 +709,8 @@ static void probe_release(picles_ctx *c);
 /* run statistics (defined behind the station probes) */
 static int stat_update(picles_ctx *c, hipStream_t s);
 static void stat_release(picles_ctx *c);
+/* open-boundary forcing (defined behind the run statistics) */
+static void bforce_release(picles_ctx *c);
 
 /* a model step has completed: the clock and the step counts the sampling schedules are counted in */
 static void step_completed(picles_ctx *c)
@@ -933,6 +944,7 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     probe_release(c);
     if (c->stat_on) hipDeviceSynchronize();     /* updates issued on caller streams read and write the planes about to go */
     stat_release(c);
+    bforce_release(c);
     if (c->ck_dev) hipFree(c->ck_dev);
     if (c->ck_host) hipHostFree(c->ck_host);
     if (c->ck_ready) hipEventDestroy(c->ck_ready);
@@ -1374,9 +1386,8 @@ PX_EXPORT int32_t picles_tick(picles_ctx *c, double dt)
     return 0;
 }
 
-PX_EXPORT int32_t picles_begin_step(picles_ctx *c, double dt, int32_t flags)
+static int begin_step(picles_ctx *c, double dt, int32_t flags)
 {
-    if (!c) return -1;
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     { int rc = flush(c); if (rc) return rc; }
     if (c->wind_grid_on) {  /* (first: a window the lattice cannot carry is refused before the step has changed anything) */
@@ -1393,6 +1404,17 @@ PX_EXPORT int32_t picles_begin_step(picles_ctx *c, double dt, int32_t flags)
     c->mr_w = (c->mr_w + 1) % 5;
     if (c->cmap_hot > 0) c->cmap_hot--;
     return 0;
+}
+
+/* the split phases are the slab drivers' interface: they bring the edge rows' records to the neighbours before a kernel behind the
+ * launch could add the forced nodes' (include/picles_hip.h, "open-boundary forcing") */
+static const char *const BFORCE_NO_SLABS = ": the context has a boundary forcing set, which the split phases and slabs do not carry "
+                                           "(picles_time_step / picles_run_steps / picles_advance do; or picles_bforce_free first)";
+PX_EXPORT int32_t picles_begin_step(picles_ctx *c, double dt, int32_t flags)
+{
+    if (!c) return -1;
+    if (c->bf_n) return fail(c, -5, std::string("picles_begin_step") + BFORCE_NO_SLABS);
+    return begin_step(c, dt, flags);
 }
 
 /* the specialised variant of the step kernels: every physics switch on, n = 2, p = 3/4, no dead band (all reference scripts).
@@ -1432,6 +1454,51 @@ static int step_prologue(picles_ctx *c, hipStream_t s)
     return 0;
 }
 
+/* ---- open-boundary forcing: the checks the step entry points make, and the launch (the contract: include/picles_hip.h; the
+ * kernel: k_bforce.hip; the set's own entry points: behind the run statistics) ---- */
+/* do the start times of the next n_steps steps of length dt lie inside the level pair's window?  Asked before anything is enqueued;
+ * a time closer to an end of the window than 1e-9 of its length is that end (the rule of picles_lattice_knots) */
+static int bforce_window(picles_ctx *c, double dt, long long n_steps, const char *who)
+{
+    if (!c->bf_n || n_steps <= 0) return 0;
+    if (!c->bf_levels) return fail(c, -2, std::string(who) + ": the boundary forcing set has no levels yet: picles_bforce_set_levels first");
+    if (c->bf_levels == 1) return 0;
+    const double slack = 1e-9 * (c->bf_t1 - c->bf_t0);
+    double t = c->clock;
+    for (long long k = 0; k < n_steps; k++, t += dt)
+        if (!(t >= c->bf_t0 - slack && t <= c->bf_t1 + slack)) {
+            char b[384];
+            snprintf(b, sizeof b, "%s: step %lld of this call starts at t = %.17g, outside the window [%.17g, %.17g] of the boundary forcing levels: "
+                                  "call picles_bforce_set_levels with the pair that brackets that time first, or take fewer steps per call",
+                     who, k + 1, t, c->bf_t0, c->bf_t1);
+            return fail(c, -2, b);
+        }
+    return 0;
+}
+
+/* the forced nodes' particles of the step in flight, behind the launch that wrote its records for the whole grid, on its stream:
+ * the same record buffer, the same generation of the reach counters and maps (A: the Arrays that launch was given) */
+static int bforce_launch(picles_ctx *c, hipStream_t s, const Arrays &A)
+{
+    BForceP B;
+    B.n = c->bf_n;
+    B.nodes = c->bf_nodes;
+    B.v0 = c->bf_lv;
+    B.v1 = c->bf_levels == 2 ? c->bf_lv + (size_t)3 * c->bf_n : nullptr;
+    B.s = c->bf_levels == 2 ? (c->clock - c->bf_t0) / (c->bf_t1 - c->bf_t0) : 0.0;
+    StepLaunch L = {dim3(1), dim3(256), s, &c->P, &c->G, &A, 0.0, 0.0, c->clock, c->step_dt, 0, 0, 0, 0};
+    launch_k_bforce(L, B, c->P.solver, c->A.pc != nullptr);      /* k_bforce.hip */
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+/* a launch over some of the rows is a slab's: refused with a set (nothing has been launched) */
+static int bforce_rows(picles_ctx *c, int which, const char *who)
+{
+    if (c->bf_n && (which != PICLES_ROWS_ALL || !c->G.single_slab)) return fail(c, -5, std::string(who) + BFORCE_NO_SLABS);
+    if (c->bf_n && !c->bf_levels) return fail(c, -2, std::string(who) + ": the boundary forcing set has no levels yet: picles_bforce_set_levels first");
+    return 0;
+}
+
 PX_EXPORT int32_t picles_advance_rows(picles_ctx *c, int32_t which, void *stream)
 {
     if (!c) return -1;
@@ -1443,20 +1510,22 @@ PX_EXPORT int32_t picles_advance_rows(picles_ctx *c, int32_t which, void *stream
     if (rc) return rc;
     long long nt = (long long)(n0 + n1) * c->G.Nx;
     if (nt == 0) return 0;
+    if ((rc = bforce_rows(c, which, "picles_advance_rows"))) return rc;
     if ((rc = step_prologue(c, s))) return rc;
     c->ord_valid = false;        /* the stand-alone advance files no dispatch order */
     if (c->cmap_hot > 0 && (rc = class_map_clear_rows(c, s, r0, n0, r1, n1))) return rc;
+    Arrays A = arrays_for(c, c->cur, c->cur);
     timing_begin(c, s, 0);
     {
         const KParams &P = c->P;
         bool fast = physics_fast(P);
         if (!P.wind_static && P.wind_nk > 1) fast = false;     /* a polyline window: the general flavours carry it (same bits: the oracle's one arithmetic) */
-        Arrays A = arrays_for(c, c->cur, c->cur);
         StepLaunch L = {dim3(nblocks(nt, 256)), dim3(256), s, &c->P, &c->G, &A, 0.0, 0.0, c->clock, c->step_dt, r0, n0, r1, n1};
         launch_k_advance(L, fast, P.solver, P.wind_static != 0, c->A.pc != nullptr);      /* k_advance.hip */
     }
     timing_end(c, s);
     HIPCHK(c, hipGetLastError());
+    if (c->bf_n && (rc = bforce_launch(c, s, A))) return rc;
     if (which == PICLES_ROWS_EDGE && s != c->stream) {
         HIPCHK(c, hipEventRecord(c->ev_edge, s));
         c->edge_pending = true;
@@ -1504,6 +1573,7 @@ static int launch_step_rows(picles_ctx *c, int which, hipStream_t s)
     if (rc) return rc;
     long long nt = (long long)(n0 + n1) * c->G.Nx;
     if (nt == 0) return 0;
+    if ((rc = bforce_rows(c, which, "picles_step_rows"))) return rc;
     if ((rc = step_prologue(c, s))) return rc;
     const KParams &P = c->P;
     Arrays A = arrays_for(c, c->cur ^ 1, c->cur);
@@ -1540,6 +1610,7 @@ static int launch_step_rows(picles_ctx *c, int which, hipStream_t s)
     }
     timing_end(c, s);
     HIPCHK(c, hipGetLastError());
+    if (c->bf_n && (rc = bforce_launch(c, s, A))) return rc;
     return 0;
 }
 
@@ -1551,6 +1622,7 @@ PX_EXPORT int32_t picles_begin_fused_step(picles_ctx *c, double dt)
 {
     if (!c) return -1;
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
+    { int rc = bforce_window(c, dt, 1, "picles_begin_fused_step"); if (rc) return rc; }
     if (!step_fusable(c, PICLES_STEP_ZERO_FIRST, dt)) return 1;
     /* PICLES_WAVEROW=require: every launch of the step — the whole grid, or a slab's edge and interior rows — must take k_step_waverow;
      * refused here, before the step has changed anything */
@@ -1680,7 +1752,7 @@ static int time_step_phases(picles_ctx *c, double dt, int32_t flags)
         if ((rc0 = picles_step_rows(c, PICLES_ROWS_ALL, nullptr))) return rc0;
         return picles_end_fused_step(c);
     }
-    int rc = picles_begin_step(c, dt, flags);
+    int rc = begin_step(c, dt, flags);
     if (rc) return rc;
     rc = picles_advance_rows(c, PICLES_ROWS_ALL, nullptr);
     if (rc) return rc;
@@ -1693,6 +1765,7 @@ PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
     if (!c->G.single_slab) return fail(c, -5, "picles_time_step needs the whole grid; slabs use begin_step/advance_rows/scatter_remesh");
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     { int rc = probe_room(c, 1, "picles_time_step"); if (rc) return rc; }      /* refused before anything has changed */
+    { int rc = bforce_window(c, dt, 1, "picles_time_step"); if (rc) return rc; }
     int rc = time_step_phases(c, dt, flags);
     if (rc) return rc;
     /* the sample of this step: directly behind its launch on the context stream.  The next step's launch reads the record buffer
@@ -1707,6 +1780,7 @@ PX_EXPORT int32_t picles_run_steps(picles_ctx *c, double dt, int32_t n_steps)
 {
     if (!c || n_steps < 0) return -1;
     if (c->G.single_slab && dt > 0.0) { int rc = probe_room(c, n_steps, "picles_run_steps"); if (rc) return rc; }   /* up front, not half-way */
+    if (c->G.single_slab && dt > 0.0) { int rc = bforce_window(c, dt, n_steps, "picles_run_steps"); if (rc) return rc; }   /* every start time, before anything is enqueued */
     const bool region = c->timing && c->timing_mode == 2 && n_steps > 0;
     if (region) {      /* one event pair around the whole call, on the stream the launches go to */
         HIPCHK(c, hipSetDevice(c->device));
@@ -1728,8 +1802,8 @@ PX_EXPORT int32_t picles_advance(picles_ctx *c, double dt, int32_t flags)
 {
     if (!c) return -1;
     if (!c->G.single_slab) return fail(c, -5, "picles_advance needs the whole grid");
-    int rc = picles_begin_step(c, dt, flags & ~(PICLES_STEP_MOVIE));
-    if (rc) return rc;
+    int rc = (dt > 0.0) ? bforce_window(c, dt, 1, "picles_advance") : 0;
+    if (rc || (rc = begin_step(c, dt, flags & ~(PICLES_STEP_MOVIE)))) return rc;
     rc = picles_advance_rows(c, PICLES_ROWS_ALL, nullptr);
     if (rc) return rc;
     return launch_scatter(c, c->stream, false);
@@ -2407,6 +2481,115 @@ PX_EXPORT int32_t picles_stat_free(picles_ctx *c)
     return 0;
 }
 
+/* ---- open-boundary forcing (the contract: include/picles_hip.h; the kernel: k_bforce.hip; the launch: bforce_launch above) ---- */
+/* the forced nodes' records, emptied in both buffers of the pair when the set goes: no step kernel writes the record of a node it
+ * does not step, so a record left behind would be scattered again by every later step.  Their particle slots go back to what a rim
+ * node's is without a set (off, no status): picles_get_particles and later checkpoints show no particle that no longer exists */
+__global__ void __launch_bounds__(256) k_bforce_clear(GridP G, double *rec_a, double *rec_b, unsigned char *on, int *status, int n, const int *nodes)
+{
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (k >= n) return;
+    const int t = nodes[k], i = t % G.Nx, jl = t / G.Nx;
+    const size_t at = (size_t)(jl + G.R) * 6 * G.Nx + (size_t)5 * G.Nx + i;
+    rec_a[at] = 0.0;
+    rec_b[at] = 0.0;
+    on[t] = 0;
+    status[t] = 0;
+}
+
+static void bforce_release(picles_ctx *c)
+{
+    if (c->bf_nodes) hipFree(c->bf_nodes);
+    if (c->bf_lv) hipFree(c->bf_lv);
+    c->bf_nodes = nullptr;
+    c->bf_lv = nullptr;
+    c->bf_n = 0;
+    c->bf_levels = 0;
+    c->bf_t0 = c->bf_t1 = 0.0;
+}
+
+PX_EXPORT int32_t picles_bforce_init(picles_ctx *c, int32_t n, const int32_t *ij)
+{
+    if (!c) return -1;
+    if (c->bf_n) return fail(c, -2, "picles_bforce_init: a boundary forcing set exists (picles_bforce_free first)");
+    if (!launch_k_bforce) return fail(c, -5, "picles_bforce_init: this build of the library was linked without k_bforce");
+    if (n < 1 || !ij) return fail(c, -2, "picles_bforce_init: n must be >= 1 and the node list given");
+    const GridP &G = c->G;
+    if (!G.single_slab || c->ring)
+        return fail(c, -5, "picles_bforce_init: slabs and the native ring do not carry a boundary forcing (a whole-grid context, not in slab mode, is needed)");
+    if (G.tripolar) return fail(c, -5, "picles_bforce_init: not supported on a tripolar grid");
+    if (c->md.periodic_boundary)
+        return fail(c, -5, "picles_bforce_init: a model with periodic_boundary steps its grid-boundary nodes itself: there is no open rim to force");
+    std::vector<int> loc((size_t)n);
+    std::vector<unsigned char> seen((size_t)c->A.n, 0);
+    for (int k = 0; k < n; k++) {
+        const int i = ij[k], j = ij[(size_t)n + k];
+        const std::string node = "picles_bforce_init: node " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) + ")";
+        if (i < 0 || i >= G.Nx || j < 0 || j >= G.Ny) return fail(c, -2, node + " lies outside [0, Nx) x [0, Ny)");
+        const long long t = (long long)j * G.Nx + i;
+        if (c->h_mask[t] != 3)
+            return fail(c, -2, node + " is no grid-boundary node (mask class " + std::to_string((int)c->h_mask[t]) + ", 3 is needed): only the open rim can be forced");
+        if (seen[t]) return fail(c, -2, node + " is given twice");
+        seen[t] = 1;
+        loc[k] = (int)t;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) bforce_release(c); } } undo{c, true};
+    HIPCHK(c, hipMalloc(&c->bf_nodes, (size_t)n * sizeof(int)));
+    HIPCHK(c, hipMalloc(&c->bf_lv, (size_t)6 * n * sizeof(double)));
+    HIPCHK(c, hipMemcpy(c->bf_nodes, loc.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));     /* blocking: loc dies here */
+    c->bf_n = n;
+    c->bf_levels = 0;
+    undo.armed = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_bforce_set_levels(picles_ctx *c, double t0, const double *v0, double t1, const double *v1)
+{
+    if (!c) return -1;
+    if (!c->bf_n) return fail(c, -2, "picles_bforce_init first");
+    if (!v0) return fail(c, -2, "picles_bforce_set_levels: level 0 must be given");
+    if (v1 && !(t1 > t0)) return fail(c, -2, "picles_bforce_set_levels: two levels need t1 > t0");
+    if (v1 && !(std::isfinite(t0) && std::isfinite(t1))) return fail(c, -2, "picles_bforce_set_levels: the level times must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    /* in stream order behind the launches that read the levels in place; a pending fused step stays pending */
+    if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());
+    const size_t b = (size_t)3 * c->bf_n * sizeof(double);
+    HIPCHK(c, hipMemcpyAsync(c->bf_lv, v0, b, hipMemcpyHostToDevice, c->stream));
+    if (v1) HIPCHK(c, hipMemcpyAsync((char *)c->bf_lv + b, v1, b, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      /* the caller's buffers are free when this returns */
+    c->bf_levels = v1 ? 2 : 1;
+    c->bf_t0 = t0;
+    c->bf_t1 = v1 ? t1 : t0;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_bforce_info(const picles_ctx *c, int32_t *n, int32_t *levels, double *t0, double *t1)
+{
+    if (!c || !c->bf_n) return -1;
+    if (n) *n = c->bf_n;
+    if (levels) *levels = c->bf_levels;
+    if (t0) *t0 = c->bf_t0;
+    if (t1) *t1 = c->bf_t1;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_bforce_free(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->bf_n) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flush(c); if (rc) return rc; }      /* a pending step's forced records are scattered before they are emptied */
+    HIPCHK(c, hipDeviceSynchronize());       /* launches in flight read the list and the levels about to go */
+    hipLaunchKernelGGL(k_bforce_clear, dim3(nblocks(c->bf_n, 256)), dim3(256), 0, c->stream, c->G, c->rec_buf[0], c->rec_buf[1], c->A.on, c->A.status,
+                       c->bf_n, (const int *)c->bf_nodes);
+    HIPCHK(c, hipGetLastError());
+    { int rc = class_map_zero(c); if (rc) return rc; }      /* records written by other means than the step kernels */
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    bforce_release(c);
+    return 0;
+}
+
 /* ---- halo blocks ---- */
 PX_EXPORT int32_t picles_halo_rows(const picles_ctx *c) { return c ? c->G.R : -1; }
 
@@ -2444,6 +2627,7 @@ PX_EXPORT int32_t picles_set_slab_mode(picles_ctx *c, int32_t on)
     GridP &G = c->G;
     if (!(G.j_begin == 0 && G.ny_loc == G.Ny)) return on ? 0 : fail(c, -2, "a partial slab cannot resolve the y wrap locally");
     if (c->pending || c->seeded) return fail(c, -2, "picles_set_slab_mode: call before picles_seed");
+    if (on && c->bf_n) return fail(c, -5, std::string("picles_set_slab_mode") + BFORCE_NO_SLABS);
     if (on) {
         if ((G.periodic_y && G.Ny <= 2 * G.R) || G.ny_loc < G.R)
             return fail(c, -2, "slab: periodic y axis not longer than 2*halo_rows, or fewer own rows than halo_rows");
@@ -2598,6 +2782,7 @@ PX_EXPORT int32_t picles_slab_comm_init(picles_ctx *c, const void *id128, int32_
     if (!c || !id128) return -1;
     if (world < 1 || rank < 0 || rank >= world) return fail(c, -2, "slab ring: need 0 <= rank < world");
     if (c->ring) return fail(c, -2, "slab ring already initialised");
+    if (c->bf_n) return fail(c, -5, std::string("picles_slab_comm_init") + BFORCE_NO_SLABS);
     if (c->G.single_slab && world > 1) return fail(c, -2, "slab ring of several ranks needs slab contexts (j_begin, j_end)");
     if (c->G.tripolar) return fail(c, -5, "slab ring: the tripolar fold is not wired into the native ring (use picles_amd.parallel)");
     HIPCHK(c, hipSetDevice(c->device));
@@ -2656,6 +2841,7 @@ PX_EXPORT int32_t picles_slab_exchange(picles_ctx *c)
     if (!c) return -1;
     SlabRing *R = c->ring;
     if (!R) return fail(c, -2, "picles_slab_comm_init first");
+    if (c->bf_n) return fail(c, -5, std::string("picles_slab_exchange") + BFORCE_NO_SLABS);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
     int rc = ring_exchange(c, R, R->sE);
@@ -2669,6 +2855,7 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
     if (!c || n_steps < 0) return -1;
     SlabRing *R = c->ring;
     if (!R) return fail(c, -2, "picles_slab_comm_init first");
+    if (c->bf_n) return fail(c, -5, std::string("picles_slab_run_steps") + BFORCE_NO_SLABS);
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     if (flags & PICLES_STEP_ATOMIC) return fail(c, -5, "PICLES_STEP_ATOMIC is single-slab only");
     { int rc = probe_room(c, n_steps, "picles_slab_run_steps"); if (rc) return rc; }      /* up front: nothing has changed yet */

@@ -558,6 +558,42 @@ class HipModel:
     def stat_free(self):
         self._ck(self.lib.picles_stat_free(self.h), "picles_stat_free")
 
+    # ---- open-boundary forcing (picles_bforce_*: prescribed sea state at rim nodes, born and advanced behind every step's launch) ----
+    def bforce_init(self, nodes):
+        """nodes: (n, 2) global 0-based (i, j), each a grid-boundary node (mask class 3) of a model without periodic_boundary, each once"""
+        ij = np.asarray(nodes, dtype=np.int64)
+        if ij.ndim != 2 or ij.shape[1] != 2:
+            raise ValueError("bforce_init: nodes must be an (n, 2) array of (i, j)")
+        if ij.size and (np.abs(ij).max() > 2**31 - 1):
+            raise ValueError("bforce_init: node index out of the int32 range")
+        planes = np.ascontiguousarray(ij.T.astype(np.int32))
+        self._ck(self.lib.picles_bforce_init(self.h, int(ij.shape[0]), planes.ctypes.data_as(K.c_int32_p)), "picles_bforce_init")
+
+    def bforce_set_levels(self, t0, v0, t1=None, v1=None):
+        """v0 (and v1): (n, 3) values (e, m_x, m_y) per forced node at t0 (and t1 > t0); one level: constant in time"""
+        n = self.bforce_info()[0]
+        def planes(v):
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape != (n, 3):
+                raise ValueError(f"bforce_set_levels: expected an ({n}, 3) array of (e, m_x, m_y), got {v.shape}")
+            return np.ascontiguousarray(v.T)
+        a = planes(v0)
+        b = None if v1 is None else planes(v1)
+        self._ck(self.lib.picles_bforce_set_levels(self.h, float(t0), K.dptr(a), float(t0 if t1 is None else t1), K.dptr(b)),
+                 "picles_bforce_set_levels")
+
+    def bforce_info(self):
+        """(n, levels held: 0, 1 or 2, t0, t1) of the forcing set; no device work"""
+        n, lv = C.c_int32(), C.c_int32()
+        t0, t1 = C.c_double(), C.c_double()
+        if self.lib.picles_bforce_info(self.h, C.byref(n), C.byref(lv), C.byref(t0), C.byref(t1)) != 0:
+            raise K.PiclesError("picles_bforce_info failed: bforce_init first")
+        return n.value, lv.value, t0.value, t1.value
+
+    def bforce_free(self):
+        self.gen += 1
+        self._ck(self.lib.picles_bforce_free(self.h), "picles_bforce_free")
+
     # ---- exact restart (picles_checkpoint_*) ----
     def checkpoint_size(self) -> int:
         n = C.c_size_t()

@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(9)
+const PICLES_ABI_VERSION = Int32(10)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -499,6 +499,40 @@ function probe_pop!(model::WaveGrowth2DHIP; max_samples::Integer=typemax(Int32))
 end
 
 probe_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_probe_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_probe_free")
+
+"""
+    bforce_init!(model, nodes)
+    bforce_set_levels!(model, t0, v0[, t1, v1])
+    bforce_free!(model)
+
+Open-boundary forcing (`picles_bforce_*`, the contract is in include/picles_hip.h): `nodes` is a vector of 1-based `(i, j)`, each a
+grid-boundary node (mask class 3) of a model without `periodic_boundary`.  Behind every model step's launch a particle is born at
+each of them from the prescribed `(e, m_x, m_y)` at the step's start time, advanced with the model's solver and scattered with the
+others; fused steps stay fused.  `v0`, `v1` are `n x 3` matrices; one level is constant in time, two are followed linearly in `t`,
+and every step must start inside `[t0, t1]`: set the next pair before the clock leaves the window.
+"""
+function bforce_init!(model::WaveGrowth2DHIP, nodes)
+    n = length(nodes)
+    ij = Vector{Int32}(undef, 2n)
+    for (k, (i, j)) in enumerate(nodes)
+        ij[k] = Int32(i - 1); ij[n + k] = Int32(j - 1)
+    end
+    check(model.ctx, ccall((:picles_bforce_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), model.ctx, n, ij), "picles_bforce_init")
+    nothing
+end
+
+function bforce_set_levels!(model::WaveGrowth2DHIP, t0::Real, v0::AbstractMatrix, t1::Real=t0, v1::Union{Nothing,AbstractMatrix}=nothing)
+    a = Matrix{Float64}(v0)
+    b = v1 === nothing ? nothing : Matrix{Float64}(v1)
+    size(a, 2) == 3 && (b === nothing || size(b) == size(a)) || error("bforce_set_levels!: levels are n x 3 matrices of (e, m_x, m_y)")
+    GC.@preserve a b begin
+        pb = b === nothing ? Ptr{Float64}(C_NULL) : pointer(b)
+        check(model.ctx, ccall((:picles_bforce_set_levels, libpicles), Int32, (Ptr{Cvoid}, Float64, Ptr{Float64}, Float64, Ptr{Float64}), model.ctx, Float64(t0), pointer(a), Float64(t1), pb), "picles_bforce_set_levels")
+    end
+    nothing
+end
+
+bforce_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_bforce_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_bforce_free")
 
 const PICLES_STAT_PEAK, PICLES_STAT_MEAN, PICLES_STAT_EXCEED = Int32(1), Int32(2), Int32(4)
 

@@ -1,5 +1,6 @@
 """OutputWriter: what run() (picles_amd/simulations.py) asks of the entries of `sim.output_writers` — Checkpointer, FieldWriter,
-StationWriter, StatisticsWriter.  run() names none of them: it calls the hooks below, each phase in the order PHASE_ORDER gives
+StationWriter, StatisticsWriter — and of the one input that is driven the same way, BoundaryForcing (picles_amd/boundary_forcing.py:
+visited first, so that the level pair of the next chunk is in place before anything else looks at the iteration).  run() names none of them: it calls the hooks below, each phase in the order PHASE_ORDER gives
 (by kind of writer, not by the dict's order), and a writer overrides the hooks it has work for.  DESIGN.md §16 says why the
 orders are what they are."""
 from __future__ import annotations
@@ -8,9 +9,9 @@ NO_LIMIT = 2**62          # steps_allowed of a writer that ends no chunk
 
 # the visiting order of each phase, by `kind`; a kind a phase does not list has no work in it (and is visited last)
 PHASE_ORDER = {
-    "begin_run": ("fields", "stations", "statistics"),
+    "begin_run": ("boundary_forcing", "fields", "stations", "statistics"),
     "after_chunk": ("stations", "checkpointer"),
-    "at_iteration": ("statistics", "checkpointer", "fields"),
+    "at_iteration": ("boundary_forcing", "statistics", "checkpointer", "fields"),
     "finish": ("checkpointer", "fields", "stations", "statistics"),
 }
 

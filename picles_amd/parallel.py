@@ -162,7 +162,11 @@ class HaloExchange:
 class SlabModel:
     """One rank's slab of a WaveGrowth2D problem, stepped with halo exchange.
 
-    `cfg_model` are the WaveGrowth2D keyword arguments (picles_amd.configs)."""
+    `cfg_model` are the WaveGrowth2D keyword arguments (picles_amd.configs).
+
+    Open-boundary forcing (picles_amd/boundary_forcing.py) is not available on slabs: the edge rows' records are exchanged before
+    the forced nodes' could be added, and both `BoundaryForcing` and the library (picles_bforce_init, picles_set_slab_mode,
+    picles_slab_*) refuse the combination."""
 
     def __init__(self, cfg_model: dict, rank: int, world: int, device: int = 0, halo_rows: int = 1,
                  backend_factory=None, use_streams=True, exchange=None, auto_halo_every: int = 0, fallback_group=None,
