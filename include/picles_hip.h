@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 10
+#define PICLES_ABI_VERSION 11
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -464,6 +464,53 @@ int32_t picles_bforce_init(picles_ctx *ctx, int32_t n, const int32_t *ij);
 int32_t picles_bforce_set_levels(picles_ctx *ctx, double t0, const double *v0, double t1, const double *v1);
 int32_t picles_bforce_info(const picles_ctx *ctx, int32_t *n, int32_t *levels, double *t0, double *t1);
 int32_t picles_bforce_free(picles_ctx *ctx);
+/* the level planes as the device holds them, 3 planes of n doubles each (NULL skips one; asking for a level the set does not hold
+ * fails, -2).  Stream-ordered behind whatever wrote them — an upload, or a parent's nest sample —; completes no pending step. */
+int32_t picles_bforce_get_levels(picles_ctx *ctx, double *v0, double *v1);
+
+/* ---- one-way nesting: a child box forced by its parent, all on the device.  The forcing set of `child` (picles_bforce_init) takes
+ * its time levels from the State of `parent`, another whole-grid context on the same device, instead of from the host: the parent
+ * is sampled behind its step, the sample is mixed onto the child's forced nodes and written into the child's level block in stream
+ * order.  State never leaves the device, the host waits for nothing, and both contexts stay on the fused path. ----
+ * THE GEOMETRY is the host's: n_corner distinct parent nodes, corner_ij = their i plane then their j plane (0-based, in the parent);
+ * per forced child node k, in the order of the child's set, four corners index[c n + k] into that list with the weights
+ * weight[c n + k], c = 0..3 (n = the set's node count).  The library uses them as given: no coordinate arithmetic on the device.
+ * A SAMPLE (picles_nest_sample) takes one time level at the parent's clock as it stands now: the State of the corner nodes — from
+ * the records of the parent's pending fused step where one is pending (it stays pending), from State in memory otherwise: the
+ * choice of picles_probe_sample — and per child node, every operation one IEEE operation in the order written:
+ *     a corner is WET when e, m_x, m_y are finite, e > 0 and m_x*m_x + m_y*m_y > 0
+ *     W = SE = SX = SY = +0.0;  for c = 0..3, if corner c is wet:  W = W + w;  SE = SE + w*e;  SX = SX + w*m_x;  SY = SY + w*m_y
+ *     E = SE / W;  MX = SX / W;  MY = SY / W;  M2 = MX*MX + MY*MY
+ *     the node is VALID when W > 0 and M2 > 0: its level is (E, MX, MY); otherwise NaN in all three
+ * (the station definition of picles_amd/station_output.py).  A NaN level is what THE BIRTH above refuses: that node bears no
+ * particle while either level of the pair is NaN.
+ * THE LEVELS.  The first sample after picles_nest_init is level 0 alone (levels = 1: constant, t0 = t1 = the parent's clock); the
+ * second becomes level 1; every later one rotates: level 1 becomes level 0, t0 <- t1, and the new level 1 is the parent's State at
+ * the parent's clock t1.  THE WINDOW rule above holds unchanged: the child steps inside [t0, t1], then the parent is stepped and
+ * sampled.  Steps of the child already enqueued keep the pair they were enqueued under.
+ * ORDERING.  picles_nest_sample returns after enqueueing: no synchronisation, no copy to the host.  Its two kernels run on the
+ * parent's stream behind whatever wrote the parent's records; the child's next launch that reads the levels waits for an event
+ * behind them, and they wait for an event behind the child's last launch that read the slot they overwrite (three slots rotate by
+ * pointer, so that launch lies a whole window back: the parent's step kernels never wait for the child's current steps).
+ *
+ *   init:    refuses (-2 / -5, both contexts unchanged and usable, picles_last_error(child) names the remedy) child == parent,
+ *            contexts on different devices, either context a slab, in slab mode or on a native ring, either context that has run
+ *            on caller-provided streams, a child without a boundary forcing set, n_corner < 1, an index outside [0, n_corner), a
+ *            corner outside the parent's grid, a weight that is not finite, a second init on the same child.  The arrays are free
+ *            on return.  The set has no levels afterwards (levels uploaded before are dropped): steps of the child are refused
+ *            until the first sample
+ *   sample:  refuses (-2, nothing changed) a child without a nest, a nest whose parent was destroyed, and a call while the
+ *            parent's clock has not moved past t1
+ *   info:    n_corner and the samples taken so far (either pointer may be NULL; -1 without a nest; no device work)
+ *   free:    drops the nest; the set keeps the level pair it holds and takes uploads again (picles_bforce_set_levels)
+ * With a nest, picles_bforce_set_levels is refused (-2: the levels come from the parent; picles_nest_free first).
+ * picles_bforce_free and picles_destroy on a nested child release the nest first.  picles_destroy(parent) detaches its children:
+ * each keeps its set and its last levels and goes on stepping under them; a later picles_nest_sample on it fails with a text.
+ * A parent may serve several children.  The nest is no part of a checkpoint. */
+int32_t picles_nest_init(picles_ctx *child, picles_ctx *parent, int32_t n_corner, const int32_t *corner_ij, const int32_t *index, const double *weight);
+int32_t picles_nest_sample(picles_ctx *child);
+int32_t picles_nest_info(const picles_ctx *child, int32_t *n_corner, int64_t *samples);
+int32_t picles_nest_free(picles_ctx *child);
 
 /* particles (own rows; z is 5 planes: lne, c̄x, c̄y, x, y). Any pointer may be NULL.
  * The state vector of a switched-off particle (on == 0) is dead storage: its content is unspecified. */

@@ -87,6 +87,35 @@ def rim_nodes(grid, side):
     raise ValueError(f"BoundaryForcing: side must be one of {SIDES}, not {side!r}")
 
 
+def node_points(grid, nodes):
+    """the mesh coordinates (x, y) of 0-based (i, j) nodes, as a list of float pairs"""
+    x, y = np.asarray(grid.data.x), np.asarray(grid.data.y)
+    return [(float(x[i, j]), float(y[i, j])) for i, j in np.asarray(nodes, dtype=np.int64).reshape(-1, 2)]
+
+
+def from_station_output(model, path, name="stations", *, nodes=None, side=None, Δt=None):
+    """the offline route of a nest: a BoundaryForcing for `model` from the file a StationWriter wrote in a parent run at the
+    model's forced nodes (`points=nesting.rim_points(model, side=... | nodes=...)`): `times` are /stations/time, `values` the
+    e, m_x, m_y of every record — NaN rows included: a station without a wet corner bears no particle.  The file's stations must
+    be the forced nodes in order"""
+    from .station_output import VAR_NAMES, read_station_output
+    if (nodes is None) == (side is None):
+        raise ValueError("from_station_output needs either nodes=[(i, j), ...] or side=...")
+    forced = np.asarray(rim_nodes(model.grid, side) if nodes is None else nodes, dtype=np.int64).reshape(-1, 2)
+    out = read_station_output(path, name)
+    data = np.asarray(out["data"], dtype=np.float64)
+    pts = np.asarray(node_points(model.grid, forced))
+    fx, fy = np.asarray(out["x"], dtype=np.float64), np.asarray(out["y"], dtype=np.float64)
+    if data.shape[1] != len(forced) or not (np.array_equal(fx, pts[:, 0]) and np.array_equal(fy, pts[:, 1])):
+        raise ValueError(f"from_station_output: the {data.shape[1]} stations of {name!r} are not the model's {len(forced)} forced nodes in order "
+                         "(write the file with StationWriter(points=nesting.rim_points(model, ...)))")
+    times = np.asarray(out["time"], dtype=np.float64)
+    keep = np.isfinite(times)                     # records a shorter run never wrote
+    names = [str(v) for v in out.get("var_names", VAR_NAMES)]
+    cols = [names.index(v) for v in ("e", "m_x", "m_y")]
+    return BoundaryForcing(model, nodes=forced, times=times[keep], values=data[keep][:, :, cols], Δt=Δt)
+
+
 class BoundaryForcing(OutputWriter):
     """BoundaryForcing(model, nodes=[(i, j), ...] | side="west" | "east" | "south" | "north" | "rim", times=[...],
     values=array(time, node, 3) | callable(t) -> (n, 3), Δt=None)"""

@@ -60,6 +60,7 @@
 #include "k_diag.h"
 #include "k_probe.h"
 #include "k_stat.h"
+#include "k_nest.h"
 
 /* ------------------------------------------------------------------------------------------
  * k_seed — init_particles! / SeedParticle / InitParticleValues / init_z0_to_State!
@@ -574,6 +575,11 @@ struct picles_ctx {
     double *bf_lv = nullptr;
     int bf_levels = 0;
     double bf_t0 = 0.0, bf_t1 = 0.0;
+    /* the planes bforce_launch hands k_bforce as level 0 and level 1: bf_lv and bf_lv + 3 bf_n for a set without a nest; with a nest
+     * (picles_nest_*, struct Nest below the context) two of its three slots, rotated by pointer at every sample */
+    double *bf_v0 = nullptr, *bf_v1 = nullptr;
+    struct Nest *nest = nullptr;                   /* this context is a nested child: its levels come from a parent context */
+    std::vector<picles_ctx *> nest_children;       /* this context is a parent: the children attached to it (picles_destroy detaches them) */
     /* gridded winds */
     bool wind_grid_on = false;
     WindGrid wg{};
@@ -711,6 +717,10 @@ static int stat_update(picles_ctx *c, hipStream_t s);
 static void stat_release(picles_ctx *c);
 /* open-boundary forcing (defined behind the run statistics) */
 static void bforce_release(picles_ctx *c);
+/* one-way nesting (defined behind the open-boundary forcing) */
+static int nest_before_launch(picles_ctx *c, hipStream_t s);
+static int nest_release(picles_ctx *c, bool keep_levels);
+static void nest_detach_children(picles_ctx *c);
 
 /* a model step has completed: the clock and the step counts the sampling schedules are counted in */
 static void step_completed(picles_ctx *c)
@@ -928,6 +938,10 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     if (c->ring) picles_slab_comm_destroy(c);
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->store_stream) hipStreamSynchronize(c->store_stream);     /* a checkpoint's copy-out may still be on PCIe */
+    /* nests: the children of this context keep their last levels and lose their parent (its stream has drained: no mix is in flight);
+     * a nested child leaves its parent's list before its own blocks go */
+    nest_detach_children(c);
+    if (c->nest) nest_release(c, false);
     Arrays &A = c->A;
     hipFree(A.state); hipFree(A.movie); hipFree(A.z); hipFree(A.qold); hipFree(A.dtn); hipFree(A.asw); hipFree(A.on);
     hipFree(A.pflags); hipFree(A.status); hipFree(A.u0); hipFree(A.v0); hipFree(A.u1); hipFree(A.v1);
@@ -1483,8 +1497,9 @@ static int bforce_launch(picles_ctx *c, hipStream_t s, const Arrays &A)
     BForceP B;
     B.n = c->bf_n;
     B.nodes = c->bf_nodes;
-    B.v0 = c->bf_lv;
-    B.v1 = c->bf_levels == 2 ? c->bf_lv + (size_t)3 * c->bf_n : nullptr;
+    if (c->nest) { int rc = nest_before_launch(c, s); if (rc) return rc; }      /* the levels a parent's stream wrote: read after write */
+    B.v0 = c->bf_v0;
+    B.v1 = c->bf_levels == 2 ? c->bf_v1 : nullptr;
     B.s = c->bf_levels == 2 ? (c->clock - c->bf_t0) / (c->bf_t1 - c->bf_t0) : 0.0;
     StepLaunch L = {dim3(1), dim3(256), s, &c->P, &c->G, &A, 0.0, 0.0, c->clock, c->step_dt, 0, 0, 0, 0};
     launch_k_bforce(L, B, c->P.solver, c->A.pc != nullptr);      /* k_bforce.hip */
@@ -2503,6 +2518,7 @@ static void bforce_release(picles_ctx *c)
     if (c->bf_lv) hipFree(c->bf_lv);
     c->bf_nodes = nullptr;
     c->bf_lv = nullptr;
+    c->bf_v0 = c->bf_v1 = nullptr;
     c->bf_n = 0;
     c->bf_levels = 0;
     c->bf_t0 = c->bf_t1 = 0.0;
@@ -2540,6 +2556,8 @@ PX_EXPORT int32_t picles_bforce_init(picles_ctx *c, int32_t n, const int32_t *ij
     HIPCHK(c, hipMemcpy(c->bf_nodes, loc.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));     /* blocking: loc dies here */
     c->bf_n = n;
     c->bf_levels = 0;
+    c->bf_v0 = c->bf_lv;
+    c->bf_v1 = c->bf_lv + (size_t)3 * n;
     undo.armed = false;
     return 0;
 }
@@ -2548,6 +2566,7 @@ PX_EXPORT int32_t picles_bforce_set_levels(picles_ctx *c, double t0, const doubl
 {
     if (!c) return -1;
     if (!c->bf_n) return fail(c, -2, "picles_bforce_init first");
+    if (c->nest) return fail(c, -2, "picles_bforce_set_levels: this set's levels come from a parent context (a nest): picles_nest_free first");
     if (!v0) return fail(c, -2, "picles_bforce_set_levels: level 0 must be given");
     if (v1 && !(t1 > t0)) return fail(c, -2, "picles_bforce_set_levels: two levels need t1 > t0");
     if (v1 && !(std::isfinite(t0) && std::isfinite(t1))) return fail(c, -2, "picles_bforce_set_levels: the level times must be finite");
@@ -2579,6 +2598,7 @@ PX_EXPORT int32_t picles_bforce_free(picles_ctx *c)
     if (!c) return -1;
     if (!c->bf_n) return 0;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->nest) { int rc = nest_release(c, false); if (rc) return rc; }      /* the nest goes with the set it feeds */
     { int rc = flush(c); if (rc) return rc; }      /* a pending step's forced records are scattered before they are emptied */
     HIPCHK(c, hipDeviceSynchronize());       /* launches in flight read the list and the levels about to go */
     hipLaunchKernelGGL(k_bforce_clear, dim3(nblocks(c->bf_n, 256)), dim3(256), 0, c->stream, c->G, c->rec_buf[0], c->rec_buf[1], c->A.on, c->A.status,
@@ -2588,6 +2608,230 @@ PX_EXPORT int32_t picles_bforce_free(picles_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     bforce_release(c);
     return 0;
+}
+
+PX_EXPORT int32_t picles_bforce_get_levels(picles_ctx *c, double *v0, double *v1)
+{
+    if (!c) return -1;
+    if (!c->bf_n) return fail(c, -2, "picles_bforce_init first");
+    if ((v0 && c->bf_levels < 1) || (v1 && c->bf_levels < 2))
+        return fail(c, -2, "picles_bforce_get_levels: the set holds " + std::to_string(c->bf_levels) + " level(s): pass NULL for a plane block it does not hold");
+    HIPCHK(c, hipSetDevice(c->device));
+    /* behind whatever wrote the levels: a parent's mix (its event), an upload on the context stream.  No flush: a pending step stays pending */
+    if (c->nest) { int rc = nest_before_launch(c, c->stream); if (rc) return rc; }
+    if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t b = (size_t)3 * c->bf_n * sizeof(double);
+    if (v0) HIPCHK(c, hipMemcpy(v0, c->bf_v0, b, hipMemcpyDeviceToHost));      /* blocking: the caller's buffers are complete on return */
+    if (v1) HIPCHK(c, hipMemcpy(v1, c->bf_v1, b, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* ---- one-way nesting (the contract: include/picles_hip.h "one-way nesting"; the mix kernel: k_nest.h) ----
+ * A nested child's forcing set takes its time levels from a PARENT context on the same device: the parent's State at the distinct
+ * corner nodes (k_probe, into `corner`), mixed onto the child's forced nodes (k_nest_mix) straight into one of three level slots.
+ * Slots 0 and 1 are the set's own block (bf_lv, bf_lv + 3 n), slot 2 is the nest's; the pair the child reads is (slot[i0], slot[i1]),
+ * rotated by pointer, and a sample writes the slot outside the pair.  Both kernels run on the PARENT's stream.  Events, both ways:
+ *   ev_mix      recorded on the parent's stream behind k_nest_mix; the child's next launch that reads the levels waits for it
+ *               (read after write: nest_before_launch)
+ *   ev_read[k]  recorded on the child's stream when slot k leaves the pair, behind the last enqueued launch that read it; the
+ *               parent's stream waits for it before the mix that overwrites slot k — a whole chunk of the child later, so the
+ *               parent's step kernels, which sit in front of the sampling on its stream, never wait for the child's current chunk
+ *               (write after read) */
+struct Nest {
+    picles_ctx *parent = nullptr;             /* nullptr: detached — the parent was destroyed; the levels stay */
+    int n_corner = 0;
+    int *corner_nodes = nullptr;              /* device: the i plane, then the row plane, of the parent's corner nodes */
+    double *corner = nullptr;                 /* device: 3 planes of n_corner doubles, the corner stage's output */
+    int *index = nullptr;                     /* device: 4 planes of bf_n */
+    double *weight = nullptr;                 /* device: 4 planes of bf_n */
+    double *extra = nullptr;                  /* device: slot 2 */
+    double *slot[3] = {nullptr, nullptr, nullptr};
+    int i0 = 0, i1 = 1;
+    hipEvent_t ev_mix = nullptr, ev_read[3] = {nullptr, nullptr, nullptr};
+    bool mix_unseen = false, read_live[3] = {false, false, false};
+    long long samples = 0;
+};
+
+/* the child's stream s is about to read the levels: behind the parent's latest mix */
+static int nest_before_launch(picles_ctx *c, hipStream_t s)
+{
+    Nest *N = c->nest;
+    if (!N->mix_unseen) return 0;
+    HIPCHK(c, hipStreamWaitEvent(s, N->ev_mix, 0));
+    if (s == c->stream) N->mix_unseen = false;
+    return 0;
+}
+
+static void nest_detach_children(picles_ctx *c)
+{
+    for (picles_ctx *k : c->nest_children)
+        if (k->nest) k->nest->parent = nullptr;
+    c->nest_children.clear();
+}
+
+/* drop the nest of c.  keep_levels: the pair the set holds moves home to (bf_lv, bf_lv + 3 n), where a set without a nest keeps it */
+static int nest_release(picles_ctx *c, bool keep_levels)
+{
+    Nest *N = c->nest;
+    if (!N) return 0;
+    HIPCHK(c, hipDeviceSynchronize());       /* a mix in flight writes the slots, launches in flight read them */
+    const size_t n3 = (size_t)3 * c->bf_n;
+    if (keep_levels && c->bf_levels > 0 && (N->i0 != 0 || (c->bf_levels == 2 && N->i1 != 1))) {
+        std::vector<double> h(2 * n3);
+        HIPCHK(c, hipMemcpy(h.data(), N->slot[N->i0], n3 * sizeof(double), hipMemcpyDeviceToHost));
+        if (c->bf_levels == 2) HIPCHK(c, hipMemcpy(h.data() + n3, N->slot[N->i1], n3 * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(c->bf_lv, h.data(), (c->bf_levels == 2 ? 2 : 1) * n3 * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (N->parent) {
+        auto &v = N->parent->nest_children;
+        v.erase(std::remove(v.begin(), v.end(), c), v.end());
+    }
+    if (N->corner_nodes) hipFree(N->corner_nodes);
+    if (N->corner) hipFree(N->corner);
+    if (N->index) hipFree(N->index);
+    if (N->weight) hipFree(N->weight);
+    if (N->extra) hipFree(N->extra);
+    if (N->ev_mix) hipEventDestroy(N->ev_mix);
+    for (int k = 0; k < 3; k++) if (N->ev_read[k]) hipEventDestroy(N->ev_read[k]);
+    delete N;
+    c->nest = nullptr;
+    c->bf_v0 = c->bf_lv;
+    c->bf_v1 = c->bf_lv ? c->bf_lv + n3 : nullptr;
+    return 0;
+}
+
+static const char *const NEST_NO_EXT_STREAMS = ": a context that has run on caller-provided streams cannot be ordered by the nest's events: "
+                                               "nest contexts that step on their own stream (stream = NULL everywhere)";
+
+PX_EXPORT int32_t picles_nest_init(picles_ctx *c, picles_ctx *p, int32_t n_corner, const int32_t *corner_ij, const int32_t *index, const double *weight)
+{
+    if (!c) return -1;
+    if (!p) return fail(c, -2, "picles_nest_init: no parent context given");
+    if (c == p) return fail(c, -2, "picles_nest_init: child and parent are the same context: a nest needs two (create the parent model separately)");
+    if (c->nest) return fail(c, -2, "picles_nest_init: this context holds a nest (picles_nest_free first)");
+    if (c->device != p->device)
+        return fail(c, -5, "picles_nest_init: child on device " + std::to_string(c->device) + ", parent on device " + std::to_string(p->device) +
+                           ": create both contexts on one device");
+    if (!c->G.single_slab || c->ring || !p->G.single_slab || p->ring)
+        return fail(c, -5, "picles_nest_init: slabs, slab mode and the native ring do not nest: both contexts must be whole-grid contexts");
+    if (!c->bf_n) return fail(c, -2, "picles_nest_init: the child has no boundary forcing set: picles_bforce_init with the nodes to force first");
+    if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string("picles_nest_init") + NEST_NO_EXT_STREAMS);
+    if (n_corner < 1 || !corner_ij || !index || !weight)
+        return fail(c, -2, "picles_nest_init: n_corner must be >= 1 and corner_ij, index and weight given");
+    const int n = c->bf_n;
+    for (int k = 0; k < n_corner; k++) {
+        const int i = corner_ij[k], j = corner_ij[(size_t)n_corner + k];
+        if (i < 0 || i >= p->G.Nx || j < 0 || j >= p->G.Ny)
+            return fail(c, -2, "picles_nest_init: corner " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) +
+                               ") lies outside the parent's grid [0, " + std::to_string(p->G.Nx) + ") x [0, " + std::to_string(p->G.Ny) + ")");
+    }
+    for (size_t k = 0; k < (size_t)4 * n; k++) {
+        if (index[k] < 0 || index[k] >= n_corner)
+            return fail(c, -2, "picles_nest_init: index " + std::to_string(index[k]) + " of node " + std::to_string(k % n) + ", corner " + std::to_string(k / n) +
+                               ", lies outside [0, n_corner = " + std::to_string(n_corner) + ")");
+        if (!std::isfinite(weight[k]))
+            return fail(c, -2, "picles_nest_init: the weight of node " + std::to_string(k % n) + ", corner " + std::to_string(k / n) + ", is not finite");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    Nest *N = new Nest;
+    c->nest = N;                              /* (no parent yet: a failure below releases without touching p) */
+    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) nest_release(c, true); } } undo{c, true};
+    HIPCHK(c, hipMalloc(&N->corner_nodes, (size_t)2 * n_corner * sizeof(int)));
+    HIPCHK(c, hipMalloc(&N->corner, (size_t)3 * n_corner * sizeof(double)));
+    HIPCHK(c, hipMalloc(&N->index, (size_t)4 * n * sizeof(int)));
+    HIPCHK(c, hipMalloc(&N->weight, (size_t)4 * n * sizeof(double)));
+    HIPCHK(c, hipMalloc(&N->extra, (size_t)3 * n * sizeof(double)));
+    HIPCHK(c, hipEventCreateWithFlags(&N->ev_mix, hipEventDisableTiming));
+    for (int k = 0; k < 3; k++) HIPCHK(c, hipEventCreateWithFlags(&N->ev_read[k], hipEventDisableTiming));
+    /* blocking copies: the caller's arrays are free on return (the parent is a whole grid: its local rows are the global ones) */
+    HIPCHK(c, hipMemcpy(N->corner_nodes, corner_ij, (size_t)2 * n_corner * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(N->index, index, (size_t)4 * n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(N->weight, weight, (size_t)4 * n * sizeof(double), hipMemcpyHostToDevice));
+    /* launches of the child enqueued under uploaded levels may still read slots 0 and 1 */
+    for (int k = 0; k < 2; k++) { HIPCHK(c, hipEventRecord(N->ev_read[k], c->stream)); N->read_live[k] = true; }
+    N->n_corner = n_corner;
+    N->slot[0] = c->bf_lv;
+    N->slot[1] = c->bf_lv + (size_t)3 * n;
+    N->slot[2] = N->extra;
+    N->parent = p;
+    p->nest_children.push_back(c);
+    c->bf_levels = 0;                         /* the levels come from the parent from here on: none taken yet */
+    c->bf_t0 = c->bf_t1 = 0.0;
+    c->bf_v0 = N->slot[0];
+    c->bf_v1 = N->slot[1];
+    undo.armed = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_sample(picles_ctx *c)
+{
+    if (!c) return -1;
+    Nest *N = c->nest;
+    if (!N) return fail(c, -2, "picles_nest_sample: picles_nest_init first");
+    picles_ctx *p = N->parent;
+    if (!p) return fail(c, -2, "picles_nest_sample: the parent context was destroyed (the set keeps its last levels): picles_nest_free, then "
+                               "picles_nest_init with a living parent");
+    if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string("picles_nest_sample") + NEST_NO_EXT_STREAMS);
+    if (N->samples > 0 && !(p->clock > c->bf_t1)) {
+        char b[256];
+        snprintf(b, sizeof b, "picles_nest_sample: the parent's clock (%.17g) has not moved past the latest level (%.17g): step the parent first", p->clock, c->bf_t1);
+        return fail(c, -2, b);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    /* the slot to write: level 0 at first, level 1 next, then the slot outside the pair — after the level that leaves the pair has
+     * had its last reader marked on the child's stream */
+    int w;
+    if (c->bf_levels == 0) w = N->i0;
+    else if (c->bf_levels == 1) w = N->i1;
+    else {
+        HIPCHK(c, hipEventRecord(N->ev_read[N->i0], c->stream));
+        N->read_live[N->i0] = true;
+        w = 3 - N->i0 - N->i1;
+    }
+    hipStream_t s = p->stream;
+    if (N->read_live[w]) { HIPCHK(c, hipStreamWaitEvent(s, N->ev_read[w], 0)); N->read_live[w] = false; }      /* write after read */
+    /* the corner stage: probe_take's choice — from the records of the parent's pending fused step, which stays pending, or from State */
+    const dim3 cgrid(nblocks(N->n_corner, PROBE_BLOCK)), cblock(PROBE_BLOCK);
+    if (p->pending)
+        hipLaunchKernelGGL(k_probe<true>, cgrid, cblock, 0, s, p->G, arrays_for(p, p->cur, p->cur), N->n_corner, (const int *)N->corner_nodes, N->corner);
+    else
+        hipLaunchKernelGGL(k_probe<false>, cgrid, cblock, 0, s, p->G, p->A, N->n_corner, (const int *)N->corner_nodes, N->corner);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_nest_mix, dim3(nblocks(c->bf_n, NEST_BLOCK)), dim3(NEST_BLOCK), 0, s, c->bf_n, N->n_corner, (const int *)N->index,
+                       (const double *)N->weight, (const double *)N->corner, N->slot[w]);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(N->ev_mix, s));      /* read after write: nest_before_launch */
+    N->mix_unseen = true;
+    if (c->bf_levels == 0) {
+        c->bf_levels = 1;
+        c->bf_t0 = c->bf_t1 = p->clock;
+    } else {
+        if (c->bf_levels == 2) { N->i0 = N->i1; c->bf_t0 = c->bf_t1; }
+        N->i1 = w;
+        c->bf_levels = 2;
+        c->bf_t1 = p->clock;
+    }
+    c->bf_v0 = N->slot[N->i0];
+    c->bf_v1 = N->slot[N->i1];
+    N->samples++;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_info(const picles_ctx *c, int32_t *n_corner, int64_t *samples)
+{
+    if (!c || !c->nest) return -1;
+    if (n_corner) *n_corner = c->nest->n_corner;
+    if (samples) *samples = c->nest->samples;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_free(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->nest) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    return nest_release(c, true);
 }
 
 /* ---- halo blocks ---- */
@@ -2628,6 +2872,7 @@ PX_EXPORT int32_t picles_set_slab_mode(picles_ctx *c, int32_t on)
     if (!(G.j_begin == 0 && G.ny_loc == G.Ny)) return on ? 0 : fail(c, -2, "a partial slab cannot resolve the y wrap locally");
     if (c->pending || c->seeded) return fail(c, -2, "picles_set_slab_mode: call before picles_seed");
     if (on && c->bf_n) return fail(c, -5, std::string("picles_set_slab_mode") + BFORCE_NO_SLABS);
+    if (on && !c->nest_children.empty()) return fail(c, -5, "picles_set_slab_mode: the context is the parent of a nest (picles_nest_free on its children first)");
     if (on) {
         if ((G.periodic_y && G.Ny <= 2 * G.R) || G.ny_loc < G.R)
             return fail(c, -2, "slab: periodic y axis not longer than 2*halo_rows, or fewer own rows than halo_rows");
@@ -2783,6 +3028,7 @@ PX_EXPORT int32_t picles_slab_comm_init(picles_ctx *c, const void *id128, int32_
     if (world < 1 || rank < 0 || rank >= world) return fail(c, -2, "slab ring: need 0 <= rank < world");
     if (c->ring) return fail(c, -2, "slab ring already initialised");
     if (c->bf_n) return fail(c, -5, std::string("picles_slab_comm_init") + BFORCE_NO_SLABS);
+    if (!c->nest_children.empty()) return fail(c, -5, "picles_slab_comm_init: the context is the parent of a nest (picles_nest_free on its children first)");
     if (c->G.single_slab && world > 1) return fail(c, -2, "slab ring of several ranks needs slab contexts (j_begin, j_end)");
     if (c->G.tripolar) return fail(c, -5, "slab ring: the tripolar fold is not wired into the native ring (use picles_amd.parallel)");
     HIPCHK(c, hipSetDevice(c->device));

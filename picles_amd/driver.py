@@ -594,6 +594,54 @@ class HipModel:
         self.gen += 1
         self._ck(self.lib.picles_bforce_free(self.h), "picles_bforce_free")
 
+    def bforce_get_levels(self):
+        """the levels as the device holds them: (v0, v1), each (n, 3) of (e, m_x, m_y) or None where the set does not hold it;
+        stream-ordered behind whatever wrote them, completes no pending step"""
+        n, lv, _, _ = self.bforce_info()
+        a = np.empty((3, n)) if lv >= 1 else None
+        b = np.empty((3, n)) if lv >= 2 else None
+        self._ck(self.lib.picles_bforce_get_levels(self.h, K.dptr(a), K.dptr(b)), "picles_bforce_get_levels")
+        return (None if a is None else np.ascontiguousarray(a.T)), (None if b is None else np.ascontiguousarray(b.T))
+
+    # ---- one-way nesting (picles_nest_*: this model's forcing set takes its levels from a parent model's State, on the device) ----
+    def nest_init(self, parent, corner_nodes, index, weights):
+        """parent: the HipModel to sample; corner_nodes (n_corner, 2): distinct 0-based (i, j) in the parent; index (n, 4) into
+        corner_nodes and weights (n, 4), per node of this model's forcing set in the set's order (one to four columns: missing
+        corners repeat the first with weight 0.0, which adds nothing)"""
+        cn = np.asarray(corner_nodes, dtype=np.int64).reshape(-1, 2)
+        ph = getattr(parent, "h", parent)
+        if self.lib.picles_bforce_info(self.h, None, None, None, None) != 0:      # no set: the library says what is missing
+            self._ck(self.lib.picles_nest_init(self.h, ph, 0, None, None, None), "picles_nest_init")
+        n = self.bforce_info()[0]
+        ix, w = np.asarray(index, dtype=np.int64), np.asarray(weights, dtype=np.float64)
+        if ix.ndim != 2 or ix.shape != w.shape or ix.shape[0] != n or not 1 <= ix.shape[1] <= 4:
+            raise ValueError(f"nest_init: index and weights must both be ({n}, 1..4) arrays, got {ix.shape} and {w.shape}")
+        if ix.shape[1] < 4:
+            pad = 4 - ix.shape[1]
+            ix = np.concatenate([ix, np.repeat(ix[:, :1], pad, axis=1)], axis=1)
+            w = np.concatenate([w, np.zeros((n, pad))], axis=1)
+        if (cn.size and np.abs(cn).max() > 2**31 - 1) or np.abs(ix).max() > 2**31 - 1:
+            raise ValueError("nest_init: index out of the int32 range")
+        cplanes = np.ascontiguousarray(cn.T.astype(np.int32))
+        iplanes = np.ascontiguousarray(ix.T.astype(np.int32))
+        wplanes = np.ascontiguousarray(w.T)
+        self._ck(self.lib.picles_nest_init(self.h, ph, int(cn.shape[0]), cplanes.ctypes.data_as(K.c_int32_p),
+                                           iplanes.ctypes.data_as(K.c_int32_p), K.dptr(wplanes)), "picles_nest_init")
+
+    def nest_sample(self):
+        """rotate the levels and take a new one from the parent as it stands now; returns after enqueueing"""
+        self._ck(self.lib.picles_nest_sample(self.h), "picles_nest_sample")
+
+    def nest_info(self):
+        """(n_corner, samples taken) of this model's nest"""
+        nc, s = C.c_int32(), C.c_int64()
+        if self.lib.picles_nest_info(self.h, C.byref(nc), C.byref(s)) != 0:
+            raise K.PiclesError("picles_nest_info failed: nest_init first")
+        return nc.value, s.value
+
+    def nest_free(self):
+        self._ck(self.lib.picles_nest_free(self.h), "picles_nest_free")
+
     # ---- exact restart (picles_checkpoint_*) ----
     def checkpoint_size(self) -> int:
         n = C.c_size_t()

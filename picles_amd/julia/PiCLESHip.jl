@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(10)
+const PICLES_ABI_VERSION = Int32(11)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -533,6 +533,55 @@ function bforce_set_levels!(model::WaveGrowth2DHIP, t0::Real, v0::AbstractMatrix
 end
 
 bforce_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_bforce_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_bforce_free")
+
+"""
+    bforce_get_levels(model) -> (v0, v1)
+
+The levels as the device holds them, `n x 3` matrices of `(e, m_x, m_y)` (`nothing` for a level the set does not hold);
+stream-ordered behind whatever wrote them, completes no pending step.
+"""
+function bforce_get_levels(model::WaveGrowth2DHIP)
+    n, lv = Ref{Int32}(0), Ref{Int32}(0)
+    ccall((:picles_bforce_info, libpicles), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ptr{Float64}, Ptr{Float64}), model.ctx, n, lv, C_NULL, C_NULL) == 0 ||
+        error("bforce_get_levels: bforce_init! first")
+    a = lv[] >= 1 ? Matrix{Float64}(undef, n[], 3) : nothing
+    b = lv[] >= 2 ? Matrix{Float64}(undef, n[], 3) : nothing
+    GC.@preserve a b begin
+        pa = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+        pb = b === nothing ? Ptr{Float64}(C_NULL) : pointer(b)
+        check(model.ctx, ccall((:picles_bforce_get_levels, libpicles), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), model.ctx, pa, pb), "picles_bforce_get_levels")
+    end
+    a, b
+end
+
+"""
+    nest_init!(child, parent, corner_nodes, index, weights)
+    nest_sample!(child)
+    nest_free!(child)
+
+One-way nesting (`picles_nest_*`, the contract is in include/picles_hip.h): the forcing set of `child` (`bforce_init!` first) takes
+its levels from the State of `parent`, a whole-grid model on the same device.  `corner_nodes` is a vector of distinct 1-based
+`(i, j)` in the parent; `index` (`n x 4`, 1-based into `corner_nodes`) and `weights` (`n x 4`) give, per forced child node in the
+set's order, the four corners to mix — the station definition of the header.  `nest_sample!` takes a level from the parent as it
+stands now (level 0 first, then level 1, then the pair rotates) and returns after enqueueing; the child then steps inside
+`[t0, t1]` (`r` steps for a refinement of `r`), the parent takes a step, and the next sample follows.
+"""
+function nest_init!(child::WaveGrowth2DHIP, parent::WaveGrowth2DHIP, corner_nodes, index::AbstractMatrix, weights::AbstractMatrix)
+    nc = length(corner_nodes)
+    ij = Vector{Int32}(undef, 2nc)
+    for (k, (i, j)) in enumerate(corner_nodes)
+        ij[k] = Int32(i - 1); ij[nc + k] = Int32(j - 1)
+    end
+    size(index, 2) == 4 && size(index) == size(weights) || error("nest_init!: index and weights are n x 4 matrices")
+    ix = Matrix{Int32}(index .- 1)          # column-major n x 4: four planes of n
+    w = Matrix{Float64}(weights)
+    check(child.ctx, ccall((:picles_nest_init, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}), child.ctx, parent.ctx, nc, ij, ix, w), "picles_nest_init")
+    nothing
+end
+
+nest_sample!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_sample, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_sample")
+
+nest_free!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_free, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_free")
 
 const PICLES_STAT_PEAK, PICLES_STAT_MEAN, PICLES_STAT_EXCEED = Int32(1), Int32(2), Int32(4)
 

@@ -1,6 +1,8 @@
 """OutputWriter: what run() (picles_amd/simulations.py) asks of the entries of `sim.output_writers` — Checkpointer, FieldWriter,
 StationWriter, StatisticsWriter — and of the one input that is driven the same way, BoundaryForcing (picles_amd/boundary_forcing.py:
-visited first, so that the level pair of the next chunk is in place before anything else looks at the iteration).  run() names none of them: it calls the hooks below, each phase in the order PHASE_ORDER gives
+visited first, so that the level pair of the next chunk is in place before anything else looks at the iteration; NestForcing of
+picles_amd/nesting.py takes its place where the levels come from a parent model, and drives that model's writers through the same
+hooks).  run() names none of them: it calls the hooks below, each phase in the order PHASE_ORDER gives
 (by kind of writer, not by the dict's order), and a writer overrides the hooks it has work for.  DESIGN.md §16 says why the
 orders are what they are."""
 from __future__ import annotations
@@ -21,6 +23,10 @@ class OutputWriter:
     needs = None            # a backend method the writer cannot do without ...
     refusal = None          # ... and what run() says of a backend that lacks it
     sized_for_run = False   # begin_run sizes a file for the run: a finite stop_time is needed
+
+    def check_run(self, sim, writers, store=False, cash_store=False, pickup=False):
+        """run(sim, ...) is about to start with these arguments and these writers: raise for a combination this writer cannot
+        serve — nothing has been loaded or seeded yet"""
 
     def load_pickup(self, checkpoint_file):
         """run(sim, pickup=...) has loaded `checkpoint_file`: take what this writer stored next to it"""

@@ -106,6 +106,8 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
     for w in writers:
         if not hasattr(m.backend, w.needs):
             raise NotImplementedError(w.refusal)
+    for w in writers:
+        w.check_run(sim, writers, store=store, cash_store=cash_store, pickup=picked is not None)
     phase = {p: in_phase(writers, p) for p in PHASE_ORDER}
     if picked is not None:
         load_checkpoint(m, picked, sim.Δt)
