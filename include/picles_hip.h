@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 11
+#define PICLES_ABI_VERSION 12
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -467,6 +467,28 @@ int32_t picles_bforce_free(picles_ctx *ctx);
 /* the level planes as the device holds them, 3 planes of n doubles each (NULL skips one; asking for a level the set does not hold
  * fails, -2).  Stream-ordered behind whatever wrote them — an upload, or a parent's nest sample —; completes no pending step. */
 int32_t picles_bforce_get_levels(picles_ctx *ctx, double *v0, double *v1);
+/* ---- forcing bands (ABI 12): a set that also holds OCEAN nodes, with an optional blend weight per node.  Sea that
+ * travels more than one cell a step crosses a forced rim column between two levels and never enters; a band as deep as the swell
+ * travels closes that hole, and a weight that falls off inward makes the band a relaxation zone.
+ *   init_band:  ij as for picles_bforce_init; nodes of mask class 3 and of class 1 (ocean).  weight: NULL (every node 1.0) or n
+ *               doubles.  Refuses everything picles_bforce_init refuses, a node of class 0 or 2, and a weight that is not finite or
+ *               not in (0, 1].  picles_bforce_set_levels / _get_levels / _info / _free, the window rule and picles_nest_* work on
+ *               either kind of set; picles_bforce_init itself still refuses a class-1 node.
+ * A FORCED OCEAN NODE IS NOT STEPPED while the set lives: init clears its "stepped" flag in stream order behind whatever is enqueued
+ * (a pending fused step stays pending; the records it left at these nodes are pulled by the next step).  From then on the node is
+ * what a forced rim node is: no step kernel touches its particle slot or writes its record, k_bforce bears its particle and writes
+ * its record every step (the empty one where the value is refused), it takes no wind re-seed, and the counters count it once.
+ * picles_bforce_free restores the flags from the mask and the model; the next remesh seeds the nodes like any other.
+ * CHECKPOINTS.  The flags plane is a segment of the blob, but picles_checkpoint_load leaves a context with ITS OWN flags — the home
+ * flags with the set that lives in it applied, whatever the blob carried: a blob written under a band set and loaded into a context
+ * without one steps the band nodes again.  The fingerprint does not depend on the set.
+ * THE BLEND.  With p the prescribed value after the time interpolation above, m the model's State at the node at the step's start
+ * (what picles_probe_sample gives for that node: from the records of a pending fused step, or from State in memory) and w the
+ * node's weight, per component, each operation one IEEE operation,
+ *     v = m + w * (p - m)
+ * and THE BIRTH test is made on v.  A node with w == 1.0 reads no State: v is p to the bit, and a set without a weight below 1
+ * runs the kernels of an unweighted set. */
+int32_t picles_bforce_init_band(picles_ctx *ctx, int32_t n, const int32_t *ij, const double *weight);
 
 /* ---- one-way nesting: a child box forced by its parent, all on the device.  The forcing set of `child` (picles_bforce_init) takes
  * its time levels from the State of `parent`, another whole-grid context on the same device, instead of from the host: the parent

@@ -101,7 +101,7 @@ LATTICE_LINEAR, LATTICE_SMOOTH3 = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 11
+ABI_VERSION = 12
 SLAB_ID_BYTES = 128
 PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
 
@@ -179,6 +179,7 @@ SYMBOLS = {
     "picles_stat_reset": (C.c_int32, [_VP]),
     "picles_stat_free": (C.c_int32, [_VP]),
     "picles_bforce_init": (C.c_int32, [_VP, C.c_int32, c_int32_p]),
+    "picles_bforce_init_band": (C.c_int32, [_VP, C.c_int32, c_int32_p, c_double_p]),
     "picles_bforce_set_levels": (C.c_int32, [_VP, C.c_double, c_double_p, C.c_double, c_double_p]),
     "picles_bforce_info": (C.c_int32, [_VP, c_int32_p, c_int32_p, c_double_p, c_double_p]),
     "picles_bforce_free": (C.c_int32, [_VP]),

@@ -20,6 +20,12 @@ operation one IEEE operation (NumPy reproduces the bits: `lerp` below):
 One time level: constant.  THE BIRTH is NodeToParticle!'s branch A (`born_particles` below restates it): e, m_x, m_y finite,
 e >= minimal_state[0] and m_x² + m_y² >= minimal_state[1]; otherwise the node bears no particle that step.
 
+BANDS (`width=`, `weights=`).  Sea that travels more than one cell a step crosses a one-node rim between two levels
+and never enters.  `width=w` forces every node within w nodes of the side that can bear a particle (`band_nodes`), ocean nodes
+included: the library takes those out of the step kernels' hands while the set lives (picles_bforce_init_band).  With weights the
+band is a relaxation zone: per node and component v = m + w (p - m), p the prescribed value above, m the model's own State at the
+step's start (`blend` reproduces the bits); w = 1 is p itself.  `"linear"`: w = (width - d) / width, d the node distance to the side.
+
 `sea_state(hs, tp, direction, model)` turns a significant wave height, a peak period and a propagation direction into
 (e, m_x, m_y): the exact inverse of the definitions of picles_amd/station_output.py.
 
@@ -71,8 +77,44 @@ def born_particles(values, minimal_state):
     return born, z
 
 
-def rim_nodes(grid, side):
-    """the 0-based (i, j) nodes of one side of the mesh (corners included) or of the whole rim, i running fastest"""
+def side_distance(grid, side):
+    """(Nx, Ny) int array: the distance in nodes of every node to the forced side (to the nearest of the four for "rim"), 0 on it"""
+    Nx, Ny = int(grid.stats.Nx), int(grid.stats.Ny)
+    i, j = np.meshgrid(np.arange(Nx), np.arange(Ny), indexing="ij")
+    if side not in SIDES:
+        raise ValueError(f"BoundaryForcing: side must be one of {SIDES}, not {side!r}")
+    d = {"west": i, "east": Nx - 1 - i, "south": j, "north": Ny - 1 - j}
+    return np.minimum(np.minimum(d["west"], d["east"]), np.minimum(d["south"], d["north"])) if side == "rim" else d[side]
+
+
+def band_nodes(grid, side, width):
+    """the nodes within `width` nodes of a side (or of the whole rim) that can bear a particle — mask class 3 (grid boundary) or 1
+    (ocean); land and coast (0, 2) are skipped — row by row, i running fastest, and their distance d to the forced side"""
+    if not (isinstance(width, (int, np.integer)) and width >= 1):
+        raise ValueError(f"BoundaryForcing: width must be an integer >= 1, not {width!r}")
+    d = side_distance(grid, side)
+    mask = np.asarray(grid.data.mask)
+    keep = (d < int(width)) & ((mask == 1) | (mask == 3))
+    j, i = np.nonzero(keep.T)                     # rows in order, i fastest within a row
+    return [(int(a), int(b)) for a, b in zip(i, j)], d[i, j]
+
+
+def linear_weights(d, width):
+    """the "linear" ramp of a relaxation zone: w = (width - d) / width — 1 on the forced side, 1 / width on the band's last node"""
+    return (np.float64(width) - np.asarray(d, dtype=np.float64)) / np.float64(width)
+
+
+def blend(m, p, w):
+    """the library's blend of a prescribed value p into the model's own State m at weight w, bit for bit: v = m + w (p - m)"""
+    m, p, w = (np.asarray(a, dtype=np.float64) for a in (m, p, w))
+    return m + w * (p - m)
+
+
+def rim_nodes(grid, side, width=1):
+    """the 0-based (i, j) nodes of one side of the mesh (corners included) or of the whole rim, i running fastest; width > 1: the
+    band of every node within `width` nodes of it that can bear a particle (band_nodes), in the same order"""
+    if width != 1:
+        return band_nodes(grid, side, width)[0]
     Nx, Ny = int(grid.stats.Nx), int(grid.stats.Ny)
     if side == "west":
         return [(0, j) for j in range(Ny)]
@@ -93,7 +135,7 @@ def node_points(grid, nodes):
     return [(float(x[i, j]), float(y[i, j])) for i, j in np.asarray(nodes, dtype=np.int64).reshape(-1, 2)]
 
 
-def from_station_output(model, path, name="stations", *, nodes=None, side=None, Δt=None):
+def from_station_output(model, path, name="stations", *, nodes=None, side=None, Δt=None, width=1, weights=None):
     """the offline route of a nest: a BoundaryForcing for `model` from the file a StationWriter wrote in a parent run at the
     model's forced nodes (`points=nesting.rim_points(model, side=... | nodes=...)`): `times` are /stations/time, `values` the
     e, m_x, m_y of every record — NaN rows included: a station without a wet corner bears no particle.  The file's stations must
@@ -101,7 +143,7 @@ def from_station_output(model, path, name="stations", *, nodes=None, side=None, 
     from .station_output import VAR_NAMES, read_station_output
     if (nodes is None) == (side is None):
         raise ValueError("from_station_output needs either nodes=[(i, j), ...] or side=...")
-    forced = np.asarray(rim_nodes(model.grid, side) if nodes is None else nodes, dtype=np.int64).reshape(-1, 2)
+    forced = np.asarray(rim_nodes(model.grid, side, width) if nodes is None else nodes, dtype=np.int64).reshape(-1, 2)
     out = read_station_output(path, name)
     data = np.asarray(out["data"], dtype=np.float64)
     pts = np.asarray(node_points(model.grid, forced))
@@ -113,30 +155,34 @@ def from_station_output(model, path, name="stations", *, nodes=None, side=None, 
     keep = np.isfinite(times)                     # records a shorter run never wrote
     names = [str(v) for v in out.get("var_names", VAR_NAMES)]
     cols = [names.index(v) for v in ("e", "m_x", "m_y")]
-    return BoundaryForcing(model, nodes=forced, times=times[keep], values=data[keep][:, :, cols], Δt=Δt)
+    if isinstance(weights, str):                   # a ramp needs the side the distances are counted from
+        return BoundaryForcing(model, side=side, width=width, weights=weights, times=times[keep], values=data[keep][:, :, cols], Δt=Δt)
+    return BoundaryForcing(model, nodes=forced, weights=weights, times=times[keep], values=data[keep][:, :, cols], Δt=Δt)
 
 
 class BoundaryForcing(OutputWriter):
     """BoundaryForcing(model, nodes=[(i, j), ...] | side="west" | "east" | "south" | "north" | "rim", times=[...],
-    values=array(time, node, 3) | callable(t) -> (n, 3), Δt=None)"""
+    values=array(time, node, 3) | callable(t) -> (n, 3), Δt=None, width=1, weights=None | "linear" | array(n))
+
+    width > 1 (with side=), or an ocean node among nodes=: a BAND set (picles_bforce_init_band) — the forced ocean nodes are not
+    stepped while the set lives.  Choose the width as deep as the fastest swell travels in a step (cells per step, rounded up): sea
+    that crosses a one-node rim between two levels never enters.  weights: the prescribed value p is blended into the model's own
+    State m at the step's start, v = m + w (p - m) (`blend`); "linear": w = (width - d) / width, d the node distance to the
+    forced side — a relaxation zone."""
 
     kind = "boundary_forcing"
     needs = "bforce_init"
     refusal = "a BoundaryForcing needs a backend with bforce_init / bforce_set_levels (the HIP library)"
 
-    def __init__(self, model, *, nodes=None, side=None, times, values, Δt=None):
+    def __init__(self, model, *, nodes=None, side=None, times, values, Δt=None, width=1, weights=None):
         if type(model).__name__ == "SlabModel":
             raise NotImplementedError("BoundaryForcing: slabs do not carry a boundary forcing (the edge rows' records are exchanged "
                                       "before the forced nodes' could be added): use a whole-grid model")
         if (nodes is None) == (side is None):
             raise ValueError("BoundaryForcing needs either nodes=[(i, j), ...] or side=...")
         self.model = model
-        self.nodes = np.asarray(rim_nodes(model.grid, side) if nodes is None else nodes, dtype=np.int64).reshape(-1, 2)
+        self._take_nodes(model, nodes, side, width, weights)
         n = len(self.nodes)
-        if n < 1:
-            raise ValueError("BoundaryForcing: no node given")
-        if len(np.unique(self.nodes, axis=0)) != n:
-            raise ValueError("BoundaryForcing: a node is given twice")
         self.times = np.asarray(times, dtype=np.float64).reshape(-1)
         if self.times.size < 1 or not np.isfinite(self.times).all() or (np.diff(self.times) <= 0.0).any():
             raise ValueError("BoundaryForcing: times must be finite and strictly increasing")
@@ -152,6 +198,56 @@ class BoundaryForcing(OutputWriter):
         self._set_on = None           # the backend that holds this forcing's set
         self._k = None                # the window [times[k], times[k + 1]] it holds
         self._mark = None             # (time, iteration) of the last visit: Δt is read off two of them when it was not given
+
+    # ---- the set ----
+    def _take_nodes(self, model, nodes, side, width, weights):
+        """self.nodes, self.node_weights (None: every node 1.0) and self.band: does the set go through bforce_init_band?"""
+        who = type(self).__name__
+        if nodes is not None and width != 1:
+            raise ValueError(f"{who}: width= goes with side=; with nodes= the list is the band")
+        dist = None
+        if nodes is None and width != 1:
+            listed, dist = band_nodes(model.grid, side, width)
+        else:
+            listed = rim_nodes(model.grid, side) if nodes is None else nodes
+        self.nodes = np.asarray(listed, dtype=np.int64).reshape(-1, 2)
+        n = len(self.nodes)
+        if n < 1:
+            raise ValueError(f"{who}: no node given")
+        if len(np.unique(self.nodes, axis=0)) != n:
+            raise ValueError(f"{who}: a node is given twice")
+        self.width = int(width)
+        if weights is None:
+            self.node_weights = None
+        elif isinstance(weights, str):
+            if weights != "linear" or nodes is not None:
+                raise ValueError(f"{who}: weights must be None, \"linear\" (with side=) or an array of one weight per node, not {weights!r}")
+            self.node_weights = linear_weights(np.zeros(n, dtype=np.int64) if dist is None else dist, self.width)
+        else:
+            self.node_weights = np.asarray(weights, dtype=np.float64).reshape(-1)
+            if self.node_weights.shape != (n,):
+                raise ValueError(f"{who}: {self.node_weights.size} weights for {n} nodes")
+        if self.node_weights is not None and not (np.isfinite(self.node_weights).all() and (self.node_weights > 0.0).all() and (self.node_weights <= 1.0).all()):
+            raise ValueError(f"{who}: weights must be finite and in (0, 1]")
+        mask = np.asarray(model.grid.data.mask)
+        inside = (self.nodes >= 0).all(axis=1) & (self.nodes[:, 0] < mask.shape[0]) & (self.nodes[:, 1] < mask.shape[1])
+        ocean = np.zeros(n, dtype=bool)
+        ocean[inside] = mask[self.nodes[inside, 0], self.nodes[inside, 1]] == 1
+        self.band = bool(self.width != 1 or ocean.any() or self.node_weights is not None)
+
+    BAND_REFUSAL = ("a forcing band (width > 1, an ocean node among the forced nodes, or weights) needs a backend with "
+                    "bforce_init_band (the HIP library, ABI 12)")
+
+    def check_run(self, sim, writers, store=False, cash_store=False, pickup=False):
+        if self.band and not hasattr(sim.model.backend, "bforce_init_band"):
+            raise NotImplementedError(self.BAND_REFUSAL)
+
+    def _init_set(self, backend):
+        """width = 1 on rim nodes without weights: bforce_init as ever; anything else is a band set"""
+        if self.band:
+            backend.bforce_init_band(self.nodes, self.node_weights)
+        else:
+            backend.bforce_init(self.nodes)
 
     # ---- the levels ----
     def level(self, k):
@@ -200,7 +296,7 @@ class BoundaryForcing(OutputWriter):
         b = model.backend
         if self._set_on is b:
             b.bforce_free()
-        b.bforce_init(self.nodes)
+        self._init_set(b)
         self._set_on = b
         self._k = None
         self._mark = (self._time(b), int(model.clock.iteration))

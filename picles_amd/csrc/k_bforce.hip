@@ -1,6 +1,7 @@
-/* k_bforce.hip — open-boundary forcing: the particles of the forced rim nodes (picles_bforce_*, include/picles_hip.h) */
-/* The step kernels do not step grid-boundary nodes of a model without periodic_boundary (mask class 3: PF_BOUNDARY without PF_STEPPED),
- * and no kernel reads or writes their particle slots or their records.  k_bforce runs behind whichever launch writes the records of
+/* k_bforce.hip — open-boundary forcing: the particles of the forced nodes (picles_bforce_*, include/picles_hip.h) */
+/* The step kernels do not step a node without PF_STEPPED: the grid-boundary nodes of a model without periodic_boundary (mask class 3),
+ * and the ocean nodes of a band set (picles_bforce_init_band clears the flag of its class-1 nodes while the set lives), and no
+ * kernel reads or writes their particle slots or their records.  k_bforce runs behind whichever launch writes the records of
  * a step for the whole grid (k_step, k_step_waverow, k_advance), on the same stream, and does for every forced node what those do for
  * a stepped one: a particle is born from the prescribed (e, m_x, m_y) at the step's start time, advanced over the step by the model's
  * own solver under the node's wind, and leaves its scatter record in the buffer the step writes.
@@ -16,9 +17,17 @@
  *              column-major order of all records — there is no second list
  *   statistics the counters of the context count these particles like any others
  * General-physics flavours only (FAST = false, STATIC = false: the same bits as the specialised ones, every wind window carried,
- * polylines included), by solver and by metric.  One lane per forced node, a few thousand at most: a latency-bound launch of about
- * one RK integration at low occupancy.  Behind the RK loop the arguments are read again (k_advance.hip has
- * the reasons); the lane's node index comes from the list again, so nothing waits in LDS. */
+ * polylines included), by solver and by metric.  One lane per forced node: a rim is a few thousand, a three-deep band on a 4096²
+ * box about 49,000 — 192 workgroups, still less than one per compute unit, so the launch stays latency-bound at about one RK
+ * integration, and occupancy beyond the two workgroups per compute unit the bounds ask for would buy nothing: the bounds stay.
+ * Behind the RK loop the arguments are read again (k_advance.hip has the reasons); the lane's node index comes from the list
+ * again, so nothing waits in LDS.
+ *
+ * BLEND (a set with a weight below 1): the prescribed value p is mixed into the model's own State m of the node at
+ * the step's start, v = m + w (p - m) per component, three IEEE operations, and the birth test is made on v.  m is k_probe's value
+ * (k_probe.h): the pull over the records of the pending fused step where the launch in front scatters one (B.from_rec: A.rec and
+ * the reach indices are that launch's own), State in memory otherwise.  A lane with w == 1.0 pulls nothing: v is p to the bit.
+ * The flavours without BLEND are instantiated apart and do not know about any of this. */
 #include "kernels.h"
 
 /* the kernel arguments as the kernarg segment lays them out (kargs_reload, kernels.h) */
@@ -34,7 +43,7 @@ static_assert(__builtin_offsetof(BForceArgs, G) == sizeof(KParams) && __builtin_
               __builtin_offsetof(BForceArgs, t_start) == __builtin_offsetof(BForceArgs, B) + sizeof(BForceP),
               "BForceArgs must mirror the kernarg layout of k_bforce");
 
-template <bool METRIC, bool TSIT, bool AUTO>
+template <bool METRIC, bool TSIT, bool AUTO, bool BLEND>
 __global__ void __launch_bounds__(256, 2) k_bforce(KParams P, GridP G, Arrays A, BForceP B, double t_start, double DT)
 {
     dp_device_init(TSIT ? 1 : 0);
@@ -55,6 +64,21 @@ __global__ void __launch_bounds__(256, 2) k_bforce(KParams P, GridP G, Arrays A,
             e = e + B.s * (e1 - e);
             mx = mx + B.s * (mx1 - mx);
             my = my + B.s * (my1 - my);
+        }
+        if constexpr (BLEND) {
+            const double wk = B.w[k];
+            if (wk != 1.0) {
+                double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+                if (B.from_rec) {
+                    const int i = (int)(t % G.Nx), jl = (int)(t / G.Nx);
+                    pull_any(G, A, i, jl, pull_reach_local(G, A, i, jl, pull_reach(G, A, jl)), m0, m1, m2);
+                } else {
+                    m0 = A.state[t]; m1 = A.state[t + A.n]; m2 = A.state[t + 2 * A.n];
+                }
+                e = m0 + wk * (e - m0);
+                mx = m1 + wk * (mx - m1);
+                my = m2 + wk * (my - m2);
+            }
         }
         /* NodeToParticle! branch A on the prescribed value; anything else: no particle at this node this step */
         if (pm_isfinite(e) && pm_isfinite(mx) && pm_isfinite(my) && e >= P.min_e && mx * mx + my * my >= P.min_m2) {
@@ -93,12 +117,13 @@ __global__ void __launch_bounds__(256, 2) k_bforce(KParams P, GridP G, Arrays A,
     if (__ballot(on != 0)) flush_stats(Ab, S, rtile);
 }
 
-#define LAUNCH_BF(M) do { if (solver == 2) hipLaunchKernelGGL((k_bforce<M, true, true>), grid, dim3(PICLES_BLOCK), 0, L.stream, *L.P, *L.G, *L.A, B, L.t_start, L.DT); \
-                          else if (solver) hipLaunchKernelGGL((k_bforce<M, true, false>), grid, dim3(PICLES_BLOCK), 0, L.stream, *L.P, *L.G, *L.A, B, L.t_start, L.DT); \
-                          else hipLaunchKernelGGL((k_bforce<M, false, false>), grid, dim3(PICLES_BLOCK), 0, L.stream, *L.P, *L.G, *L.A, B, L.t_start, L.DT); } while (0)
+#define LAUNCH_BF(M, W) do { if (solver == 2) hipLaunchKernelGGL((k_bforce<M, true, true, W>), grid, dim3(PICLES_BLOCK), 0, L.stream, *L.P, *L.G, *L.A, B, L.t_start, L.DT); \
+                             else if (solver) hipLaunchKernelGGL((k_bforce<M, true, false, W>), grid, dim3(PICLES_BLOCK), 0, L.stream, *L.P, *L.G, *L.A, B, L.t_start, L.DT); \
+                             else hipLaunchKernelGGL((k_bforce<M, false, false, W>), grid, dim3(PICLES_BLOCK), 0, L.stream, *L.P, *L.G, *L.A, B, L.t_start, L.DT); } while (0)
+/* B.w != nullptr: the set has a weight below 1 (picles_bforce_init_band keeps no weight plane otherwise) */
 void launch_k_bforce(const StepLaunch &L, const BForceP &B, int solver, bool metric)
 {
     const dim3 grid((unsigned)((B.n + PICLES_BLOCK - 1) / PICLES_BLOCK));
-    if (metric) LAUNCH_BF(true);
-    else LAUNCH_BF(false);
+    if (B.w) { if (metric) LAUNCH_BF(true, true); else LAUNCH_BF(false, true); }
+    else { if (metric) LAUNCH_BF(true, false); else LAUNCH_BF(false, false); }
 }

@@ -1279,12 +1279,16 @@ void launch_k_step_auto(const StepLaunch &L, bool wind_static, bool metric);
 void launch_k_advance(const StepLaunch &L, bool fast, int solver, bool wind_static, bool metric);
 
 /* open-boundary forcing (k_bforce.hip): the forced nodes' local indices i + Nx jl, the two levels of the prescribed (e, m_x, m_y) —
- * 3 planes of n doubles each; v1 == nullptr: constant — and s = (t - t0) / (t1 - t0) of the step's start time, formed on the host */
+ * 3 planes of n doubles each; v1 == nullptr: constant — and s = (t - t0) / (t1 - t0) of the step's start time, formed on the host.
+ * w: nullptr, or the n blend weights of a set that has one below 1; from_rec: the launch in front scatters a pending fused step, so
+ * State at the step's start is the pull over the records that launch reads (the BLEND flavours alone read either) */
 struct BForceP {
     int n;
     const int *nodes;
     const double *v0, *v1;
     double s;
+    const double *w;
+    int from_rec;
 };
 /* behind the launch that writes the step's records, same stream (L.grid, L.block and the row ranges are not read).  A weak reference:
  * a build that links the host side without this unit (the host-only sanitizer harness links the four older ones) still links, and

@@ -578,7 +578,11 @@ struct picles_ctx {
     /* the planes bforce_launch hands k_bforce as level 0 and level 1: bf_lv and bf_lv + 3 bf_n for a set without a nest; with a nest
      * (picles_nest_*, struct Nest below the context) two of its three slots, rotated by pointer at every sample */
     double *bf_v0 = nullptr, *bf_v1 = nullptr;
-    struct Nest *nest = nullptr;                   /* this context is a nested child: its levels come from a parent context */
+    /* a band set (picles_bforce_init_band): the set's ocean nodes (mask class 1, local indices), whose PF_STEPPED is cleared in
+     * A.pflags while the set lives (context_pflags), and the blend weights of a set that has one below 1 (nullptr: none) */
+    std::vector<int> bf_ocean;
+    double *bf_w = nullptr;
+    struct Nest *nest = nullptr;                  /* this context is a nested child: its levels come from a parent context */
     std::vector<picles_ctx *> nest_children;       /* this context is a parent: the children attached to it (picles_destroy detaches them) */
     /* gridded winds */
     bool wind_grid_on = false;
@@ -717,6 +721,34 @@ static int stat_update(picles_ctx *c, hipStream_t s);
 static void stat_release(picles_ctx *c);
 /* open-boundary forcing (defined behind the run statistics) */
 static void bforce_release(picles_ctx *c);
+
+/* the particle flags of a context without a forcing set, from the node classes and the model alone:
+ * ocean_points (WaveGrowthModels2D.jl:256-270) and check_boundary_point (core_2D.jl:360-366) */
+static std::vector<unsigned char> home_pflags(const std::vector<signed char> &mask, bool periodic_boundary)
+{
+    std::vector<unsigned char> pf(mask.size(), 0);
+    for (size_t k = 0; k < mask.size(); k++) {
+        const signed char mk = mask[k];
+        unsigned char f = 0;
+        if (mk == 1) f |= PF_STEPPED;
+        if (mk == 3 && periodic_boundary) f |= PF_STEPPED | PF_GROUP2;
+        const bool bnd = periodic_boundary ? (mk == 2) : (mk >= 2);
+        if (bnd) f |= PF_BOUNDARY;
+        pf[k] = f;
+    }
+    return pf;
+}
+
+/* A.pflags as this context must hold it: the home flags with the live band set, if any, applied — its ocean nodes are not stepped.
+ * Formed from the host's own truth, never from the device plane; on the context stream, complete on return */
+static int context_pflags(picles_ctx *c)
+{
+    std::vector<unsigned char> pf = home_pflags(c->h_mask, c->md.periodic_boundary != 0);
+    for (int t : c->bf_ocean) pf[(size_t)t] &= (unsigned char)~PF_STEPPED;
+    HIPCHK(c, hipMemcpyAsync(c->A.pflags, pf.data(), pf.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      /* pf dies here */
+    return 0;
+}
 /* one-way nesting (defined behind the open-boundary forcing) */
 static int nest_before_launch(picles_ctx *c, hipStream_t s);
 static int nest_release(picles_ctx *c, bool keep_levels);
@@ -864,19 +896,10 @@ PX_EXPORT int32_t picles_create(const picles_grid *g, const picles_phys *p, cons
             c->h_mask[(long long)jl * G.Nx + i] = mk;
         }
     /* ocean_points (WaveGrowthModels2D.jl:256-270) and check_boundary_point (core_2D.jl:360-366) */
-    std::vector<unsigned char> pf(n, 0);
     bool any3 = false;
     if (g->mask) { for (long long k = 0; k < (long long)G.Nx * G.Ny; k++) if (g->mask[k] == 3) { any3 = true; break; } }
     else any3 = (!g->periodic_x || !g->periodic_y);
-    for (long long k = 0; k < n; k++) {
-        signed char mk = c->h_mask[k];
-        unsigned char f = 0;
-        if (mk == 1) f |= PF_STEPPED;
-        if (mk == 3 && m->periodic_boundary) f |= PF_STEPPED | PF_GROUP2;
-        bool bnd = m->periodic_boundary ? (mk == 2) : (mk >= 2);
-        if (bnd) f |= PF_BOUNDARY;
-        pf[k] = f;
-    }
+    const std::vector<unsigned char> pf = home_pflags(c->h_mask, m->periodic_boundary != 0);
     if (any3 && m->periodic_boundary) G.ngroups = 2;
     if ((long long)(G.ny_loc + 2 * G.R) * 6 * G.Nx >= (1LL << 31)) {
         g_create_error = "slab too large for 32-bit record offsets ((ny_loc + 2 halo_rows) * 6 * Nx must be < 2^31): use more slabs";
@@ -1492,11 +1515,15 @@ static int bforce_window(picles_ctx *c, double dt, long long n_steps, const char
 
 /* the forced nodes' particles of the step in flight, behind the launch that wrote its records for the whole grid, on its stream:
  * the same record buffer, the same generation of the reach counters and maps (A: the Arrays that launch was given) */
-static int bforce_launch(picles_ctx *c, hipStream_t s, const Arrays &A)
+/* from_rec: that launch scatters a pending fused step (A.rec holds its records, A.mr_idx its reach): State at the step's start, which
+ * a weighted set blends into, exists as those records only — probe_take's choice */
+static int bforce_launch(picles_ctx *c, hipStream_t s, const Arrays &A, bool from_rec)
 {
     BForceP B;
     B.n = c->bf_n;
     B.nodes = c->bf_nodes;
+    B.w = c->bf_w;
+    B.from_rec = from_rec ? 1 : 0;
     if (c->nest) { int rc = nest_before_launch(c, s); if (rc) return rc; }      /* the levels a parent's stream wrote: read after write */
     B.v0 = c->bf_v0;
     B.v1 = c->bf_levels == 2 ? c->bf_v1 : nullptr;
@@ -1540,7 +1567,7 @@ PX_EXPORT int32_t picles_advance_rows(picles_ctx *c, int32_t which, void *stream
     }
     timing_end(c, s);
     HIPCHK(c, hipGetLastError());
-    if (c->bf_n && (rc = bforce_launch(c, s, A))) return rc;
+    if (c->bf_n && (rc = bforce_launch(c, s, A, false))) return rc;
     if (which == PICLES_ROWS_EDGE && s != c->stream) {
         HIPCHK(c, hipEventRecord(c->ev_edge, s));
         c->edge_pending = true;
@@ -1625,7 +1652,7 @@ static int launch_step_rows(picles_ctx *c, int which, hipStream_t s)
     }
     timing_end(c, s);
     HIPCHK(c, hipGetLastError());
-    if (c->bf_n && (rc = bforce_launch(c, s, A))) return rc;
+    if (c->bf_n && (rc = bforce_launch(c, s, A, true))) return rc;
     return 0;
 }
 
@@ -2516,50 +2543,100 @@ static void bforce_release(picles_ctx *c)
 {
     if (c->bf_nodes) hipFree(c->bf_nodes);
     if (c->bf_lv) hipFree(c->bf_lv);
+    if (c->bf_w) hipFree(c->bf_w);
     c->bf_nodes = nullptr;
     c->bf_lv = nullptr;
+    c->bf_w = nullptr;
+    c->bf_ocean.clear();
     c->bf_v0 = c->bf_v1 = nullptr;
     c->bf_n = 0;
     c->bf_levels = 0;
     c->bf_t0 = c->bf_t1 = 0.0;
 }
 
-PX_EXPORT int32_t picles_bforce_init(picles_ctx *c, int32_t n, const int32_t *ij)
+/* band: picles_bforce_init_band — ocean nodes (mask class 1) are taken too, and an optional weight per node */
+__global__ void __launch_bounds__(256) k_bforce_unstep(unsigned char *pflags, int n, const int *nodes)
 {
-    if (!c) return -1;
-    if (c->bf_n) return fail(c, -2, "picles_bforce_init: a boundary forcing set exists (picles_bforce_free first)");
-    if (!launch_k_bforce) return fail(c, -5, "picles_bforce_init: this build of the library was linked without k_bforce");
-    if (n < 1 || !ij) return fail(c, -2, "picles_bforce_init: n must be >= 1 and the node list given");
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (k < n) pflags[nodes[k]] &= (unsigned char)~PF_STEPPED;      /* each node once in the list: a byte has one writer */
+}
+
+static int bforce_init_any(picles_ctx *c, int32_t n, const int32_t *ij, const double *weight, bool band)
+{
+    const std::string who = band ? "picles_bforce_init_band" : "picles_bforce_init";
+    if (c->bf_n) return fail(c, -2, who + ": a boundary forcing set exists (picles_bforce_free first)");
+    if (!launch_k_bforce) return fail(c, -5, who + ": this build of the library was linked without k_bforce");
+    if (n < 1 || !ij) return fail(c, -2, who + ": n must be >= 1 and the node list given");
     const GridP &G = c->G;
     if (!G.single_slab || c->ring)
-        return fail(c, -5, "picles_bforce_init: slabs and the native ring do not carry a boundary forcing (a whole-grid context, not in slab mode, is needed)");
-    if (G.tripolar) return fail(c, -5, "picles_bforce_init: not supported on a tripolar grid");
+        return fail(c, -5, who + ": slabs and the native ring do not carry a boundary forcing (a whole-grid context, not in slab mode, is needed)");
+    if (G.tripolar) return fail(c, -5, who + ": not supported on a tripolar grid");
     if (c->md.periodic_boundary)
-        return fail(c, -5, "picles_bforce_init: a model with periodic_boundary steps its grid-boundary nodes itself: there is no open rim to force");
-    std::vector<int> loc((size_t)n);
+        return fail(c, -5, who + ": a model with periodic_boundary steps its grid-boundary nodes itself: there is no open rim to force");
+    std::vector<int> loc((size_t)n), ocean;
     std::vector<unsigned char> seen((size_t)c->A.n, 0);
+    bool blend = false;
     for (int k = 0; k < n; k++) {
         const int i = ij[k], j = ij[(size_t)n + k];
-        const std::string node = "picles_bforce_init: node " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) + ")";
+        const std::string node = who + ": node " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) + ")";
         if (i < 0 || i >= G.Nx || j < 0 || j >= G.Ny) return fail(c, -2, node + " lies outside [0, Nx) x [0, Ny)");
         const long long t = (long long)j * G.Nx + i;
-        if (c->h_mask[t] != 3)
-            return fail(c, -2, node + " is no grid-boundary node (mask class " + std::to_string((int)c->h_mask[t]) + ", 3 is needed): only the open rim can be forced");
+        const int mk = (int)c->h_mask[t];
+        if (!band && mk != 3)
+            return fail(c, -2, node + " is no grid-boundary node (mask class " + std::to_string(mk) + ", 3 is needed): only the open rim can be forced");
+        if (band && mk != 3 && mk != 1)
+            return fail(c, -2, node + " is neither a grid-boundary node nor an ocean node (mask class " + std::to_string(mk) +
+                               ", 3 or 1 is needed): land and coast carry no particle");
         if (seen[t]) return fail(c, -2, node + " is given twice");
+        if (weight) {
+            const double w = weight[k];
+            if (!(std::isfinite(w) && w > 0.0 && w <= 1.0)) {
+                char b[64];
+                snprintf(b, sizeof b, "%.17g", w);
+                return fail(c, -2, node + " has the weight " + b + ": a weight must be finite and in (0, 1]");
+            }
+            if (w != 1.0) blend = true;
+        }
         seen[t] = 1;
         loc[k] = (int)t;
+        if (mk == 1) ocean.push_back((int)t);
     }
     HIPCHK(c, hipSetDevice(c->device));
     struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) bforce_release(c); } } undo{c, true};
     HIPCHK(c, hipMalloc(&c->bf_nodes, (size_t)n * sizeof(int)));
     HIPCHK(c, hipMalloc(&c->bf_lv, (size_t)6 * n * sizeof(double)));
     HIPCHK(c, hipMemcpy(c->bf_nodes, loc.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));     /* blocking: loc dies here */
+    if (blend) {      /* (a set whose weights are all 1.0 is an unweighted set: the flavours without BLEND, no plane) */
+        HIPCHK(c, hipMalloc(&c->bf_w, (size_t)n * sizeof(double)));
+        HIPCHK(c, hipMemcpy(c->bf_w, weight, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (!ocean.empty()) {
+        /* the set's ocean nodes leave the step kernels' hands: in stream order behind whatever is enqueued (a launch in flight on
+         * a caller's stream is waited for), a pending fused step stays pending — the records it left at these nodes are legitimate
+         * and the next step pulls them */
+        if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());
+        hipLaunchKernelGGL(k_bforce_unstep, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, c->A.pflags, n, (const int *)c->bf_nodes);
+        HIPCHK(c, hipGetLastError());
+    }
+    c->bf_ocean.swap(ocean);
     c->bf_n = n;
     c->bf_levels = 0;
     c->bf_v0 = c->bf_lv;
     c->bf_v1 = c->bf_lv + (size_t)3 * n;
     undo.armed = false;
     return 0;
+}
+
+PX_EXPORT int32_t picles_bforce_init(picles_ctx *c, int32_t n, const int32_t *ij)
+{
+    if (!c) return -1;
+    return bforce_init_any(c, n, ij, nullptr, false);
+}
+
+PX_EXPORT int32_t picles_bforce_init_band(picles_ctx *c, int32_t n, const int32_t *ij, const double *weight)
+{
+    if (!c) return -1;
+    return bforce_init_any(c, n, ij, weight, true);
 }
 
 PX_EXPORT int32_t picles_bforce_set_levels(picles_ctx *c, double t0, const double *v0, double t1, const double *v1)
@@ -2606,7 +2683,11 @@ PX_EXPORT int32_t picles_bforce_free(picles_ctx *c)
     HIPCHK(c, hipGetLastError());
     { int rc = class_map_zero(c); if (rc) return rc; }      /* records written by other means than the step kernels */
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    const bool band = !c->bf_ocean.empty();
     bforce_release(c);
+    /* the band's ocean nodes go back to the step kernels: the home flags, from h_mask and the model; the remesh of the next step
+     * finds them without a particle and seeds them like any other node */
+    if (band) return context_pflags(c);
     return 0;
 }
 
@@ -3577,6 +3658,9 @@ PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t 
     ckpt_launch(c, 2, S, payload);
     HIPCHK(c, hipGetLastError());
     { int rc = class_map_zero(c); if (rc) return rc; }      /* the map is not part of a checkpoint: it changes speed, never results */
+    /* the flags plane of the blob is the writer's; this context keeps its own: a band set that lives here leaves its ocean nodes
+     * unstepped, one that lived there does not reach here */
+    { int rc = context_pflags(c); if (rc) return rc; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->clock = h.clock;
     c->step_dt = h.step_dt;

@@ -559,8 +559,11 @@ class HipModel:
         self._ck(self.lib.picles_stat_free(self.h), "picles_stat_free")
 
     # ---- open-boundary forcing (picles_bforce_*: prescribed sea state at rim nodes, born and advanced behind every step's launch) ----
-    def bforce_init(self, nodes):
-        """nodes: (n, 2) global 0-based (i, j), each a grid-boundary node (mask class 3) of a model without periodic_boundary, each once"""
+    def bforce_init(self, nodes, weights=None):
+        """nodes: (n, 2) global 0-based (i, j), each a grid-boundary node (mask class 3) of a model without periodic_boundary, each once.
+        With weights the call is bforce_init_band's (ocean nodes are taken there too)"""
+        if weights is not None:
+            return self.bforce_init_band(nodes, weights)
         ij = np.asarray(nodes, dtype=np.int64)
         if ij.ndim != 2 or ij.shape[1] != 2:
             raise ValueError("bforce_init: nodes must be an (n, 2) array of (i, j)")
@@ -568,6 +571,23 @@ class HipModel:
             raise ValueError("bforce_init: node index out of the int32 range")
         planes = np.ascontiguousarray(ij.T.astype(np.int32))
         self._ck(self.lib.picles_bforce_init(self.h, int(ij.shape[0]), planes.ctypes.data_as(K.c_int32_p)), "picles_bforce_init")
+
+    def bforce_init_band(self, nodes, weights=None):
+        """a band set: nodes as for bforce_init, of mask class 3 or 1 (ocean: not stepped while the set lives); weights: None
+        (every node 1.0) or n values in (0, 1] — the prescribed value is blended into the model's own State, v = m + w (p - m)"""
+        ij = np.asarray(nodes, dtype=np.int64)
+        if ij.ndim != 2 or ij.shape[1] != 2:
+            raise ValueError("bforce_init_band: nodes must be an (n, 2) array of (i, j)")
+        if ij.size and (np.abs(ij).max() > 2**31 - 1):
+            raise ValueError("bforce_init_band: node index out of the int32 range")
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+            if w.shape != (ij.shape[0],):
+                raise ValueError(f"bforce_init_band: expected {ij.shape[0]} weights, got {w.shape[0]}")
+        planes = np.ascontiguousarray(ij.T.astype(np.int32))
+        self._ck(self.lib.picles_bforce_init_band(self.h, int(ij.shape[0]), planes.ctypes.data_as(K.c_int32_p), K.dptr(w)),
+                 "picles_bforce_init_band")
 
     def bforce_set_levels(self, t0, v0, t1=None, v1=None):
         """v0 (and v1): (n, 3) values (e, m_x, m_y) per forced node at t0 (and t1 > t0); one level: constant in time"""

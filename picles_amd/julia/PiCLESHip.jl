@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(11)
+const PICLES_ABI_VERSION = Int32(12)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -501,7 +501,7 @@ end
 probe_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_probe_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_probe_free")
 
 """
-    bforce_init!(model, nodes)
+    bforce_init!(model, nodes; band=false, weights=nothing)
     bforce_set_levels!(model, t0, v0[, t1, v1])
     bforce_free!(model)
 
@@ -511,13 +511,24 @@ each of them from the prescribed `(e, m_x, m_y)` at the step's start time, advan
 others; fused steps stay fused.  `v0`, `v1` are `n x 3` matrices; one level is constant in time, two are followed linearly in `t`,
 and every step must start inside `[t0, t1]`: set the next pair before the clock leaves the window.
 """
-function bforce_init!(model::WaveGrowth2DHIP, nodes)
+function bforce_init!(model::WaveGrowth2DHIP, nodes; band::Bool=false, weights::Union{Nothing,AbstractVector}=nothing)
     n = length(nodes)
     ij = Vector{Int32}(undef, 2n)
     for (k, (i, j)) in enumerate(nodes)
         ij[k] = Int32(i - 1); ij[n + k] = Int32(j - 1)
     end
-    check(model.ctx, ccall((:picles_bforce_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), model.ctx, n, ij), "picles_bforce_init")
+    if band || weights !== nothing
+        # a band set (`picles_bforce_init_band`): ocean nodes (mask class 1) are taken too and are not stepped while the set lives;
+        # `weights` in (0, 1] blend the prescribed value into the model's own State, v = m + w (p - m)
+        w = weights === nothing ? nothing : Vector{Float64}(weights)
+        w === nothing || length(w) == n || error("bforce_init!: one weight per node")
+        GC.@preserve w begin
+            pw = w === nothing ? Ptr{Float64}(C_NULL) : pointer(w)
+            check(model.ctx, ccall((:picles_bforce_init_band, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}), model.ctx, n, ij, pw), "picles_bforce_init_band")
+        end
+    else
+        check(model.ctx, ccall((:picles_bforce_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), model.ctx, n, ij), "picles_bforce_init")
+    end
     nothing
 end
 

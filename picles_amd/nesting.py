@@ -36,12 +36,12 @@ from .station_output import locate_points
 RATIO_EPS = 1e-12          # |r Δt_child - Δt_parent| may be this fraction of Δt_parent
 
 
-def rim_points(model, *, side=None, nodes=None):
+def rim_points(model, side=None, *, nodes=None, width=1):
     """the (x, y) of a model's forced nodes, in the order of its forcing set: the `points` of the StationWriter that records, in a
-    parent run, what a NestForcing would hand the model"""
+    parent run, what a NestForcing would hand the model (width > 1: the band of boundary_forcing.band_nodes)"""
     if (nodes is None) == (side is None):
         raise ValueError("rim_points needs either nodes=[(i, j), ...] or side=...")
-    return node_points(model.grid, rim_nodes(model.grid, side) if nodes is None else nodes)
+    return node_points(model.grid, rim_nodes(model.grid, side, width) if nodes is None else nodes)
 
 
 def locate_in_parent(parent_grid, points):
@@ -70,14 +70,16 @@ def _chunked(model, dt):
 
 
 class NestForcing(BoundaryForcing):
-    """NestForcing(child_model, parent=<Simulation>, nodes=[(i, j), ...] | side="west" | ... | "rim", ratio=r, Δt=None)
-    Δt: the child's step, where it is not parent.Δt / ratio to the last bit"""
+    """NestForcing(child_model, parent=<Simulation>, nodes=[(i, j), ...] | side="west" | ... | "rim", ratio=r, Δt=None, width=1,
+    weights=None | "linear" | array(n))
+    Δt: the child's step, where it is not parent.Δt / ratio to the last bit; width, weights: BoundaryForcing's — a band as deep as
+    the parent's fastest swell travels in a child step lets it enter"""
 
     kind = "boundary_forcing"
     needs = "nest_init"
     refusal = "a NestForcing needs a backend with nest_init / nest_sample (the HIP library)"
 
-    def __init__(self, model, *, parent, nodes=None, side=None, ratio=1, Δt=None):
+    def __init__(self, model, *, parent, nodes=None, side=None, ratio=1, Δt=None, width=1, weights=None):
         if type(model).__name__ == "SlabModel" or type(parent.model).__name__ == "SlabModel":
             raise NotImplementedError("NestForcing: slabs do not nest: use whole-grid models")
         if (nodes is None) == (side is None):
@@ -85,11 +87,7 @@ class NestForcing(BoundaryForcing):
         if parent.model is model:
             raise ValueError("NestForcing: the parent must be another model")
         self.model, self.parent = model, parent
-        self.nodes = np.asarray(rim_nodes(model.grid, side) if nodes is None else nodes, dtype=np.int64).reshape(-1, 2)
-        if len(self.nodes) < 1:
-            raise ValueError("NestForcing: no node given")
-        if len(np.unique(self.nodes, axis=0)) != len(self.nodes):
-            raise ValueError("NestForcing: a node is given twice")
+        self._take_nodes(model, nodes, side, width, weights)
         self.dt = float(parent.Δt) / _whole(ratio) if Δt is None else float(Δt)
         self.ratio = check_ratio(ratio, self.dt, float(parent.Δt))
         self.corner_nodes, self.index, self.weights = locate_in_parent(parent.model.grid, node_points(model.grid, self.nodes))
@@ -104,6 +102,7 @@ class NestForcing(BoundaryForcing):
 
     # ---- before anything is seeded ----
     def check_run(self, sim, writers, store=False, cash_store=False, pickup=False):
+        super().check_run(sim, writers, store=store, cash_store=cash_store, pickup=pickup)
         pw = writers_of(self.parent)
         if pickup or any(w.kind == "checkpointer" for w in list(writers) + pw):
             raise NotImplementedError("NestForcing: a nested pair cannot be checkpointed or picked up yet (the parent is a step ahead of the "
@@ -185,7 +184,7 @@ class NestForcing(BoundaryForcing):
             raise ValueError(f"NestForcing: the child's clock ({model.clock.time!r}) and the parent's ({pm.clock.time!r}) differ")
         if self._set_on is b:
             b.bforce_free()
-        b.bforce_init(self.nodes)
+        self._init_set(b)
         b.nest_init(pm.backend, self.corner_nodes, self.index, self.weights)
         self._set_on = b
         self.times, self._have, self._k = np.zeros(0), -1, None
