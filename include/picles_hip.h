@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 12
+#define PICLES_ABI_VERSION 13
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -533,6 +533,50 @@ int32_t picles_nest_init(picles_ctx *child, picles_ctx *parent, int32_t n_corner
 int32_t picles_nest_sample(picles_ctx *child);
 int32_t picles_nest_info(const picles_ctx *child, int32_t *n_corner, int64_t *samples);
 int32_t picles_nest_free(picles_ctx *child);
+
+/* ---- two-way nesting: the child's sea state fed back into its parent.  A nested child (picles_nest_init) may feed back: the library
+ * makes a forcing set on the PARENT — its ocean nodes under the child — whose one level is the child's State restricted onto them,
+ * written on the device behind the child's steps.  The set is picles_bforce_init_band's kind (its nodes leave the parent's step
+ * kernels' hands and bear their particle from the level behind every parent step: THE BIRTH above), unweighted, of mask class 1
+ * only, and it is allowed on a periodic_boundary parent.  No step kernel differs; both contexts stay on the fused path. ----
+ * THE GEOMETRY is the host's: n_fb parent nodes fb_ij (i plane, then j plane, 0-based, each once, mask class 1); n_src distinct child
+ * nodes src_ij likewise; per feedback node p a stencil of m entries, entry c at [c n_fb + p]: index into the source list and weight
+ * (finite, >= 0; 0.0 marks padding, which is skipped whatever its index names; at least one entry per node is not padding).
+ * A FEEDBACK (picles_nest_feedback) takes one level at the child's clock: the State of the source nodes — from the records of the
+ * child's pending fused step where one is pending (it stays pending), from State in memory otherwise — and per feedback node the
+ * station definition above over its m entries in order, every operation one IEEE operation:
+ *     W = SE = SX = SY = +0.0;  for c = 0..m-1, if w_c != 0 and source c is wet:  W = W + w;  SE = SE + w*e;  SX = SX + w*m_x;  SY = SY + w*m_y
+ *     E = SE / W;  MX = SX / W;  MY = SY / W;  valid when W > 0 and MX*MX + MY*MY > 0, otherwise NaN in all three
+ * A calm or dry source counts as missing, not as zero; a NaN level bears no particle: a parent node the child sees as land or wholly
+ * calm is empty in the parent for that step.
+ * THE LEVEL.  The parent's set always holds one level (levels = 1, constant; t0 = t1 = the child's clock at the feedback): the next
+ * parent step bears its feedback particles from it as it is.  It lives in the set's own two slots, used alternately; steps of the
+ * parent already enqueued keep the slot they were enqueued under.
+ * ORDERING.  picles_nest_feedback returns after enqueueing: no synchronisation, no copy to the host.  Its two kernels run on the
+ * child's stream behind whatever wrote the child's records; the parent's next k_bforce (behind its step kernel, which therefore
+ * still overlaps the child's steps) and picles_bforce_get_levels(parent) wait for an event behind them, and they wait for an event
+ * behind the parent's last launch that read the slot they overwrite — the parent step before last.
+ *
+ *   init:    refuses (-2 / -5, both contexts unchanged and usable, picles_last_error(child) has the text) a child without a nest or
+ *            whose parent was destroyed, a parent that holds a forcing set of its own (a context carries one set: feedback and an own
+ *            forcing of the parent are not supported together), either context that has run on caller-provided streams, n_fb < 1,
+ *            n_src < 1, m < 1, a source node outside the child's grid, an index outside [0, n_src), a weight that is not finite or is
+ *            negative, a node whose weights are all zero, a second init, and whatever picles_bforce_init_band refuses of a set on the
+ *            parent (a node off the grid or given twice, a tripolar grid, slabs, the native ring) or a node not of mask class 1.
+ *            The arrays are free on return.  The parent's set has no level afterwards: its steps are refused until the first feedback
+ *   feedback: refuses (-2, nothing changed) a child without feedback, a destroyed parent, and clocks of child and parent that differ
+ *            by more than 1e-9 of the child's step length (before any step of the child: that differ at all)
+ *   info:    the set's shape and the levels taken so far (any pointer may be NULL; -1 without feedback; no device work)
+ *   free:    drops the feedback and the parent's set; the parent's nodes go back to its step kernels (picles_bforce_free's way)
+ * While feedback lives, picles_bforce_set_levels(parent) is refused; picles_bforce_free(parent) drops the feedback with the set (the
+ * child keeps its one-way nest); picles_nest_free, picles_bforce_free and picles_destroy on the child release the feedback first;
+ * picles_destroy(parent) detaches it: a later picles_nest_feedback fails with a text.  Slab mode and the native ring stay refused
+ * on both contexts.  The feedback is no part of a checkpoint. */
+int32_t picles_nest_feedback_init(picles_ctx *child, int32_t n_fb, const int32_t *fb_ij, int32_t n_src, const int32_t *src_ij, int32_t m,
+                                  const int32_t *index, const double *weight);
+int32_t picles_nest_feedback(picles_ctx *child);
+int32_t picles_nest_feedback_info(const picles_ctx *child, int32_t *n_fb, int32_t *n_src, int32_t *m, int64_t *taken);
+int32_t picles_nest_feedback_free(picles_ctx *child);
 
 /* particles (own rows; z is 5 planes: lne, c̄x, c̄y, x, y). Any pointer may be NULL.
  * The state vector of a switched-off particle (on == 0) is dead storage: its content is unspecified. */

@@ -584,6 +584,10 @@ struct picles_ctx {
     double *bf_w = nullptr;
     struct Nest *nest = nullptr;                  /* this context is a nested child: its levels come from a parent context */
     std::vector<picles_ctx *> nest_children;       /* this context is a parent: the children attached to it (picles_destroy detaches them) */
+    /* two-way nesting (picles_nest_feedback_*, struct Feedback below the nest): a child that feeds its State back owns `fb`; the
+     * parent whose forcing set that feedback made and fills names the child in `fb_child` */
+    struct Feedback *fb = nullptr;
+    picles_ctx *fb_child = nullptr;
     /* gridded winds */
     bool wind_grid_on = false;
     WindGrid wg{};
@@ -753,6 +757,12 @@ static int context_pflags(picles_ctx *c)
 static int nest_before_launch(picles_ctx *c, hipStream_t s);
 static int nest_release(picles_ctx *c, bool keep_levels);
 static void nest_detach_children(picles_ctx *c);
+/* two-way nesting (defined behind the one-way nesting) */
+static int fb_before_launch(picles_ctx *p, hipStream_t s);
+static int fb_after_launch(picles_ctx *p, hipStream_t s, const double *read);
+static void fb_drop(picles_ctx *child);
+static void fb_detach(picles_ctx *p);
+static int fb_release(picles_ctx *child);
 
 /* a model step has completed: the clock and the step counts the sampling schedules are counted in */
 static void step_completed(picles_ctx *c)
@@ -964,6 +974,13 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     /* nests: the children of this context keep their last levels and lose their parent (its stream has drained: no mix is in flight);
      * a nested child leaves its parent's list before its own blocks go */
     nest_detach_children(c);
+    /* feedback: a child that feeds back frees it and, with it, the set it made on its parent; a parent that is fed detaches — the
+     * child's stream is drained first (a restrict in flight writes this context's level block), the child keeps its one-way nest */
+    if (c->fb) fb_release(c);
+    if (c->fb_child) {
+        hipDeviceSynchronize();
+        fb_detach(c);
+    }
     if (c->nest) nest_release(c, false);
     Arrays &A = c->A;
     hipFree(A.state); hipFree(A.movie); hipFree(A.z); hipFree(A.qold); hipFree(A.dtn); hipFree(A.asw); hipFree(A.on);
@@ -1525,12 +1542,14 @@ static int bforce_launch(picles_ctx *c, hipStream_t s, const Arrays &A, bool fro
     B.w = c->bf_w;
     B.from_rec = from_rec ? 1 : 0;
     if (c->nest) { int rc = nest_before_launch(c, s); if (rc) return rc; }      /* the levels a parent's stream wrote: read after write */
+    if (c->fb_child) { int rc = fb_before_launch(c, s); if (rc) return rc; }    /* the level a child's stream wrote: likewise */
     B.v0 = c->bf_v0;
     B.v1 = c->bf_levels == 2 ? c->bf_v1 : nullptr;
     B.s = c->bf_levels == 2 ? (c->clock - c->bf_t0) / (c->bf_t1 - c->bf_t0) : 0.0;
     StepLaunch L = {dim3(1), dim3(256), s, &c->P, &c->G, &A, 0.0, 0.0, c->clock, c->step_dt, 0, 0, 0, 0};
     launch_k_bforce(L, B, c->P.solver, c->A.pc != nullptr);      /* k_bforce.hip */
     HIPCHK(c, hipGetLastError());
+    if (c->fb_child) return fb_after_launch(c, s, B.v0);      /* the slot this launch read: write after read */
     return 0;
 }
 /* a launch over some of the rows is a slab's: refused with a set (nothing has been launched) */
@@ -2561,9 +2580,14 @@ __global__ void __launch_bounds__(256) k_bforce_unstep(unsigned char *pflags, in
     if (k < n) pflags[nodes[k]] &= (unsigned char)~PF_STEPPED;      /* each node once in the list: a byte has one writer */
 }
 
-static int bforce_init_any(picles_ctx *c, int32_t n, const int32_t *ij, const double *weight, bool band)
+/* mode: the rim set of picles_bforce_init, the band set of picles_bforce_init_band, or BF_FEEDBACK — the set picles_nest_feedback_init
+ * makes on a parent: ocean nodes (mask class 1) only, unweighted, and allowed on a periodic_boundary model (no rim there, but an interior) */
+enum { BF_RIM = 0, BF_BAND = 1, BF_FEEDBACK = 2 };
+
+static int bforce_init_any(picles_ctx *c, int32_t n, const int32_t *ij, const double *weight, int mode)
 {
-    const std::string who = band ? "picles_bforce_init_band" : "picles_bforce_init";
+    const bool band = mode == BF_BAND;
+    const std::string who = mode == BF_FEEDBACK ? "picles_nest_feedback_init: the parent's set" : band ? "picles_bforce_init_band" : "picles_bforce_init";
     if (c->bf_n) return fail(c, -2, who + ": a boundary forcing set exists (picles_bforce_free first)");
     if (!launch_k_bforce) return fail(c, -5, who + ": this build of the library was linked without k_bforce");
     if (n < 1 || !ij) return fail(c, -2, who + ": n must be >= 1 and the node list given");
@@ -2571,7 +2595,7 @@ static int bforce_init_any(picles_ctx *c, int32_t n, const int32_t *ij, const do
     if (!G.single_slab || c->ring)
         return fail(c, -5, who + ": slabs and the native ring do not carry a boundary forcing (a whole-grid context, not in slab mode, is needed)");
     if (G.tripolar) return fail(c, -5, who + ": not supported on a tripolar grid");
-    if (c->md.periodic_boundary)
+    if (c->md.periodic_boundary && mode != BF_FEEDBACK)
         return fail(c, -5, who + ": a model with periodic_boundary steps its grid-boundary nodes itself: there is no open rim to force");
     std::vector<int> loc((size_t)n), ocean;
     std::vector<unsigned char> seen((size_t)c->A.n, 0);
@@ -2582,7 +2606,9 @@ static int bforce_init_any(picles_ctx *c, int32_t n, const int32_t *ij, const do
         if (i < 0 || i >= G.Nx || j < 0 || j >= G.Ny) return fail(c, -2, node + " lies outside [0, Nx) x [0, Ny)");
         const long long t = (long long)j * G.Nx + i;
         const int mk = (int)c->h_mask[t];
-        if (!band && mk != 3)
+        if (mode == BF_FEEDBACK && mk != 1)
+            return fail(c, -2, node + " is no ocean node of the parent (mask class " + std::to_string(mk) + ", 1 is needed): feedback goes to nodes the parent steps");
+        if (mode == BF_RIM && mk != 3)
             return fail(c, -2, node + " is no grid-boundary node (mask class " + std::to_string(mk) + ", 3 is needed): only the open rim can be forced");
         if (band && mk != 3 && mk != 1)
             return fail(c, -2, node + " is neither a grid-boundary node nor an ocean node (mask class " + std::to_string(mk) +
@@ -2630,13 +2656,13 @@ static int bforce_init_any(picles_ctx *c, int32_t n, const int32_t *ij, const do
 PX_EXPORT int32_t picles_bforce_init(picles_ctx *c, int32_t n, const int32_t *ij)
 {
     if (!c) return -1;
-    return bforce_init_any(c, n, ij, nullptr, false);
+    return bforce_init_any(c, n, ij, nullptr, BF_RIM);
 }
 
 PX_EXPORT int32_t picles_bforce_init_band(picles_ctx *c, int32_t n, const int32_t *ij, const double *weight)
 {
     if (!c) return -1;
-    return bforce_init_any(c, n, ij, weight, true);
+    return bforce_init_any(c, n, ij, weight, BF_BAND);
 }
 
 PX_EXPORT int32_t picles_bforce_set_levels(picles_ctx *c, double t0, const double *v0, double t1, const double *v1)
@@ -2644,6 +2670,8 @@ PX_EXPORT int32_t picles_bforce_set_levels(picles_ctx *c, double t0, const doubl
     if (!c) return -1;
     if (!c->bf_n) return fail(c, -2, "picles_bforce_init first");
     if (c->nest) return fail(c, -2, "picles_bforce_set_levels: this set's levels come from a parent context (a nest): picles_nest_free first");
+    if (c->fb_child) return fail(c, -2, "picles_bforce_set_levels: this set's level comes from a child context (nest feedback): picles_nest_feedback_free "
+                                        "on the child, or picles_bforce_free here, first");
     if (!v0) return fail(c, -2, "picles_bforce_set_levels: level 0 must be given");
     if (v1 && !(t1 > t0)) return fail(c, -2, "picles_bforce_set_levels: two levels need t1 > t0");
     if (v1 && !(std::isfinite(t0) && std::isfinite(t1))) return fail(c, -2, "picles_bforce_set_levels: the level times must be finite");
@@ -2675,7 +2703,12 @@ PX_EXPORT int32_t picles_bforce_free(picles_ctx *c)
     if (!c) return -1;
     if (!c->bf_n) return 0;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->fb) { int rc = fb_release(c); if (rc) return rc; }                  /* a child's feedback goes before its nest */
     if (c->nest) { int rc = nest_release(c, false); if (rc) return rc; }      /* the nest goes with the set it feeds */
+    if (c->fb_child) {      /* a fed parent: the feedback goes with the set; the child keeps its one-way nest */
+        HIPCHK(c, hipDeviceSynchronize());       /* a restrict in flight on the child's stream writes the level block */
+        fb_drop(c->fb_child);
+    }
     { int rc = flush(c); if (rc) return rc; }      /* a pending step's forced records are scattered before they are emptied */
     HIPCHK(c, hipDeviceSynchronize());       /* launches in flight read the list and the levels about to go */
     hipLaunchKernelGGL(k_bforce_clear, dim3(nblocks(c->bf_n, 256)), dim3(256), 0, c->stream, c->G, c->rec_buf[0], c->rec_buf[1], c->A.on, c->A.status,
@@ -2700,6 +2733,7 @@ PX_EXPORT int32_t picles_bforce_get_levels(picles_ctx *c, double *v0, double *v1
     HIPCHK(c, hipSetDevice(c->device));
     /* behind whatever wrote the levels: a parent's mix (its event), an upload on the context stream.  No flush: a pending step stays pending */
     if (c->nest) { int rc = nest_before_launch(c, c->stream); if (rc) return rc; }
+    if (c->fb_child) { int rc = fb_before_launch(c, c->stream); if (rc) return rc; }
     if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t b = (size_t)3 * c->bf_n * sizeof(double);
@@ -2912,7 +2946,226 @@ PX_EXPORT int32_t picles_nest_free(picles_ctx *c)
     if (!c) return -1;
     if (!c->nest) return 0;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->fb) { int rc = fb_release(c); if (rc) return rc; }      /* the feedback lives on the nest */
     return nest_release(c, true);
+}
+
+/* ---- two-way nesting (the contract: include/picles_hip.h "two-way nesting"; the restrict kernel: k_nest.h) ----
+ * A nested child feeds its State back: the PARENT carries a forcing set of ocean nodes (bforce_init_any, BF_FEEDBACK) whose one
+ * level is the child's State restricted onto them — the child's State at the distinct source nodes (k_probe, into `src`), restricted
+ * (k_nest_restrict) straight into one of the set's own two slots (bf_lv, bf_lv + 3 n), used alternately; the parent's bf_v0 is
+ * switched by pointer.  Both kernels run on the CHILD's stream.  Events, both ways:
+ *   ev_restrict  recorded on the child's stream behind k_nest_restrict; the parent's next k_bforce (and picles_bforce_get_levels)
+ *                waits for it (read after write: fb_before_launch) — k_bforce sits behind the parent's step kernel on its stream,
+ *                so that kernel still overlaps the child's chunk
+ *   ev_read[k]   recorded on the parent's stream behind every k_bforce that read slot k (fb_after_launch); the child's stream waits
+ *                for it before the restrict that overwrites slot k.  With two slots that launch belongs to the parent step before
+ *                last: never current work (write after read) */
+struct Feedback {
+    picles_ctx *parent = nullptr;             /* nullptr: detached — the parent was destroyed */
+    int n_fb = 0, n_src = 0, m = 0;
+    int *src_nodes = nullptr;                 /* device: the i plane, then the row plane, of the child's source nodes */
+    double *src = nullptr;                    /* device: 3 planes of n_src doubles, the source stage's output */
+    int *index = nullptr;                     /* device: m planes of n_fb */
+    double *weight = nullptr;                 /* device: m planes of n_fb */
+    double *slot[2] = {nullptr, nullptr};     /* the parent's bf_lv and bf_lv + 3 n_fb */
+    int cur = 1;                              /* the slot the parent reads (the first feedback writes slot 0) */
+    hipEvent_t ev_restrict = nullptr, ev_read[2] = {nullptr, nullptr};
+    bool restrict_unseen = false, read_live[2] = {false, false};
+    long long taken = 0;
+};
+
+/* the parent's stream s is about to read the level: behind the child's latest restrict */
+static int fb_before_launch(picles_ctx *p, hipStream_t s)
+{
+    Feedback *F = p->fb_child->fb;
+    if (!F->restrict_unseen) return 0;
+    HIPCHK(p, hipStreamWaitEvent(s, F->ev_restrict, 0));
+    if (s == p->stream) F->restrict_unseen = false;
+    return 0;
+}
+
+/* a launch on the parent's stream s has been enqueued that reads the level at `read` */
+static int fb_after_launch(picles_ctx *p, hipStream_t s, const double *read)
+{
+    Feedback *F = p->fb_child->fb;
+    for (int k = 0; k < 2; k++)
+        if (read == F->slot[k]) {
+            HIPCHK(p, hipEventRecord(F->ev_read[k], s));
+            F->read_live[k] = true;
+        }
+    return 0;
+}
+
+/* free the child's feedback blocks and cut both links; the parent's set is the caller's business (nothing of it is touched).
+ * The caller has drained the device where work may be in flight */
+static void fb_drop(picles_ctx *c)
+{
+    Feedback *F = c->fb;
+    if (!F) return;
+    if (F->parent) F->parent->fb_child = nullptr;
+    if (F->src_nodes) hipFree(F->src_nodes);
+    if (F->src) hipFree(F->src);
+    if (F->index) hipFree(F->index);
+    if (F->weight) hipFree(F->weight);
+    if (F->ev_restrict) hipEventDestroy(F->ev_restrict);
+    for (int k = 0; k < 2; k++) if (F->ev_read[k]) hipEventDestroy(F->ev_read[k]);
+    delete F;
+    c->fb = nullptr;
+}
+
+/* the parent p goes: the child keeps its Feedback, without a parent and without slots (picles_nest_feedback then fails with a text) */
+static void fb_detach(picles_ctx *p)
+{
+    Feedback *F = p->fb_child->fb;
+    F->parent = nullptr;
+    F->slot[0] = F->slot[1] = nullptr;
+    F->restrict_unseen = F->read_live[0] = F->read_live[1] = false;
+    p->fb_child = nullptr;
+}
+
+/* drop the feedback of child c and, where the parent lives, the set it made there (its nodes go back to the parent's step kernels:
+ * picles_bforce_free restores the flags through context_pflags) */
+static int fb_release(picles_ctx *c)
+{
+    if (!c->fb) return 0;
+    picles_ctx *p = c->fb->parent;
+    HIPCHK(c, hipDeviceSynchronize());       /* a restrict in flight writes the parent's slots, the parent's launches read them */
+    fb_drop(c);
+    if (p) {
+        int rc = picles_bforce_free(p);
+        if (rc) return fail(c, rc, "picles_nest_feedback_free: the parent's set: " + p->err);
+    }
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_feedback_init(picles_ctx *c, int32_t n_fb, const int32_t *fb_ij, int32_t n_src, const int32_t *src_ij, int32_t m,
+                                            const int32_t *index, const double *weight)
+{
+    if (!c) return -1;
+    if (c->fb) return fail(c, -2, "picles_nest_feedback_init: this context feeds back already (picles_nest_feedback_free first)");
+    Nest *N = c->nest;
+    if (!N) return fail(c, -2, "picles_nest_feedback_init: the child holds no nest: picles_nest_init first (feedback goes to the parent of a nest)");
+    picles_ctx *p = N->parent;
+    if (!p) return fail(c, -2, "picles_nest_feedback_init: the parent context was destroyed");
+    if (p->bf_n)
+        return fail(c, -5, p->fb_child ? "picles_nest_feedback_init: the parent is fed by another child: one child per parent feeds back"
+                                       : "picles_nest_feedback_init: the parent holds a boundary forcing set of its own; a context carries one set, and feedback "
+                                         "is one: not supported together (picles_bforce_free on the parent first)");
+    if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string("picles_nest_feedback_init") + NEST_NO_EXT_STREAMS);
+    if (n_fb < 1 || !fb_ij) return fail(c, -2, "picles_nest_feedback_init: n_fb must be >= 1 and fb_ij given");
+    if (n_src < 1 || m < 1 || !src_ij || !index || !weight)
+        return fail(c, -2, "picles_nest_feedback_init: n_src and m must be >= 1 and src_ij, index and weight given");
+    for (int k = 0; k < n_src; k++) {
+        const int i = src_ij[k], j = src_ij[(size_t)n_src + k];
+        if (i < 0 || i >= c->G.Nx || j < 0 || j >= c->G.Ny)
+            return fail(c, -2, "picles_nest_feedback_init: source node " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) +
+                               ") lies outside the child's grid [0, " + std::to_string(c->G.Nx) + ") x [0, " + std::to_string(c->G.Ny) + ")");
+    }
+    {
+        std::vector<unsigned char> any((size_t)n_fb, 0);
+        for (size_t k = 0; k < (size_t)m * n_fb; k++) {
+            const std::string at = "node " + std::to_string(k % n_fb) + ", entry " + std::to_string(k / n_fb);
+            if (index[k] < 0 || index[k] >= n_src)
+                return fail(c, -2, "picles_nest_feedback_init: index " + std::to_string(index[k]) + " of " + at + ", lies outside [0, n_src = " +
+                                   std::to_string(n_src) + ")");
+            if (!std::isfinite(weight[k]) || weight[k] < 0.0)
+                return fail(c, -2, "picles_nest_feedback_init: the weight of " + at + ", is not finite or is negative");
+            if (weight[k] > 0.0) any[k % n_fb] = 1;
+        }
+        for (int k = 0; k < n_fb; k++)
+            if (!any[(size_t)k]) return fail(c, -2, "picles_nest_feedback_init: every weight of node " + std::to_string(k) + " is zero: it has no source");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    Feedback *F = new Feedback;
+    c->fb = F;                                /* (no parent yet: a failure below drops without touching p) */
+    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) fb_drop(c); } } undo{c, true};
+    HIPCHK(c, hipMalloc(&F->src_nodes, (size_t)2 * n_src * sizeof(int)));
+    HIPCHK(c, hipMalloc(&F->src, (size_t)3 * n_src * sizeof(double)));
+    HIPCHK(c, hipMalloc(&F->index, (size_t)m * n_fb * sizeof(int)));
+    HIPCHK(c, hipMalloc(&F->weight, (size_t)m * n_fb * sizeof(double)));
+    HIPCHK(c, hipEventCreateWithFlags(&F->ev_restrict, hipEventDisableTiming));
+    for (int k = 0; k < 2; k++) HIPCHK(c, hipEventCreateWithFlags(&F->ev_read[k], hipEventDisableTiming));
+    /* blocking copies: the caller's arrays are free on return (the child is a whole grid: its local rows are the global ones) */
+    HIPCHK(c, hipMemcpy(F->src_nodes, src_ij, (size_t)2 * n_src * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(F->index, index, (size_t)m * n_fb * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(F->weight, weight, (size_t)m * n_fb * sizeof(double), hipMemcpyHostToDevice));
+    /* the parent's set, last: what it refuses (a node off the grid, given twice or not of class 1; a tripolar grid) leaves both contexts as they were */
+    {
+        const std::string keep = p->err;
+        int rc = bforce_init_any(p, n_fb, fb_ij, nullptr, BF_FEEDBACK);
+        if (rc) {
+            const std::string why = p->err;
+            p->err = keep;
+            return fail(c, rc, why);
+        }
+    }
+    F->n_fb = n_fb;
+    F->n_src = n_src;
+    F->m = m;
+    F->slot[0] = p->bf_lv;
+    F->slot[1] = p->bf_lv + (size_t)3 * n_fb;
+    F->parent = p;
+    p->fb_child = c;
+    undo.armed = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_feedback(picles_ctx *c)
+{
+    if (!c) return -1;
+    Feedback *F = c->fb;
+    if (!F) return fail(c, -2, "picles_nest_feedback: picles_nest_feedback_init first");
+    picles_ctx *p = F->parent;
+    if (!p) return fail(c, -2, "picles_nest_feedback: the parent context was destroyed (its set went with it): picles_nest_feedback_free");
+    if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string("picles_nest_feedback") + NEST_NO_EXT_STREAMS);
+    /* the slack rule of the window check: within 1e-9 of the child's step length; before any step the clocks must be equal */
+    if (!(std::fabs(c->clock - p->clock) <= 1e-9 * c->step_dt)) {
+        char b[256];
+        snprintf(b, sizeof b, "picles_nest_feedback: the child's clock (%.17g) and the parent's (%.17g) differ: a feedback is taken where both "
+                              "models stand at the same time", c->clock, p->clock);
+        return fail(c, -2, b);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int w = 1 - F->cur;
+    hipStream_t s = c->stream;
+    if (F->read_live[w]) { HIPCHK(c, hipStreamWaitEvent(s, F->ev_read[w], 0)); F->read_live[w] = false; }      /* write after read */
+    /* the source stage: probe_take's choice — from the records of the child's pending fused step, which stays pending, or from State */
+    const dim3 sgrid(nblocks(F->n_src, PROBE_BLOCK)), sblock(PROBE_BLOCK);
+    if (c->pending)
+        hipLaunchKernelGGL(k_probe<true>, sgrid, sblock, 0, s, c->G, arrays_for(c, c->cur, c->cur), F->n_src, (const int *)F->src_nodes, F->src);
+    else
+        hipLaunchKernelGGL(k_probe<false>, sgrid, sblock, 0, s, c->G, c->A, F->n_src, (const int *)F->src_nodes, F->src);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_nest_restrict, dim3(nblocks(F->n_fb, NEST_BLOCK)), dim3(NEST_BLOCK), 0, s, F->n_fb, F->n_src, F->m, (const int *)F->index,
+                       (const double *)F->weight, (const double *)F->src, F->slot[w]);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(F->ev_restrict, s));      /* read after write: fb_before_launch */
+    F->restrict_unseen = true;
+    F->cur = w;
+    F->taken++;
+    p->bf_v0 = F->slot[w];
+    p->bf_levels = 1;                         /* one level, constant: the parent's next step bears its feedback particles from it as it is */
+    p->bf_t0 = p->bf_t1 = c->clock;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_feedback_info(const picles_ctx *c, int32_t *n_fb, int32_t *n_src, int32_t *m, int64_t *taken)
+{
+    if (!c || !c->fb) return -1;
+    if (n_fb) *n_fb = c->fb->n_fb;
+    if (n_src) *n_src = c->fb->n_src;
+    if (m) *m = c->fb->m;
+    if (taken) *taken = c->fb->taken;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_feedback_free(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->fb) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    return fb_release(c);
 }
 
 /* ---- halo blocks ---- */

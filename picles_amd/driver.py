@@ -612,6 +612,7 @@ class HipModel:
 
     def bforce_free(self):
         self.gen += 1
+        self._feedback_goes()
         self._ck(self.lib.picles_bforce_free(self.h), "picles_bforce_free")
 
     def bforce_get_levels(self):
@@ -647,6 +648,7 @@ class HipModel:
         wplanes = np.ascontiguousarray(w.T)
         self._ck(self.lib.picles_nest_init(self.h, ph, int(cn.shape[0]), cplanes.ctypes.data_as(K.c_int32_p),
                                            iplanes.ctypes.data_as(K.c_int32_p), K.dptr(wplanes)), "picles_nest_init")
+        self._nest_parent = parent if hasattr(parent, "gen") else None
 
     def nest_sample(self):
         """rotate the levels and take a new one from the parent as it stands now; returns after enqueueing"""
@@ -660,7 +662,50 @@ class HipModel:
         return nc.value, s.value
 
     def nest_free(self):
+        self._feedback_goes()
         self._ck(self.lib.picles_nest_free(self.h), "picles_nest_free")
+
+    # ---- two-way nesting (picles_nest_feedback_*: this nested model's State restricted onto ocean nodes of its parent, on the device) ----
+    def nest_feedback_init(self, fb_nodes, src_nodes, index, weights):
+        """fb_nodes (n_fb, 2): 0-based (i, j) of the parent's ocean nodes to feed; src_nodes (n_src, 2): distinct 0-based (i, j) of
+        this model; index (n_fb, m) into src_nodes and weights (n_fb, m) >= 0, 0.0 marking padding
+        (picles_amd/nesting.py: restriction_stencil).  The library makes the forcing set on the parent of this model's nest"""
+        fb = np.asarray(fb_nodes, dtype=np.int64).reshape(-1, 2)
+        sn = np.asarray(src_nodes, dtype=np.int64).reshape(-1, 2)
+        ix, w = np.asarray(index, dtype=np.int64), np.asarray(weights, dtype=np.float64)
+        if ix.ndim != 2 or ix.shape != w.shape or ix.shape[0] != fb.shape[0]:
+            raise ValueError(f"nest_feedback_init: index and weights must both be ({fb.shape[0]}, m) arrays, got {ix.shape} and {w.shape}")
+        if any(a.size and np.abs(a).max() > 2**31 - 1 for a in (fb, sn, ix)):
+            raise ValueError("nest_feedback_init: index out of the int32 range")
+        fplanes = np.ascontiguousarray(fb.T.astype(np.int32))
+        splanes = np.ascontiguousarray(sn.T.astype(np.int32))
+        iplanes = np.ascontiguousarray(ix.T.astype(np.int32))
+        wplanes = np.ascontiguousarray(w.T)
+        self._ck(self.lib.picles_nest_feedback_init(self.h, int(fb.shape[0]), fplanes.ctypes.data_as(K.c_int32_p), int(sn.shape[0]),
+                                                    splanes.ctypes.data_as(K.c_int32_p), int(ix.shape[1]), iplanes.ctypes.data_as(K.c_int32_p),
+                                                    K.dptr(wplanes)), "picles_nest_feedback_init")
+
+    def nest_feedback(self):
+        """take one level at this model's clock into the parent's set; returns after enqueueing"""
+        self._ck(self.lib.picles_nest_feedback(self.h), "picles_nest_feedback")
+
+    def nest_feedback_info(self):
+        """(n_fb, n_src, m, levels taken) of this model's feedback"""
+        a, b, m, t = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        if self.lib.picles_nest_feedback_info(self.h, C.byref(a), C.byref(b), C.byref(m), C.byref(t)) != 0:
+            raise K.PiclesError("picles_nest_feedback_info failed: nest_feedback_init first")
+        return a.value, b.value, m.value, t.value
+
+    def _feedback_goes(self):
+        """this model's feedback, if it has one, is about to be released: the parent's set goes with it, and the parent's pending
+        step is completed on the way"""
+        p = getattr(self, "_nest_parent", None)
+        if p is not None and self.lib.picles_nest_feedback_info(self.h, None, None, None, None) == 0:
+            p.gen += 1
+
+    def nest_feedback_free(self):
+        self._feedback_goes()
+        self._ck(self.lib.picles_nest_feedback_free(self.h), "picles_nest_feedback_free")
 
     # ---- exact restart (picles_checkpoint_*) ----
     def checkpoint_size(self) -> int:

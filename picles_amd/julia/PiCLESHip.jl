@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(12)
+const PICLES_ABI_VERSION = Int32(13)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -593,6 +593,48 @@ end
 nest_sample!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_sample, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_sample")
 
 nest_free!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_free, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_free")
+
+"""
+    nest_feedback_init!(child, fb_nodes, src_nodes, index, weights)
+    nest_feedback!(child)
+    nest_feedback_info(child)
+    nest_feedback_free!(child)
+
+Two-way nesting (`picles_nest_feedback_*`, the contract is in include/picles_hip.h): the nested `child` (`nest_init!` first) feeds its
+State back into its parent.  `fb_nodes` is a vector of 1-based `(i, j)` of the parent's ocean nodes to feed, `src_nodes` one of
+distinct 1-based `(i, j)` of the child; `index` (`n_fb x m`, 1-based into `src_nodes`) and `weights` (`n_fb x m`, `>= 0`, `0.0`
+marking padding) give the restriction stencil per feedback node.  `nest_feedback!` takes one level at the child's clock, which must
+be the parent's, and returns after enqueueing; the parent's next step bears its feedback particles from it.
+`nest_feedback_info` returns `(n_fb, n_src, m, taken)`.
+"""
+function nest_feedback_init!(child::WaveGrowth2DHIP, fb_nodes, src_nodes, index::AbstractMatrix, weights::AbstractMatrix)
+    planes(nodes) = begin
+        n = length(nodes)
+        ij = Vector{Int32}(undef, 2n)
+        for (k, (i, j)) in enumerate(nodes)
+            ij[k] = Int32(i - 1); ij[n + k] = Int32(j - 1)
+        end
+        ij
+    end
+    nf, ns = length(fb_nodes), length(src_nodes)
+    size(index, 1) == nf && size(index) == size(weights) || error("nest_feedback_init!: index and weights are n_fb x m matrices")
+    fb, sn = planes(fb_nodes), planes(src_nodes)
+    ix = Matrix{Int32}(index .- 1)          # column-major n_fb x m: m planes of n_fb
+    w = Matrix{Float64}(weights)
+    check(child.ctx, ccall((:picles_nest_feedback_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Float64}), child.ctx, nf, fb, ns, sn, size(index, 2), ix, w), "picles_nest_feedback_init")
+    nothing
+end
+
+nest_feedback!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_feedback, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_feedback")
+
+function nest_feedback_info(child::WaveGrowth2DHIP)
+    a, b, m, t = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0), Ref{Int64}(0)
+    ccall((:picles_nest_feedback_info, libpicles), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int64}), child.ctx, a, b, m, t) == 0 ||
+        error("picles_nest_feedback_info failed: nest_feedback_init! first")
+    (a[], b[], m[], t[])
+end
+
+nest_feedback_free!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_feedback_free, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_feedback_free")
 
 const PICLES_STAT_PEAK, PICLES_STAT_MEAN, PICLES_STAT_EXCEED = Int32(1), Int32(2), Int32(4)
 

@@ -22,10 +22,18 @@ TIME.  `ratio` is an integer r >= 1 with |r Δt_child - Δt_parent| <= 1e-12 Δt
 THE OFFLINE ROUTE gives the same bits: run the parent alone with `StationWriter(points=rim_points(child_model, side=...))`, then the
 child under `boundary_forcing.from_station_output(child_model, path, side=...)`.
 
+TWO-WAY (`feedback=True`).  The parent learns what the child resolved: its ocean nodes under the child, a margin
+inside the child's band, become a forcing set of the parent whose one level is the child's State restricted onto them
+(`restriction_stencil`, `restrict_records`; picles_nest_feedback_*, the kernel is k_nest_restrict in picles_amd/csrc/k_nest.h).  A
+feedback is taken exactly when a parent step is taken, with both clocks equal, in front of that step.  Not for a parent that carries a
+BoundaryForcing of its own.
+
 Not for slabs, not together with a Checkpointer or `pickup=` (a restart of a pair whose parent is a step ahead is not defined yet),
 and only where run() takes its chunked path on both models: static winds, no `store`, no `cash_store`.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
@@ -51,6 +59,88 @@ def locate_in_parent(parent_grid, points):
     return corner_nodes, np.asarray(inv).reshape(corners.shape[:2]), weights
 
 
+SNAP = 1e-9               # a child node closer to a parent node, or to the end of its hat, than this fraction of a parent cell is on it
+
+
+def _axis_hat(pc, cc, D):
+    """per parent coordinate pc[k] the child coordinates inside its hat (|cc - pc| < D): (index int64 [n, mx], weight [n, mx]),
+    ascending in the child index, padded with weight 0.0; w = 1 - |cc - pc| / D from the coordinates alone"""
+    t = np.abs(np.asarray(cc, dtype=np.float64)[None, :] - np.asarray(pc, dtype=np.float64)[:, None]) / np.float64(D)
+    t = np.where(t < SNAP, 0.0, np.where(t > 1.0 - SNAP, 1.0, t))
+    w = np.maximum(0.0, 1.0 - t)
+    mx = max(int((w > 0.0).sum(axis=1).max(initial=0)), 1)
+    order = np.argsort(w == 0.0, axis=1, kind="stable")[:, :mx]          # the entries of the hat first, in child order
+    return order, np.take_along_axis(w, order, axis=1)
+
+
+def restriction_stencil(parent_grid, child_grid, margin=1):
+    """(fb_nodes int64 [n_fb, 2], src_nodes int64 [n_src, 2], index int64 [n_fb, m], weight float64 [n_fb, m]) of a two-way nest.
+
+    The feedback nodes are the parent's ocean nodes (mask class 1) whose one-cell neighbourhood lies inside the child's grid and
+    which lie at least `margin` parent cells inside the child's outermost nodes, row by row, i fastest.  The weights are the
+    adjoint of the bilinear interpolation the child's rim uses: for a child node at (xc, yc) and a parent node at (xp, yp),
+    w = max(0, 1 - |xc - xp| / Dx) max(0, 1 - |yc - yp| / Dy), from the coordinates alone (a distance within 1e-9 of a cell of 0 or
+    of Dx is that).  Per node the entries with w > 0, in row order of the child, i fastest, padded to m with weight 0.0 (the
+    padding repeats the node's first index); src_nodes are the distinct child nodes used, in row order, and index points into them.
+    A child at the parent's spacing gives m = 1 with weight 1.0 (injection), an aligned child at spacing ratio rs (2 rs - 1)²."""
+    if not (isinstance(margin, (int, np.integer)) and margin >= 0):
+        raise ValueError(f"restriction_stencil: margin must be an integer >= 0, not {margin!r}")
+    px, py = np.asarray(parent_grid.data.x)[:, 0], np.asarray(parent_grid.data.y)[0, :]
+    cx, cy = np.asarray(child_grid.data.x)[:, 0], np.asarray(child_grid.data.y)[0, :]
+    Dx, Dy = float(parent_grid.stats.dx), float(parent_grid.stats.dy)
+    reach = max(int(margin), 1)
+    okx = (px - reach * Dx >= cx[0] - SNAP * Dx) & (px + reach * Dx <= cx[-1] + SNAP * Dx)
+    oky = (py - reach * Dy >= cy[0] - SNAP * Dy) & (py + reach * Dy <= cy[-1] + SNAP * Dy)
+    keep = okx[:, None] & oky[None, :] & (np.asarray(parent_grid.data.mask) == 1)
+    j, i = np.nonzero(keep.T)                     # rows in order, i fastest within a row
+    fb_nodes = np.stack([i, j], axis=1).astype(np.int64)
+    if len(fb_nodes) == 0:
+        return fb_nodes, np.zeros((0, 2), dtype=np.int64), np.zeros((0, 1), dtype=np.int64), np.zeros((0, 1))
+    ix, wx = _axis_hat(px, cx, Dx)
+    iy, wy = _axis_hat(py, cy, Dy)
+    # entry (b, a) of node (i, j): child node (ix[i, a], iy[j, b]), a fastest — the child's row order
+    ci = np.repeat(ix[i][:, None, :], iy.shape[1], axis=1).reshape(len(i), -1)
+    cj = np.repeat(iy[j][:, :, None], ix.shape[1], axis=2).reshape(len(i), -1)
+    w = (wy[j][:, :, None] * wx[i][:, None, :]).reshape(len(i), -1)
+    m = int((w > 0.0).sum(axis=1).max())
+    order = np.argsort(w == 0.0, axis=1, kind="stable")[:, :m]
+    ci, cj, w = (np.take_along_axis(a, order, axis=1) for a in (ci, cj, w))
+    ci, cj = np.where(w > 0.0, ci, ci[:, :1]), np.where(w > 0.0, cj, cj[:, :1])
+    Ncx = len(cx)
+    flat, inv = np.unique(cj * Ncx + ci, return_inverse=True)
+    src_nodes = np.stack([flat % Ncx, flat // Ncx], axis=1).astype(np.int64)
+    return fb_nodes, src_nodes, np.asarray(inv).reshape(ci.shape).astype(np.int64), np.ascontiguousarray(w)
+
+
+def restrict_records(values, index, weight):
+    """k_nest_restrict in NumPy, bit for bit: values float64 [n_src, 3] (e, m_x, m_y of the source nodes), index int [n_fb, m]
+    into them, weight [n_fb, m] -> float64 [n_fb, 3], NaN rows where no entry is wet.  The station definition of
+    picles_amd/station_output.py over m entries in order; an entry whose weight is 0.0 is padding and is skipped"""
+    v = np.asarray(values, dtype=np.float64).reshape(-1, 3)
+    index, weight = np.asarray(index, dtype=np.int64), np.asarray(weight, dtype=np.float64)
+    n = index.shape[0]
+    W = np.zeros(n); SE = np.zeros(n); SX = np.zeros(n); SY = np.zeros(n)
+    with np.errstate(all="ignore"):
+        for c in range(index.shape[1]):
+            e, mx, my = v[index[:, c], 0], v[index[:, c], 1], v[index[:, c], 2]
+            w = weight[:, c]
+            take = (w != 0.0) & np.isfinite(e) & np.isfinite(mx) & np.isfinite(my) & (e > 0.0) & (mx * mx + my * my > 0.0)
+            W = np.where(take, W + w, W)
+            SE = np.where(take, SE + w * e, SE)
+            SX = np.where(take, SX + w * mx, SX)
+            SY = np.where(take, SY + w * my, SY)
+        E, MX, MY = SE / W, SX / W, SY / W
+        valid = (W > 0.0) & (MX * MX + MY * MY > 0.0)
+    out = np.stack([E, MX, MY], axis=1)
+    out[~valid] = np.nan
+    return out
+
+
+def default_feedback_margin(width, dx_child, dx_parent):
+    """1 + ceil(width dx_child / dx_parent) parent cells: no node of the child's band is among the sources"""
+    return 1 + int(math.ceil(float(width) * float(dx_child) / float(dx_parent) - 1e-12))
+
+
 def _whole(ratio):
     if not (isinstance(ratio, (int, float, np.integer, np.floating)) and ratio == int(ratio) and ratio >= 1):
         raise ValueError(f"NestForcing: ratio must be an integer >= 1, not {ratio!r}")
@@ -71,7 +161,9 @@ def _chunked(model, dt):
 
 class NestForcing(BoundaryForcing):
     """NestForcing(child_model, parent=<Simulation>, nodes=[(i, j), ...] | side="west" | ... | "rim", ratio=r, Δt=None, width=1,
-    weights=None | "linear" | array(n))
+    weights=None | "linear" | array(n), feedback=False, feedback_margin=None)
+    feedback=True: two-way — the child's State is restricted onto the parent's ocean nodes under it, feedback_margin parent cells
+    inside the child's outermost nodes (default 1 + ceil(width dx_child / dx_parent): no band node of the child is fed back)
     Δt: the child's step, where it is not parent.Δt / ratio to the last bit; width, weights: BoundaryForcing's — a band as deep as
     the parent's fastest swell travels in a child step lets it enter"""
 
@@ -79,7 +171,9 @@ class NestForcing(BoundaryForcing):
     needs = "nest_init"
     refusal = "a NestForcing needs a backend with nest_init / nest_sample (the HIP library)"
 
-    def __init__(self, model, *, parent, nodes=None, side=None, ratio=1, Δt=None, width=1, weights=None):
+    FEEDBACK_REFUSAL = "a NestForcing with feedback=True needs a backend with nest_feedback_init / nest_feedback (the HIP library, ABI 13)"
+
+    def __init__(self, model, *, parent, nodes=None, side=None, ratio=1, Δt=None, width=1, weights=None, feedback=False, feedback_margin=None):
         if type(model).__name__ == "SlabModel" or type(parent.model).__name__ == "SlabModel":
             raise NotImplementedError("NestForcing: slabs do not nest: use whole-grid models")
         if (nodes is None) == (side is None):
@@ -91,6 +185,18 @@ class NestForcing(BoundaryForcing):
         self.dt = float(parent.Δt) / _whole(ratio) if Δt is None else float(Δt)
         self.ratio = check_ratio(ratio, self.dt, float(parent.Δt))
         self.corner_nodes, self.index, self.weights = locate_in_parent(parent.model.grid, node_points(model.grid, self.nodes))
+        self.feedback = bool(feedback)
+        self.feedbacks = 0            # levels handed to the parent
+        self._fb_on = None
+        if self.feedback:
+            self.needs, self.refusal = "nest_feedback_init", self.FEEDBACK_REFUSAL
+            pg, cg = parent.model.grid, model.grid
+            self.feedback_margin = (default_feedback_margin(self.width, cg.stats.dx, pg.stats.dx) if feedback_margin is None
+                                    else feedback_margin)
+            self.fb_nodes, self.src_nodes, self.fb_index, self.fb_weights = restriction_stencil(pg, cg, self.feedback_margin)
+            if len(self.fb_nodes) == 0:
+                raise ValueError(f"NestForcing: feedback=True, but no ocean node of the parent lies {self.feedback_margin} parent cell(s) "
+                                 "inside the child: a larger child or a smaller feedback_margin is needed")
         self.times = np.zeros(0)      # the parent's clock at every level taken, and behind them the time of the level to come
         self.values = None
         self.uploads = 0              # levels taken from the parent
@@ -107,6 +213,12 @@ class NestForcing(BoundaryForcing):
         if pickup or any(w.kind == "checkpointer" for w in list(writers) + pw):
             raise NotImplementedError("NestForcing: a nested pair cannot be checkpointed or picked up yet (the parent is a step ahead of the "
                                       "child): run without a Checkpointer and without pickup=")
+        if self.feedback:
+            if not hasattr(self.parent.model.backend, "bforce_init_band"):
+                raise NotImplementedError(self.FEEDBACK_REFUSAL)
+            if any(w.kind == "boundary_forcing" for w in pw):
+                raise NotImplementedError("NestForcing: feedback=True on a parent that carries a BoundaryForcing of its own: a model holds one "
+                                          "forcing set, and the feedback is one (not supported together)")
         if store or cash_store:
             raise NotImplementedError("NestForcing: run(child, store=True / cash_store=True) takes the per-step loop; a nest needs the chunked path")
         if sim.stop_time == float("inf"):
@@ -141,6 +253,8 @@ class NestForcing(BoundaryForcing):
         for w in self._pw:
             if w.steps_allowed(pb, self._pit0 + self.parent_steps) < 1:
                 raise RuntimeError(f"NestForcing: the parent's {w.kind} writer allows no step")
+        if self.feedback:
+            self._feed(child_backend)         # both clocks stand at the parent's: what the child resolved goes into this step
         pb.run_steps(ps.Δt, 1)
         child_backend.nest_sample()
         for w in self._pphase["after_chunk"]:
@@ -150,6 +264,10 @@ class NestForcing(BoundaryForcing):
         pm.clock.iteration = self._pit0 + self.parent_steps
         for w in self._pphase["at_iteration"]:
             w.at_iteration(pm, self._pw)
+
+    def _feed(self, child_backend):
+        child_backend.nest_feedback()
+        self.feedbacks += 1
 
     def _took_level(self, backend):
         """the library holds a new level: its time is the parent's clock, and the level to come is one parent step later"""
@@ -183,7 +301,8 @@ class NestForcing(BoundaryForcing):
         if float(pm.clock.time) != float(model.clock.time):
             raise ValueError(f"NestForcing: the child's clock ({model.clock.time!r}) and the parent's ({pm.clock.time!r}) differ")
         if self._set_on is b:
-            b.bforce_free()
+            b.bforce_free()               # (a feedback left behind goes with it)
+            self._fb_on = None
         self._init_set(b)
         b.nest_init(pm.backend, self.corner_nodes, self.index, self.weights)
         self._set_on = b
@@ -191,6 +310,11 @@ class NestForcing(BoundaryForcing):
         self._mark = (self._time(b), int(model.clock.iteration))
         b.nest_sample()                   # level 0: the parent at the common clock
         self._took_level(b)
+        if self.feedback:
+            b.nest_feedback_init(self.fb_nodes, self.src_nodes, self.fb_index, self.fb_weights)
+            self._fb_on = b
+            self.feedbacks = 0
+            self._feed(b)                 # the seed: State in memory at the common clock — the parent's set holds a level from here on
         self._parent_step(b)              # the parent is one step ahead from here on
         self._took_level(b)
 
@@ -216,6 +340,9 @@ class NestForcing(BoundaryForcing):
             for w in self._pphase["finish"]:
                 w.finish(pm.backend, pm.clock.iteration)
             self._pw = None
+        if self._fb_on is backend:
+            backend.nest_feedback_free()
+            self._fb_on = None
         if self._set_on is backend:
             backend.nest_free()
             backend.bforce_free()

@@ -7,7 +7,15 @@ process after un-timed conditioning steps:
   (c) host route run together: the parent's probe of the corner nodes popped (blocking) after every parent step, the NumPy mix,
       picles_bforce_set_levels, four child steps
 One JSON line on stdout.  --profile: a short nested run and nothing else, for
-`rocprofv3 --kernel-trace --stats -- python scripts/nest_cost.py --profile`."""
+`rocprofv3 --kernel-trace --stats -- python scripts/nest_cost.py --profile`.
+
+--feedback: the cost of two-way nesting instead, on the same pair: the parent's ocean nodes under the child, two
+parent cells inside its rim, are fed from the child (picles_nest_feedback_*: (2 * 4 - 1)^2 = 49 entries per node).  Per parent
+step, alternated rounds as above:
+  (t) two-way: four child steps, picles_nest_feedback, parent step, picles_nest_sample
+  (o) one-way: four child steps, parent step, picles_nest_sample
+  (b) parts:   the parent alone; the child alone under a constant level
+--feedback --profile: a short two-way run and nothing else, for rocprofv3 as above."""
 import json
 import sys
 import time
@@ -19,7 +27,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from picles_amd import configs, models
 from picles_amd.boundary_forcing import rim_nodes
 from picles_amd.grids import TwoDCartesianGridMesh
-from picles_amd.nesting import locate_in_parent, rim_points
+from picles_amd.nesting import default_feedback_margin, locate_in_parent, restriction_stencil, rim_points
 from picles_amd.simulations import Simulation, initialize_simulation
 from picles_amd.station_output import station_records
 
@@ -53,6 +61,76 @@ def wall(fn, contexts):
         b.sync()
     return 1e3 * (time.perf_counter() - t0) / STEPS
 
+
+def feedback_cost():
+    def pair():
+        p, c = parent(), child()
+        rim = rim_nodes(c.grid, "rim")
+        corner_nodes, index, weights = locate_in_parent(p.grid, rim_points(c, side="rim"))
+        c.backend.bforce_init(rim)
+        c.backend.nest_init(p.backend, corner_nodes, index, weights)
+        c.backend.nest_sample()
+        return p, c, rim
+
+    po, co, rim = pair()
+    pt, ct, _ = pair()
+    fb, src, index, weight = restriction_stencil(pt.grid, ct.grid, default_feedback_margin(1, CDX, PDX))
+    print(f"feedback nodes: {len(fb)}, child source nodes: {len(src)}, entries per node: {index.shape[1]}", file=sys.stderr)
+    ct.backend.nest_feedback_init(fb, src, index, weight)
+    ct.backend.nest_feedback()                  # the seed
+    for p, c in ((po, co), (pt, ct)):
+        p.backend.run_steps(DT, 1)
+        c.backend.nest_sample()
+
+    def one_way(n=STEPS):
+        for _ in range(n):
+            co.backend.run_steps(DT / RATIO, RATIO)
+            po.backend.run_steps(DT, 1)
+            co.backend.nest_sample()
+
+    def two_way(n=STEPS):
+        for _ in range(n):
+            ct.backend.run_steps(DT / RATIO, RATIO)
+            ct.backend.nest_feedback()
+            pt.backend.run_steps(DT, 1)
+            ct.backend.nest_sample()
+
+    one_way(WARM)
+    two_way(WARM)
+    if profile:
+        two_way(10)
+        pt.backend.sync(); ct.backend.sync()
+        return
+    pb, cb = parent(), child()
+    cb.backend.bforce_init(rim)
+    cb.backend.bforce_set_levels(0.0, co.backend.bforce_get_levels()[1])
+    pb.backend.run_steps(DT, WARM + 1)
+    cb.backend.run_steps(DT / RATIO, RATIO * WARM)
+    rows = {"two_way": [], "one_way": [], "parent_alone": [], "child_alone": []}
+    for r in range(ROUNDS + 1):          # round 0 conditions the clocks and is dropped
+        t = wall(two_way, (pt.backend, ct.backend))
+        o = wall(one_way, (po.backend, co.backend))
+        bp = wall(lambda: pb.backend.run_steps(DT, STEPS), (pb.backend,))
+        bc = wall(lambda: cb.backend.run_steps(DT / RATIO, RATIO * STEPS), (cb.backend,))
+        print(f"round {r}: two-way {t:.4f} ms per parent step; one-way {o:.4f}; parent alone {bp:.4f} + child alone {bc:.4f} = {bp + bc:.4f}", file=sys.stderr)
+        if r:
+            for k, x in zip(rows, (t, o, bp, bc)):
+                rows[k].append(x)
+    out = {"n": N, "ratio": RATIO, "forced_nodes": len(rim), "feedback_nodes": int(len(fb)), "source_nodes": int(len(src)), "entries_per_node": int(index.shape[1]),
+           "parent_steps_per_round": STEPS, "unit": "ms per parent step (host wall time)", "levels_taken": ct.backend.nest_feedback_info()[3]}
+    out.update({k + "_ms": v for k, v in rows.items()})
+    out.update({"median_" + k + "_ms": float(np.median(v)) for k, v in rows.items()})
+    out["median_parts_sum_ms"] = out["median_parent_alone_ms"] + out["median_child_alone_ms"]
+    out["median_feedback_cost_ms"] = out["median_two_way_ms"] - out["median_one_way_ms"]
+    out["one_way_overlap_ms"] = out["median_parts_sum_ms"] - out["median_one_way_ms"]
+    level = pt.backend.bforce_get_levels()[0]
+    out["nan_feedback_nodes"] = int(np.isnan(level[:, 0]).sum())
+    print(json.dumps(out))
+
+
+if "--feedback" in sys.argv:
+    feedback_cost()
+    sys.exit(0)
 
 # (a) the nested pair
 pa, ca = parent(), child()
