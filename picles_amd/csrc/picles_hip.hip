@@ -582,11 +582,11 @@ struct picles_ctx {
      * A.pflags while the set lives (context_pflags), and the blend weights of a set that has one below 1 (nullptr: none) */
     std::vector<int> bf_ocean;
     double *bf_w = nullptr;
-    struct Nest *nest = nullptr;                  /* this context is a nested child: its levels come from a parent context */
-    std::vector<picles_ctx *> nest_children;       /* this context is a parent: the children attached to it (picles_destroy detaches them) */
-    /* two-way nesting (picles_nest_feedback_*, struct Feedback below the nest): a child that feeds its State back owns `fb`; the
-     * parent whose forcing set that feedback made and fills names the child in `fb_child` */
+    /* nesting (picles_nest_*, picles_nest_feedback_*; struct Nest and struct Feedback below the forcing): a child owns `nest` (its
+     * levels come from a parent) and, where it feeds its State back, `fb`; a parent names its children, and the one that feeds it */
+    struct Nest *nest = nullptr;
     struct Feedback *fb = nullptr;
+    std::vector<picles_ctx *> nest_children;
     picles_ctx *fb_child = nullptr;
     /* gridded winds */
     bool wind_grid_on = false;
@@ -626,6 +626,14 @@ struct picles_ctx {
             return -10;                                                                        \
         }                                                                                      \
     } while (0)
+
+/* an init that fails half-way leaves nothing behind: `undo` runs when the scope is left, unless the init got through and kept it */
+template <class F> struct Undo {
+    F undo;
+    bool armed = true;
+    ~Undo() { if (armed) undo(); }
+};
+template <class F> Undo(F) -> Undo<F>;
 
 /* hipStreamQuery without side effects on the sticky last-error state (hipErrorNotReady is not a failure) */
 static bool stream_idle(hipStream_t s)
@@ -753,16 +761,11 @@ static int context_pflags(picles_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));      /* pf dies here */
     return 0;
 }
-/* one-way nesting (defined behind the open-boundary forcing) */
-static int nest_before_launch(picles_ctx *c, hipStream_t s);
-static int nest_release(picles_ctx *c, bool keep_levels);
-static void nest_detach_children(picles_ctx *c);
-/* two-way nesting (defined behind the one-way nesting) */
-static int fb_before_launch(picles_ctx *p, hipStream_t s);
-static int fb_after_launch(picles_ctx *p, hipStream_t s, const double *read);
-static void fb_drop(picles_ctx *child);
-static void fb_detach(picles_ctx *p);
-static int fb_release(picles_ctx *child);
+/* nesting, both directions (defined behind the open-boundary forcing) */
+static int nest_levels_wait(picles_ctx *c, hipStream_t s);
+static int nest_levels_read(picles_ctx *c, hipStream_t s, const double *read);
+static int nest_leave_set(picles_ctx *c);
+static void nest_leave_context(picles_ctx *c);
 
 /* a model step has completed: the clock and the step counts the sampling schedules are counted in */
 static void step_completed(picles_ctx *c)
@@ -971,17 +974,7 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     if (c->ring) picles_slab_comm_destroy(c);
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->store_stream) hipStreamSynchronize(c->store_stream);     /* a checkpoint's copy-out may still be on PCIe */
-    /* nests: the children of this context keep their last levels and lose their parent (its stream has drained: no mix is in flight);
-     * a nested child leaves its parent's list before its own blocks go */
-    nest_detach_children(c);
-    /* feedback: a child that feeds back frees it and, with it, the set it made on its parent; a parent that is fed detaches — the
-     * child's stream is drained first (a restrict in flight writes this context's level block), the child keeps its one-way nest */
-    if (c->fb) fb_release(c);
-    if (c->fb_child) {
-        hipDeviceSynchronize();
-        fb_detach(c);
-    }
-    if (c->nest) nest_release(c, false);
+    nest_leave_context(c);      /* nests and feedback, as a parent and as a child */
     Arrays &A = c->A;
     hipFree(A.state); hipFree(A.movie); hipFree(A.z); hipFree(A.qold); hipFree(A.dtn); hipFree(A.asw); hipFree(A.on);
     hipFree(A.pflags); hipFree(A.status); hipFree(A.u0); hipFree(A.v0); hipFree(A.u1); hipFree(A.v1);
@@ -1533,7 +1526,7 @@ static int bforce_window(picles_ctx *c, double dt, long long n_steps, const char
 /* the forced nodes' particles of the step in flight, behind the launch that wrote its records for the whole grid, on its stream:
  * the same record buffer, the same generation of the reach counters and maps (A: the Arrays that launch was given) */
 /* from_rec: that launch scatters a pending fused step (A.rec holds its records, A.mr_idx its reach): State at the step's start, which
- * a weighted set blends into, exists as those records only — probe_take's choice */
+ * a weighted set blends into, exists as those records only — probe_launch's choice */
 static int bforce_launch(picles_ctx *c, hipStream_t s, const Arrays &A, bool from_rec)
 {
     BForceP B;
@@ -1541,16 +1534,14 @@ static int bforce_launch(picles_ctx *c, hipStream_t s, const Arrays &A, bool fro
     B.nodes = c->bf_nodes;
     B.w = c->bf_w;
     B.from_rec = from_rec ? 1 : 0;
-    if (c->nest) { int rc = nest_before_launch(c, s); if (rc) return rc; }      /* the levels a parent's stream wrote: read after write */
-    if (c->fb_child) { int rc = fb_before_launch(c, s); if (rc) return rc; }    /* the level a child's stream wrote: likewise */
+    { int rc = nest_levels_wait(c, s); if (rc) return rc; }      /* levels another context's stream wrote: read after write */
     B.v0 = c->bf_v0;
     B.v1 = c->bf_levels == 2 ? c->bf_v1 : nullptr;
     B.s = c->bf_levels == 2 ? (c->clock - c->bf_t0) / (c->bf_t1 - c->bf_t0) : 0.0;
     StepLaunch L = {dim3(1), dim3(256), s, &c->P, &c->G, &A, 0.0, 0.0, c->clock, c->step_dt, 0, 0, 0, 0};
     launch_k_bforce(L, B, c->P.solver, c->A.pc != nullptr);      /* k_bforce.hip */
     HIPCHK(c, hipGetLastError());
-    if (c->fb_child) return fb_after_launch(c, s, B.v0);      /* the slot this launch read: write after read */
-    return 0;
+    return nest_levels_read(c, s, B.v0);      /* the slot this launch read: write after read */
 }
 /* a launch over some of the rows is a slab's: refused with a set (nothing has been launched) */
 static int bforce_rows(picles_ctx *c, int which, const char *who)
@@ -2071,7 +2062,7 @@ void OutRing::release()
 
 int OutRing::init(picles_ctx *c, int n_slots, size_t slot_bytes)
 {
-    struct Undo { OutRing *r; ~Undo() { if (r) r->release(); } } undo{this};
+    Undo undo{[this] { release(); }};
     { int rc = store_stream_get(c); if (rc) return rc; }
     stride = (slot_bytes + 15) & ~(size_t)15;
     HIPCHK(c, hipMalloc(&dev, (size_t)n_slots * stride));
@@ -2085,7 +2076,7 @@ int OutRing::init(picles_ctx *c, int n_slots, size_t slot_bytes)
     time.assign(n_slots, 0.0);
     step.assign(n_slots, 0);
     cap = n_slots;
-    undo.r = nullptr;
+    undo.armed = false;
     return 0;
 }
 
@@ -2238,20 +2229,27 @@ static int probe_room(picles_ctx *c, long long n_steps, const char *who)
     return 0;
 }
 
-/* One sample into the next ring slot, on stream s — which the caller has ordered behind everything the sample depends on.  With a
- * fused step pending the values come from its records, with the arrays and reach indices flush() would hand k_scatter at this
- * point; otherwise from State.  Neither the pending step nor any plane of the model is touched; the host does not wait. */
+/* State of context c at n nodes (device list: the i plane, then the local-row plane) into 3 planes of n doubles at `out`, on stream
+ * s — which the caller has ordered behind everything the values depend on.  With a fused step pending they come from its records,
+ * with the arrays and reach indices flush() would hand k_scatter at this point; otherwise from State.  Neither the pending step
+ * nor any plane of the model is touched; the host does not wait.  Errors are reported on `err`: c, or the context whose call this is */
+static int probe_launch(picles_ctx *err, picles_ctx *c, hipStream_t s, int n, const int *nodes, double *out)
+{
+    const dim3 grid(nblocks(n, PROBE_BLOCK)), block(PROBE_BLOCK);
+    if (c->pending)
+        hipLaunchKernelGGL(k_probe<true>, grid, block, 0, s, c->G, arrays_for(c, c->cur, c->cur), n, nodes, out);
+    else
+        hipLaunchKernelGGL(k_probe<false>, grid, block, 0, s, c->G, c->A, n, nodes, out);
+    HIPCHK(err, hipGetLastError());
+    return 0;
+}
+
+/* one sample into the next ring slot */
 static int probe_take(picles_ctx *c, hipStream_t s)
 {
     unsigned char *slot = c->probe.next_slot();
     if (!slot) return fail(c, PICLES_PROBE_E_FULL, "probe ring full: picles_probe_pop first");
-    double *d = (double *)slot;
-    const dim3 grid(nblocks(c->probe_n, PROBE_BLOCK)), block(PROBE_BLOCK);
-    if (c->pending)
-        hipLaunchKernelGGL(k_probe<true>, grid, block, 0, s, c->G, arrays_for(c, c->cur, c->cur), c->probe_n, (const int *)c->probe_nodes, d);
-    else
-        hipLaunchKernelGGL(k_probe<false>, grid, block, 0, s, c->G, c->A, c->probe_n, (const int *)c->probe_nodes, d);
-    HIPCHK(c, hipGetLastError());
+    { int rc = probe_launch(c, c, s, c->probe_n, c->probe_nodes, (double *)slot); if (rc) return rc; }
     return c->probe.ship(c, slot, s, (size_t)3 * c->probe_n * sizeof(double), c->probe_cad.steps);
 }
 
@@ -2281,7 +2279,7 @@ PX_EXPORT int32_t picles_probe_init(picles_ctx *c, int32_t n, const int32_t *ij,
         loc[(size_t)n + k] = j - G.j_begin;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) probe_release(c); } } undo{c, true};
+    Undo undo{[c] { probe_release(c); }};
     { int rc = c->probe.init(c, capacity, (size_t)3 * n * sizeof(double)); if (rc) return rc; }
     HIPCHK(c, hipMalloc(&c->probe_nodes, (size_t)2 * n * sizeof(int)));
     HIPCHK(c, hipMemcpy(c->probe_nodes, loc.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice));     /* blocking: loc dies here */
@@ -2432,7 +2430,7 @@ PX_EXPORT int32_t picles_stat_init(picles_ctx *c, int32_t group_mask, int32_t n_
     S.nthr = n_thresholds;
     for (int k = 0; k < n_thresholds; k++) S.thr[k] = thresholds[k];
     const size_t bytes = (size_t)c->A.n * ((size_t)stat_nf64(S) * 8 + (size_t)stat_nu32(S) * 4);
-    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) stat_release(c); } } undo{c, true};
+    Undo undo{[c] { stat_release(c); }};
     { int rc = store_stream_get(c); if (rc) return rc; }
     HIPCHK(c, hipMalloc(&c->stat_dev, bytes));
     HIPCHK(c, hipEventCreateWithFlags(&c->stat_ev, hipEventDisableTiming));
@@ -2628,7 +2626,7 @@ static int bforce_init_any(picles_ctx *c, int32_t n, const int32_t *ij, const do
         if (mk == 1) ocean.push_back((int)t);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) bforce_release(c); } } undo{c, true};
+    Undo undo{[c] { bforce_release(c); }};
     HIPCHK(c, hipMalloc(&c->bf_nodes, (size_t)n * sizeof(int)));
     HIPCHK(c, hipMalloc(&c->bf_lv, (size_t)6 * n * sizeof(double)));
     HIPCHK(c, hipMemcpy(c->bf_nodes, loc.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));     /* blocking: loc dies here */
@@ -2703,12 +2701,7 @@ PX_EXPORT int32_t picles_bforce_free(picles_ctx *c)
     if (!c) return -1;
     if (!c->bf_n) return 0;
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->fb) { int rc = fb_release(c); if (rc) return rc; }                  /* a child's feedback goes before its nest */
-    if (c->nest) { int rc = nest_release(c, false); if (rc) return rc; }      /* the nest goes with the set it feeds */
-    if (c->fb_child) {      /* a fed parent: the feedback goes with the set; the child keeps its one-way nest */
-        HIPCHK(c, hipDeviceSynchronize());       /* a restrict in flight on the child's stream writes the level block */
-        fb_drop(c->fb_child);
-    }
+    { int rc = nest_leave_set(c); if (rc) return rc; }      /* a nest and a feedback go with the set they fill */
     { int rc = flush(c); if (rc) return rc; }      /* a pending step's forced records are scattered before they are emptied */
     HIPCHK(c, hipDeviceSynchronize());       /* launches in flight read the list and the levels about to go */
     hipLaunchKernelGGL(k_bforce_clear, dim3(nblocks(c->bf_n, 256)), dim3(256), 0, c->stream, c->G, c->rec_buf[0], c->rec_buf[1], c->A.on, c->A.status,
@@ -2731,9 +2724,8 @@ PX_EXPORT int32_t picles_bforce_get_levels(picles_ctx *c, double *v0, double *v1
     if ((v0 && c->bf_levels < 1) || (v1 && c->bf_levels < 2))
         return fail(c, -2, "picles_bforce_get_levels: the set holds " + std::to_string(c->bf_levels) + " level(s): pass NULL for a plane block it does not hold");
     HIPCHK(c, hipSetDevice(c->device));
-    /* behind whatever wrote the levels: a parent's mix (its event), an upload on the context stream.  No flush: a pending step stays pending */
-    if (c->nest) { int rc = nest_before_launch(c, c->stream); if (rc) return rc; }
-    if (c->fb_child) { int rc = fb_before_launch(c, c->stream); if (rc) return rc; }
+    /* behind whatever wrote the levels: another context's stencil (its event), an upload on the context stream.  No flush: a pending step stays pending */
+    { int rc = nest_levels_wait(c, c->stream); if (rc) return rc; }
     if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const size_t b = (size_t)3 * c->bf_n * sizeof(double);
@@ -2742,47 +2734,158 @@ PX_EXPORT int32_t picles_bforce_get_levels(picles_ctx *c, double *v0, double *v1
     return 0;
 }
 
-/* ---- one-way nesting (the contract: include/picles_hip.h "one-way nesting"; the mix kernel: k_nest.h) ----
- * A nested child's forcing set takes its time levels from a PARENT context on the same device: the parent's State at the distinct
- * corner nodes (k_probe, into `corner`), mixed onto the child's forced nodes (k_nest_mix) straight into one of three level slots.
- * Slots 0 and 1 are the set's own block (bf_lv, bf_lv + 3 n), slot 2 is the nest's; the pair the child reads is (slot[i0], slot[i1]),
- * rotated by pointer, and a sample writes the slot outside the pair.  Both kernels run on the PARENT's stream.  Events, both ways:
- *   ev_mix      recorded on the parent's stream behind k_nest_mix; the child's next launch that reads the levels waits for it
- *               (read after write: nest_before_launch)
- *   ev_read[k]  recorded on the child's stream when slot k leaves the pair, behind the last enqueued launch that read it; the
- *               parent's stream waits for it before the mix that overwrites slot k — a whole chunk of the child later, so the
- *               parent's step kernels, which sit in front of the sampling on its stream, never wait for the child's current chunk
- *               (write after read) */
-struct Nest {
-    picles_ctx *parent = nullptr;             /* nullptr: detached — the parent was destroyed; the levels stay */
-    int n_corner = 0;
-    int *corner_nodes = nullptr;              /* device: the i plane, then the row plane, of the parent's corner nodes */
-    double *corner = nullptr;                 /* device: 3 planes of n_corner doubles, the corner stage's output */
-    int *index = nullptr;                     /* device: 4 planes of bf_n */
-    double *weight = nullptr;                 /* device: 4 planes of bf_n */
-    double *extra = nullptr;                  /* device: slot 2 */
-    double *slot[3] = {nullptr, nullptr, nullptr};
-    int i0 = 0, i1 = 1;
-    hipEvent_t ev_mix = nullptr, ev_read[3] = {nullptr, nullptr, nullptr};
-    bool mix_unseen = false, read_live[3] = {false, false, false};
-    long long samples = 0;
+/* ---- nesting: one link behind both directions (the contract: include/picles_hip.h "one-way nesting" and "two-way nesting"; the
+ * stencil kernels: k_nest.h) ----
+ * A link carries the State of a SOURCE context onto the nodes of a TARGET context's forcing set, all on the device: the State at the
+ * distinct source nodes (k_probe, into the stencil's staging block), then per target node the weighted mean of its entries
+ * (k_nest_mix / k_nest_restrict) straight into one of the set's level slots.  Both kernels run on the SOURCE's stream; the target's
+ * k_bforce reads the slots on the TARGET's.
+ *   one-way (struct Nest)      source = parent, target = child.  Three slots: 0 and 1 are the set's own block (bf_lv, bf_lv + 3 n),
+ *                              2 is the nest's; the pair the child reads is (slot[i0], slot[i1]), rotated by pointer, and a sample
+ *                              writes the slot outside the pair
+ *   two-way (struct Feedback)  source = child, target = parent.  The set's own two slots, used alternately; the parent reads one
+ *                              level, its bf_v0 switched by pointer
+ * ORDERING: two rules, kept by one SlotSync per link.
+ *   read after write   `written` is recorded on the source's stream behind the stencil kernel (published); the target's next launch
+ *                      that reads the levels, and picles_bforce_get_levels, wait for it (wait_written).  k_bforce sits behind the
+ *                      target's step kernel on its stream, so that kernel still overlaps the source's work
+ *   write after read   read[k] is recorded on the target's stream behind a launch that read slot k (mark_read); the source's stream
+ *                      waits for it before the stencil that overwrites slot k (claim)
+ *   one-way marks a slot once, when it leaves the pair — in picles_nest_sample, behind the last enqueued launch that read it, and at
+ *   init for slots 0 and 1, which launches enqueued under uploaded levels may still read: no runtime call in a child step, and the
+ *   wait lies a whole chunk of the child back, so the parent's step kernels, in front of the sampling on its stream, never wait for
+ *   the child's current chunk.  Two-way marks behind every k_bforce of the parent (nest_levels_read); with two slots the launch
+ *   waited for belongs to the parent step before last: never current work */
+struct SlotSync {
+    hipEvent_t written = nullptr, read[3] = {nullptr, nullptr, nullptr};
+    bool unseen = false, live[3] = {false, false, false};
+    int create(picles_ctx *c, int n_slots)
+    {
+        HIPCHK(c, hipEventCreateWithFlags(&written, hipEventDisableTiming));
+        for (int k = 0; k < n_slots; k++) HIPCHK(c, hipEventCreateWithFlags(&read[k], hipEventDisableTiming));
+        return 0;
+    }
+    void destroy() { for (hipEvent_t e : {written, read[0], read[1], read[2]}) if (e) hipEventDestroy(e); }
+    void forget() { unseen = live[0] = live[1] = live[2] = false; }
+    /* the target's stream s is about to read the levels.  own: s is its context stream, which every later launch of it follows */
+    int wait_written(picles_ctx *c, hipStream_t s, bool own)
+    {
+        if (unseen) { HIPCHK(c, hipStreamWaitEvent(s, written, 0)); unseen = !own; }
+        return 0;
+    }
+    int mark_read(picles_ctx *c, int k, hipStream_t s) { HIPCHK(c, hipEventRecord(read[k], s)); live[k] = true; return 0; }
+    int claim(picles_ctx *c, int k, hipStream_t s)
+    {
+        if (live[k]) { HIPCHK(c, hipStreamWaitEvent(s, read[k], 0)); live[k] = false; }
+        return 0;
+    }
+    int published(picles_ctx *c, hipStream_t s) { HIPCHK(c, hipEventRecord(written, s)); unseen = true; return 0; }
 };
 
-/* the child's stream s is about to read the levels: behind the parent's latest mix */
-static int nest_before_launch(picles_ctx *c, hipStream_t s)
+/* the words and the rules in which the stencils of the two directions differ */
+struct StencilRules {
+    const char *who, *source, *entry, *grid, *count;
+    bool padded;      /* weights are >= 0, 0.0 marks padding, a node needs an entry that is none: k_nest_restrict; else four entries, k_nest_mix */
+};
+static const StencilRules NEST_RULES = {"picles_nest_init", "corner", "corner", "the parent's grid", "n_corner", false};
+static const StencilRules FEEDBACK_RULES = {"picles_nest_feedback_init", "source node", "entry", "the child's grid", "n_src", true};
+
+/* G: the source's grid (a whole grid: its local rows are the global ones) */
+static int stencil_check(picles_ctx *c, const StencilRules &R, const GridP &G, int n_out, int n_src, int m, const int32_t *src_ij, const int32_t *index,
+                         const double *weight)
 {
-    Nest *N = c->nest;
-    if (!N->mix_unseen) return 0;
-    HIPCHK(c, hipStreamWaitEvent(s, N->ev_mix, 0));
-    if (s == c->stream) N->mix_unseen = false;
+    const std::string who = std::string(R.who) + ": ";
+    for (int k = 0; k < n_src; k++) {
+        const int i = src_ij[k], j = src_ij[(size_t)n_src + k];
+        if (i < 0 || i >= G.Nx || j < 0 || j >= G.Ny)
+            return fail(c, -2, who + R.source + " " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) + ") lies outside " + R.grid +
+                               " [0, " + std::to_string(G.Nx) + ") x [0, " + std::to_string(G.Ny) + ")");
+    }
+    std::vector<unsigned char> any((size_t)n_out, 0);
+    for (size_t k = 0; k < (size_t)m * n_out; k++) {
+        auto at = [&] { return "node " + std::to_string(k % n_out) + ", " + R.entry + " " + std::to_string(k / n_out); };
+        if (index[k] < 0 || index[k] >= n_src)
+            return fail(c, -2, who + "index " + std::to_string(index[k]) + " of " + at() + ", lies outside [0, " + R.count + " = " + std::to_string(n_src) + ")");
+        if (!std::isfinite(weight[k]) || (R.padded && weight[k] < 0.0))
+            return fail(c, -2, who + "the weight of " + at() + (R.padded ? ", is not finite or is negative" : ", is not finite"));
+        if (weight[k] > 0.0) any[k % n_out] = 1;
+    }
+    for (int k = 0; R.padded && k < n_out; k++)
+        if (!any[(size_t)k]) return fail(c, -2, who + "every weight of node " + std::to_string(k) + " is zero: it has no source");
     return 0;
 }
 
-static void nest_detach_children(picles_ctx *c)
+struct NestStencil {
+    int n_out = 0, n_src = 0, m = 0;
+    bool padded = false;
+    int *src_nodes = nullptr;                 /* device: the i plane, then the row plane, of the source nodes */
+    double *src = nullptr;                    /* device: 3 planes of n_src doubles, the staging block k_probe fills */
+    int *index = nullptr;                     /* device: m planes of n_out */
+    double *weight = nullptr;                 /* device: m planes of n_out */
+    /* checked arrays (stencil_check) onto the device; blocking copies: the caller's arrays are free on return */
+    int upload(picles_ctx *c, const StencilRules &R, int n_out_, int n_src_, int m_, const int32_t *src_ij, const int32_t *ix, const double *w)
+    {
+        n_out = n_out_; n_src = n_src_; m = m_; padded = R.padded;
+        const size_t e = (size_t)m * n_out;
+        HIPCHK(c, hipMalloc(&src_nodes, (size_t)2 * n_src * sizeof(int)));
+        HIPCHK(c, hipMalloc(&src, (size_t)3 * n_src * sizeof(double)));
+        HIPCHK(c, hipMalloc(&index, e * sizeof(int)));
+        HIPCHK(c, hipMalloc(&weight, e * sizeof(double)));
+        HIPCHK(c, hipMemcpy(src_nodes, src_ij, (size_t)2 * n_src * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(index, ix, e * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(weight, w, e * sizeof(double), hipMemcpyHostToDevice));
+        return 0;
+    }
+    void release() { for (void *q : {(void *)src_nodes, (void *)src, (void *)index, (void *)weight}) if (q) hipFree(q); }
+    /* one level into `out` (3 planes of n_out) on stream s: the State of `from` as that stream finds it — probe_launch's choice: from
+     * the records of a pending fused step, which stays pending, or from State.  Errors are reported on c, the child */
+    int run(picles_ctx *c, picles_ctx *from, hipStream_t s, double *out) const
+    {
+        { int rc = probe_launch(c, from, s, n_src, src_nodes, src); if (rc) return rc; }
+        const dim3 grid(nblocks(n_out, NEST_BLOCK)), block(NEST_BLOCK);
+        if (padded)
+            hipLaunchKernelGGL(k_nest_restrict, grid, block, 0, s, n_out, n_src, m, (const int *)index, (const double *)weight, (const double *)src, out);
+        else
+            hipLaunchKernelGGL(k_nest_mix, grid, block, 0, s, n_out, n_src, (const int *)index, (const double *)weight, (const double *)src, out);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+    }
+};
+
+struct Nest {
+    picles_ctx *parent = nullptr;             /* nullptr: detached — the parent was destroyed; the levels stay */
+    NestStencil st;                           /* the parent's corner nodes onto the child's forced nodes, four corners each */
+    SlotSync sync;
+    double *extra = nullptr;                  /* device: slot 2 */
+    double *slot[3] = {nullptr, nullptr, nullptr};
+    int i0 = 0, i1 = 1;
+    long long samples = 0;
+};
+struct Feedback {
+    picles_ctx *parent = nullptr;             /* nullptr: detached — the parent was destroyed, and the slots with its set */
+    NestStencil st;                           /* the child's source nodes onto the parent's feedback nodes, m entries each */
+    SlotSync sync;
+    double *slot[2] = {nullptr, nullptr};     /* the parent's bf_lv and bf_lv + 3 n_fb */
+    int cur = 1;                              /* the slot the parent reads (the first feedback writes slot 0) */
+    long long taken = 0;
+};
+
+/* stream s of context c is about to read c's levels: behind the latest stencil of whoever writes them */
+static int nest_levels_wait(picles_ctx *c, hipStream_t s)
 {
-    for (picles_ctx *k : c->nest_children)
-        if (k->nest) k->nest->parent = nullptr;
-    c->nest_children.clear();
+    if (c->nest) { int rc = c->nest->sync.wait_written(c, s, s == c->stream); if (rc) return rc; }
+    if (c->fb_child) return c->fb_child->fb->sync.wait_written(c, s, s == c->stream);
+    return 0;
+}
+
+/* a launch on stream s of context c has been enqueued that reads the level at `read`: a fed parent marks the slot */
+static int nest_levels_read(picles_ctx *c, hipStream_t s, const double *read)
+{
+    if (!c->fb_child) return 0;
+    Feedback *F = c->fb_child->fb;
+    for (int k = 0; k < 2; k++)
+        if (read == F->slot[k]) { int rc = F->sync.mark_read(c, k, s); if (rc) return rc; }
+    return 0;
 }
 
 /* drop the nest of c.  keep_levels: the pair the set holds moves home to (bf_lv, bf_lv + 3 n), where a set without a nest keeps it */
@@ -2802,18 +2905,75 @@ static int nest_release(picles_ctx *c, bool keep_levels)
         auto &v = N->parent->nest_children;
         v.erase(std::remove(v.begin(), v.end(), c), v.end());
     }
-    if (N->corner_nodes) hipFree(N->corner_nodes);
-    if (N->corner) hipFree(N->corner);
-    if (N->index) hipFree(N->index);
-    if (N->weight) hipFree(N->weight);
+    N->st.release();
     if (N->extra) hipFree(N->extra);
-    if (N->ev_mix) hipEventDestroy(N->ev_mix);
-    for (int k = 0; k < 3; k++) if (N->ev_read[k]) hipEventDestroy(N->ev_read[k]);
+    N->sync.destroy();
     delete N;
     c->nest = nullptr;
     c->bf_v0 = c->bf_lv;
     c->bf_v1 = c->bf_lv ? c->bf_lv + n3 : nullptr;
     return 0;
+}
+
+/* free the child's feedback blocks and cut both links; the parent's set is the caller's business (nothing of it is touched).
+ * The caller has drained the device where work may be in flight */
+static void fb_drop(picles_ctx *c)
+{
+    Feedback *F = c->fb;
+    if (!F) return;
+    if (F->parent) F->parent->fb_child = nullptr;
+    F->st.release();
+    F->sync.destroy();
+    delete F;
+    c->fb = nullptr;
+}
+
+/* drop the feedback of child c and, where the parent lives, the set it made there (its nodes go back to the parent's step kernels:
+ * picles_bforce_free restores the flags through context_pflags) */
+static int fb_release(picles_ctx *c)
+{
+    if (!c->fb) return 0;
+    picles_ctx *p = c->fb->parent;
+    HIPCHK(c, hipDeviceSynchronize());       /* a restrict in flight writes the parent's slots, the parent's launches read them */
+    fb_drop(c);
+    if (p) {
+        int rc = picles_bforce_free(p);
+        if (rc) return fail(c, rc, "picles_nest_feedback_free: the parent's set: " + p->err);
+    }
+    return 0;
+}
+
+/* picles_bforce_free(c): a nest and a feedback go with the set they fill */
+static int nest_leave_set(picles_ctx *c)
+{
+    if (c->fb) { int rc = fb_release(c); if (rc) return rc; }                  /* a child's feedback goes before its nest */
+    if (c->nest) { int rc = nest_release(c, false); if (rc) return rc; }      /* the nest goes with the set it feeds */
+    if (c->fb_child) {      /* a fed parent: the feedback goes with the set; the child keeps its one-way nest */
+        HIPCHK(c, hipDeviceSynchronize());       /* a restrict in flight on the child's stream writes the level block */
+        fb_drop(c->fb_child);
+    }
+    return 0;
+}
+
+/* picles_destroy(c), its streams drained.  As a parent: the children keep their last levels and lose their parent (no mix is in
+ * flight); a child that feeds c keeps its Feedback, without a parent and without slots (picles_nest_feedback then fails with a
+ * text) and its one-way nest — its stream is drained first: a restrict in flight writes c's level block.  As a child: the feedback
+ * goes, and with it the set it made on the parent; then the nest, which leaves the parent's list before its blocks go */
+static void nest_leave_context(picles_ctx *c)
+{
+    for (picles_ctx *k : c->nest_children)
+        if (k->nest) k->nest->parent = nullptr;
+    c->nest_children.clear();
+    if (c->fb) fb_release(c);
+    if (c->fb_child) {
+        hipDeviceSynchronize();
+        Feedback *F = c->fb_child->fb;
+        F->parent = nullptr;
+        F->slot[0] = F->slot[1] = nullptr;
+        F->sync.forget();
+        c->fb_child = nullptr;
+    }
+    if (c->nest) nest_release(c, false);
 }
 
 static const char *const NEST_NO_EXT_STREAMS = ": a context that has run on caller-provided streams cannot be ordered by the nest's events: "
@@ -2835,37 +2995,16 @@ PX_EXPORT int32_t picles_nest_init(picles_ctx *c, picles_ctx *p, int32_t n_corne
     if (n_corner < 1 || !corner_ij || !index || !weight)
         return fail(c, -2, "picles_nest_init: n_corner must be >= 1 and corner_ij, index and weight given");
     const int n = c->bf_n;
-    for (int k = 0; k < n_corner; k++) {
-        const int i = corner_ij[k], j = corner_ij[(size_t)n_corner + k];
-        if (i < 0 || i >= p->G.Nx || j < 0 || j >= p->G.Ny)
-            return fail(c, -2, "picles_nest_init: corner " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) +
-                               ") lies outside the parent's grid [0, " + std::to_string(p->G.Nx) + ") x [0, " + std::to_string(p->G.Ny) + ")");
-    }
-    for (size_t k = 0; k < (size_t)4 * n; k++) {
-        if (index[k] < 0 || index[k] >= n_corner)
-            return fail(c, -2, "picles_nest_init: index " + std::to_string(index[k]) + " of node " + std::to_string(k % n) + ", corner " + std::to_string(k / n) +
-                               ", lies outside [0, n_corner = " + std::to_string(n_corner) + ")");
-        if (!std::isfinite(weight[k]))
-            return fail(c, -2, "picles_nest_init: the weight of node " + std::to_string(k % n) + ", corner " + std::to_string(k / n) + ", is not finite");
-    }
+    { int rc = stencil_check(c, NEST_RULES, p->G, n, n_corner, 4, corner_ij, index, weight); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     Nest *N = new Nest;
     c->nest = N;                              /* (no parent yet: a failure below releases without touching p) */
-    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) nest_release(c, true); } } undo{c, true};
-    HIPCHK(c, hipMalloc(&N->corner_nodes, (size_t)2 * n_corner * sizeof(int)));
-    HIPCHK(c, hipMalloc(&N->corner, (size_t)3 * n_corner * sizeof(double)));
-    HIPCHK(c, hipMalloc(&N->index, (size_t)4 * n * sizeof(int)));
-    HIPCHK(c, hipMalloc(&N->weight, (size_t)4 * n * sizeof(double)));
+    Undo undo{[c] { nest_release(c, true); }};
+    { int rc = N->st.upload(c, NEST_RULES, n, n_corner, 4, corner_ij, index, weight); if (rc) return rc; }
     HIPCHK(c, hipMalloc(&N->extra, (size_t)3 * n * sizeof(double)));
-    HIPCHK(c, hipEventCreateWithFlags(&N->ev_mix, hipEventDisableTiming));
-    for (int k = 0; k < 3; k++) HIPCHK(c, hipEventCreateWithFlags(&N->ev_read[k], hipEventDisableTiming));
-    /* blocking copies: the caller's arrays are free on return (the parent is a whole grid: its local rows are the global ones) */
-    HIPCHK(c, hipMemcpy(N->corner_nodes, corner_ij, (size_t)2 * n_corner * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(N->index, index, (size_t)4 * n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(N->weight, weight, (size_t)4 * n * sizeof(double), hipMemcpyHostToDevice));
+    { int rc = N->sync.create(c, 3); if (rc) return rc; }
     /* launches of the child enqueued under uploaded levels may still read slots 0 and 1 */
-    for (int k = 0; k < 2; k++) { HIPCHK(c, hipEventRecord(N->ev_read[k], c->stream)); N->read_live[k] = true; }
-    N->n_corner = n_corner;
+    for (int k = 0; k < 2; k++) { int rc = N->sync.mark_read(c, k, c->stream); if (rc) return rc; }
     N->slot[0] = c->bf_lv;
     N->slot[1] = c->bf_lv + (size_t)3 * n;
     N->slot[2] = N->extra;
@@ -2900,24 +3039,13 @@ PX_EXPORT int32_t picles_nest_sample(picles_ctx *c)
     if (c->bf_levels == 0) w = N->i0;
     else if (c->bf_levels == 1) w = N->i1;
     else {
-        HIPCHK(c, hipEventRecord(N->ev_read[N->i0], c->stream));
-        N->read_live[N->i0] = true;
+        { int rc = N->sync.mark_read(c, N->i0, c->stream); if (rc) return rc; }
         w = 3 - N->i0 - N->i1;
     }
     hipStream_t s = p->stream;
-    if (N->read_live[w]) { HIPCHK(c, hipStreamWaitEvent(s, N->ev_read[w], 0)); N->read_live[w] = false; }      /* write after read */
-    /* the corner stage: probe_take's choice — from the records of the parent's pending fused step, which stays pending, or from State */
-    const dim3 cgrid(nblocks(N->n_corner, PROBE_BLOCK)), cblock(PROBE_BLOCK);
-    if (p->pending)
-        hipLaunchKernelGGL(k_probe<true>, cgrid, cblock, 0, s, p->G, arrays_for(p, p->cur, p->cur), N->n_corner, (const int *)N->corner_nodes, N->corner);
-    else
-        hipLaunchKernelGGL(k_probe<false>, cgrid, cblock, 0, s, p->G, p->A, N->n_corner, (const int *)N->corner_nodes, N->corner);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_nest_mix, dim3(nblocks(c->bf_n, NEST_BLOCK)), dim3(NEST_BLOCK), 0, s, c->bf_n, N->n_corner, (const int *)N->index,
-                       (const double *)N->weight, (const double *)N->corner, N->slot[w]);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(N->ev_mix, s));      /* read after write: nest_before_launch */
-    N->mix_unseen = true;
+    { int rc = N->sync.claim(c, w, s); if (rc) return rc; }
+    { int rc = N->st.run(c, p, s, N->slot[w]); if (rc) return rc; }
+    { int rc = N->sync.published(c, s); if (rc) return rc; }
     if (c->bf_levels == 0) {
         c->bf_levels = 1;
         c->bf_t0 = c->bf_t1 = p->clock;
@@ -2936,7 +3064,7 @@ PX_EXPORT int32_t picles_nest_sample(picles_ctx *c)
 PX_EXPORT int32_t picles_nest_info(const picles_ctx *c, int32_t *n_corner, int64_t *samples)
 {
     if (!c || !c->nest) return -1;
-    if (n_corner) *n_corner = c->nest->n_corner;
+    if (n_corner) *n_corner = c->nest->st.n_src;
     if (samples) *samples = c->nest->samples;
     return 0;
 }
@@ -2948,95 +3076,6 @@ PX_EXPORT int32_t picles_nest_free(picles_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     if (c->fb) { int rc = fb_release(c); if (rc) return rc; }      /* the feedback lives on the nest */
     return nest_release(c, true);
-}
-
-/* ---- two-way nesting (the contract: include/picles_hip.h "two-way nesting"; the restrict kernel: k_nest.h) ----
- * A nested child feeds its State back: the PARENT carries a forcing set of ocean nodes (bforce_init_any, BF_FEEDBACK) whose one
- * level is the child's State restricted onto them — the child's State at the distinct source nodes (k_probe, into `src`), restricted
- * (k_nest_restrict) straight into one of the set's own two slots (bf_lv, bf_lv + 3 n), used alternately; the parent's bf_v0 is
- * switched by pointer.  Both kernels run on the CHILD's stream.  Events, both ways:
- *   ev_restrict  recorded on the child's stream behind k_nest_restrict; the parent's next k_bforce (and picles_bforce_get_levels)
- *                waits for it (read after write: fb_before_launch) — k_bforce sits behind the parent's step kernel on its stream,
- *                so that kernel still overlaps the child's chunk
- *   ev_read[k]   recorded on the parent's stream behind every k_bforce that read slot k (fb_after_launch); the child's stream waits
- *                for it before the restrict that overwrites slot k.  With two slots that launch belongs to the parent step before
- *                last: never current work (write after read) */
-struct Feedback {
-    picles_ctx *parent = nullptr;             /* nullptr: detached — the parent was destroyed */
-    int n_fb = 0, n_src = 0, m = 0;
-    int *src_nodes = nullptr;                 /* device: the i plane, then the row plane, of the child's source nodes */
-    double *src = nullptr;                    /* device: 3 planes of n_src doubles, the source stage's output */
-    int *index = nullptr;                     /* device: m planes of n_fb */
-    double *weight = nullptr;                 /* device: m planes of n_fb */
-    double *slot[2] = {nullptr, nullptr};     /* the parent's bf_lv and bf_lv + 3 n_fb */
-    int cur = 1;                              /* the slot the parent reads (the first feedback writes slot 0) */
-    hipEvent_t ev_restrict = nullptr, ev_read[2] = {nullptr, nullptr};
-    bool restrict_unseen = false, read_live[2] = {false, false};
-    long long taken = 0;
-};
-
-/* the parent's stream s is about to read the level: behind the child's latest restrict */
-static int fb_before_launch(picles_ctx *p, hipStream_t s)
-{
-    Feedback *F = p->fb_child->fb;
-    if (!F->restrict_unseen) return 0;
-    HIPCHK(p, hipStreamWaitEvent(s, F->ev_restrict, 0));
-    if (s == p->stream) F->restrict_unseen = false;
-    return 0;
-}
-
-/* a launch on the parent's stream s has been enqueued that reads the level at `read` */
-static int fb_after_launch(picles_ctx *p, hipStream_t s, const double *read)
-{
-    Feedback *F = p->fb_child->fb;
-    for (int k = 0; k < 2; k++)
-        if (read == F->slot[k]) {
-            HIPCHK(p, hipEventRecord(F->ev_read[k], s));
-            F->read_live[k] = true;
-        }
-    return 0;
-}
-
-/* free the child's feedback blocks and cut both links; the parent's set is the caller's business (nothing of it is touched).
- * The caller has drained the device where work may be in flight */
-static void fb_drop(picles_ctx *c)
-{
-    Feedback *F = c->fb;
-    if (!F) return;
-    if (F->parent) F->parent->fb_child = nullptr;
-    if (F->src_nodes) hipFree(F->src_nodes);
-    if (F->src) hipFree(F->src);
-    if (F->index) hipFree(F->index);
-    if (F->weight) hipFree(F->weight);
-    if (F->ev_restrict) hipEventDestroy(F->ev_restrict);
-    for (int k = 0; k < 2; k++) if (F->ev_read[k]) hipEventDestroy(F->ev_read[k]);
-    delete F;
-    c->fb = nullptr;
-}
-
-/* the parent p goes: the child keeps its Feedback, without a parent and without slots (picles_nest_feedback then fails with a text) */
-static void fb_detach(picles_ctx *p)
-{
-    Feedback *F = p->fb_child->fb;
-    F->parent = nullptr;
-    F->slot[0] = F->slot[1] = nullptr;
-    F->restrict_unseen = F->read_live[0] = F->read_live[1] = false;
-    p->fb_child = nullptr;
-}
-
-/* drop the feedback of child c and, where the parent lives, the set it made there (its nodes go back to the parent's step kernels:
- * picles_bforce_free restores the flags through context_pflags) */
-static int fb_release(picles_ctx *c)
-{
-    if (!c->fb) return 0;
-    picles_ctx *p = c->fb->parent;
-    HIPCHK(c, hipDeviceSynchronize());       /* a restrict in flight writes the parent's slots, the parent's launches read them */
-    fb_drop(c);
-    if (p) {
-        int rc = picles_bforce_free(p);
-        if (rc) return fail(c, rc, "picles_nest_feedback_free: the parent's set: " + p->err);
-    }
-    return 0;
 }
 
 PX_EXPORT int32_t picles_nest_feedback_init(picles_ctx *c, int32_t n_fb, const int32_t *fb_ij, int32_t n_src, const int32_t *src_ij, int32_t m,
@@ -3056,40 +3095,13 @@ PX_EXPORT int32_t picles_nest_feedback_init(picles_ctx *c, int32_t n_fb, const i
     if (n_fb < 1 || !fb_ij) return fail(c, -2, "picles_nest_feedback_init: n_fb must be >= 1 and fb_ij given");
     if (n_src < 1 || m < 1 || !src_ij || !index || !weight)
         return fail(c, -2, "picles_nest_feedback_init: n_src and m must be >= 1 and src_ij, index and weight given");
-    for (int k = 0; k < n_src; k++) {
-        const int i = src_ij[k], j = src_ij[(size_t)n_src + k];
-        if (i < 0 || i >= c->G.Nx || j < 0 || j >= c->G.Ny)
-            return fail(c, -2, "picles_nest_feedback_init: source node " + std::to_string(k) + " = (" + std::to_string(i) + ", " + std::to_string(j) +
-                               ") lies outside the child's grid [0, " + std::to_string(c->G.Nx) + ") x [0, " + std::to_string(c->G.Ny) + ")");
-    }
-    {
-        std::vector<unsigned char> any((size_t)n_fb, 0);
-        for (size_t k = 0; k < (size_t)m * n_fb; k++) {
-            const std::string at = "node " + std::to_string(k % n_fb) + ", entry " + std::to_string(k / n_fb);
-            if (index[k] < 0 || index[k] >= n_src)
-                return fail(c, -2, "picles_nest_feedback_init: index " + std::to_string(index[k]) + " of " + at + ", lies outside [0, n_src = " +
-                                   std::to_string(n_src) + ")");
-            if (!std::isfinite(weight[k]) || weight[k] < 0.0)
-                return fail(c, -2, "picles_nest_feedback_init: the weight of " + at + ", is not finite or is negative");
-            if (weight[k] > 0.0) any[k % n_fb] = 1;
-        }
-        for (int k = 0; k < n_fb; k++)
-            if (!any[(size_t)k]) return fail(c, -2, "picles_nest_feedback_init: every weight of node " + std::to_string(k) + " is zero: it has no source");
-    }
+    { int rc = stencil_check(c, FEEDBACK_RULES, c->G, n_fb, n_src, m, src_ij, index, weight); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
     Feedback *F = new Feedback;
     c->fb = F;                                /* (no parent yet: a failure below drops without touching p) */
-    struct Undo { picles_ctx *c; bool armed; ~Undo() { if (armed) fb_drop(c); } } undo{c, true};
-    HIPCHK(c, hipMalloc(&F->src_nodes, (size_t)2 * n_src * sizeof(int)));
-    HIPCHK(c, hipMalloc(&F->src, (size_t)3 * n_src * sizeof(double)));
-    HIPCHK(c, hipMalloc(&F->index, (size_t)m * n_fb * sizeof(int)));
-    HIPCHK(c, hipMalloc(&F->weight, (size_t)m * n_fb * sizeof(double)));
-    HIPCHK(c, hipEventCreateWithFlags(&F->ev_restrict, hipEventDisableTiming));
-    for (int k = 0; k < 2; k++) HIPCHK(c, hipEventCreateWithFlags(&F->ev_read[k], hipEventDisableTiming));
-    /* blocking copies: the caller's arrays are free on return (the child is a whole grid: its local rows are the global ones) */
-    HIPCHK(c, hipMemcpy(F->src_nodes, src_ij, (size_t)2 * n_src * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(F->index, index, (size_t)m * n_fb * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(F->weight, weight, (size_t)m * n_fb * sizeof(double), hipMemcpyHostToDevice));
+    Undo undo{[c] { fb_drop(c); }};
+    { int rc = F->st.upload(c, FEEDBACK_RULES, n_fb, n_src, m, src_ij, index, weight); if (rc) return rc; }
+    { int rc = F->sync.create(c, 2); if (rc) return rc; }
     /* the parent's set, last: what it refuses (a node off the grid, given twice or not of class 1; a tripolar grid) leaves both contexts as they were */
     {
         const std::string keep = p->err;
@@ -3100,9 +3112,6 @@ PX_EXPORT int32_t picles_nest_feedback_init(picles_ctx *c, int32_t n_fb, const i
             return fail(c, rc, why);
         }
     }
-    F->n_fb = n_fb;
-    F->n_src = n_src;
-    F->m = m;
     F->slot[0] = p->bf_lv;
     F->slot[1] = p->bf_lv + (size_t)3 * n_fb;
     F->parent = p;
@@ -3129,19 +3138,9 @@ PX_EXPORT int32_t picles_nest_feedback(picles_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     const int w = 1 - F->cur;
     hipStream_t s = c->stream;
-    if (F->read_live[w]) { HIPCHK(c, hipStreamWaitEvent(s, F->ev_read[w], 0)); F->read_live[w] = false; }      /* write after read */
-    /* the source stage: probe_take's choice — from the records of the child's pending fused step, which stays pending, or from State */
-    const dim3 sgrid(nblocks(F->n_src, PROBE_BLOCK)), sblock(PROBE_BLOCK);
-    if (c->pending)
-        hipLaunchKernelGGL(k_probe<true>, sgrid, sblock, 0, s, c->G, arrays_for(c, c->cur, c->cur), F->n_src, (const int *)F->src_nodes, F->src);
-    else
-        hipLaunchKernelGGL(k_probe<false>, sgrid, sblock, 0, s, c->G, c->A, F->n_src, (const int *)F->src_nodes, F->src);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_nest_restrict, dim3(nblocks(F->n_fb, NEST_BLOCK)), dim3(NEST_BLOCK), 0, s, F->n_fb, F->n_src, F->m, (const int *)F->index,
-                       (const double *)F->weight, (const double *)F->src, F->slot[w]);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(F->ev_restrict, s));      /* read after write: fb_before_launch */
-    F->restrict_unseen = true;
+    { int rc = F->sync.claim(c, w, s); if (rc) return rc; }
+    { int rc = F->st.run(c, c, s, F->slot[w]); if (rc) return rc; }
+    { int rc = F->sync.published(c, s); if (rc) return rc; }
     F->cur = w;
     F->taken++;
     p->bf_v0 = F->slot[w];
@@ -3153,9 +3152,9 @@ PX_EXPORT int32_t picles_nest_feedback(picles_ctx *c)
 PX_EXPORT int32_t picles_nest_feedback_info(const picles_ctx *c, int32_t *n_fb, int32_t *n_src, int32_t *m, int64_t *taken)
 {
     if (!c || !c->fb) return -1;
-    if (n_fb) *n_fb = c->fb->n_fb;
-    if (n_src) *n_src = c->fb->n_src;
-    if (m) *m = c->fb->m;
+    if (n_fb) *n_fb = c->fb->st.n_out;
+    if (n_src) *n_src = c->fb->st.n_src;
+    if (m) *m = c->fb->st.m;
     if (taken) *taken = c->fb->taken;
     return 0;
 }

@@ -30,6 +30,21 @@ def _col(a, n):
     return a
 
 
+def _int32_planes(a, who, what="index", pairs=False):
+    """an integer array, nodes or stencil rows along axis 0 -> its columns as contiguous int32 planes, the layout of the C ABI's
+    node lists and stencils; pairs: the array must be (n, 2), a list of (i, j)"""
+    a = np.asarray(a, dtype=np.int64)
+    if pairs and (a.ndim != 2 or a.shape[1] != 2):
+        raise ValueError(f"{who}: nodes must be an (n, 2) array of (i, j)")
+    if a.size and np.abs(a).max() > 2**31 - 1:
+        raise ValueError(f"{who}: {what} out of the int32 range")
+    return np.ascontiguousarray(a.T.astype(np.int32))
+
+
+def _p32(planes):
+    return planes.ctypes.data_as(K.c_int32_p)
+
+
 def diag_field_mask(fields) -> int:
     """field names (or a ready bit mask) -> PICLES_DIAG_* bit mask"""
     if isinstance(fields, (int, np.integer)):
@@ -564,30 +579,19 @@ class HipModel:
         With weights the call is bforce_init_band's (ocean nodes are taken there too)"""
         if weights is not None:
             return self.bforce_init_band(nodes, weights)
-        ij = np.asarray(nodes, dtype=np.int64)
-        if ij.ndim != 2 or ij.shape[1] != 2:
-            raise ValueError("bforce_init: nodes must be an (n, 2) array of (i, j)")
-        if ij.size and (np.abs(ij).max() > 2**31 - 1):
-            raise ValueError("bforce_init: node index out of the int32 range")
-        planes = np.ascontiguousarray(ij.T.astype(np.int32))
-        self._ck(self.lib.picles_bforce_init(self.h, int(ij.shape[0]), planes.ctypes.data_as(K.c_int32_p)), "picles_bforce_init")
+        planes = _int32_planes(nodes, "bforce_init", "node index", pairs=True)
+        self._ck(self.lib.picles_bforce_init(self.h, planes.shape[1], _p32(planes)), "picles_bforce_init")
 
     def bforce_init_band(self, nodes, weights=None):
         """a band set: nodes as for bforce_init, of mask class 3 or 1 (ocean: not stepped while the set lives); weights: None
         (every node 1.0) or n values in (0, 1] — the prescribed value is blended into the model's own State, v = m + w (p - m)"""
-        ij = np.asarray(nodes, dtype=np.int64)
-        if ij.ndim != 2 or ij.shape[1] != 2:
-            raise ValueError("bforce_init_band: nodes must be an (n, 2) array of (i, j)")
-        if ij.size and (np.abs(ij).max() > 2**31 - 1):
-            raise ValueError("bforce_init_band: node index out of the int32 range")
-        w = None
+        planes = _int32_planes(nodes, "bforce_init_band", "node index", pairs=True)
+        n, w = planes.shape[1], None
         if weights is not None:
             w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
-            if w.shape != (ij.shape[0],):
-                raise ValueError(f"bforce_init_band: expected {ij.shape[0]} weights, got {w.shape[0]}")
-        planes = np.ascontiguousarray(ij.T.astype(np.int32))
-        self._ck(self.lib.picles_bforce_init_band(self.h, int(ij.shape[0]), planes.ctypes.data_as(K.c_int32_p), K.dptr(w)),
-                 "picles_bforce_init_band")
+            if w.shape != (n,):
+                raise ValueError(f"bforce_init_band: expected {n} weights, got {w.shape[0]}")
+        self._ck(self.lib.picles_bforce_init_band(self.h, n, _p32(planes), K.dptr(w)), "picles_bforce_init_band")
 
     def bforce_set_levels(self, t0, v0, t1=None, v1=None):
         """v0 (and v1): (n, 3) values (e, m_x, m_y) per forced node at t0 (and t1 > t0); one level: constant in time"""
@@ -641,13 +645,8 @@ class HipModel:
             pad = 4 - ix.shape[1]
             ix = np.concatenate([ix, np.repeat(ix[:, :1], pad, axis=1)], axis=1)
             w = np.concatenate([w, np.zeros((n, pad))], axis=1)
-        if (cn.size and np.abs(cn).max() > 2**31 - 1) or np.abs(ix).max() > 2**31 - 1:
-            raise ValueError("nest_init: index out of the int32 range")
-        cplanes = np.ascontiguousarray(cn.T.astype(np.int32))
-        iplanes = np.ascontiguousarray(ix.T.astype(np.int32))
-        wplanes = np.ascontiguousarray(w.T)
-        self._ck(self.lib.picles_nest_init(self.h, ph, int(cn.shape[0]), cplanes.ctypes.data_as(K.c_int32_p),
-                                           iplanes.ctypes.data_as(K.c_int32_p), K.dptr(wplanes)), "picles_nest_init")
+        cplanes, iplanes, wplanes = _int32_planes(cn, "nest_init"), _int32_planes(ix, "nest_init"), np.ascontiguousarray(w.T)
+        self._ck(self.lib.picles_nest_init(self.h, ph, cplanes.shape[1], _p32(cplanes), _p32(iplanes), K.dptr(wplanes)), "picles_nest_init")
         self._nest_parent = parent if hasattr(parent, "gen") else None
 
     def nest_sample(self):
@@ -675,15 +674,10 @@ class HipModel:
         ix, w = np.asarray(index, dtype=np.int64), np.asarray(weights, dtype=np.float64)
         if ix.ndim != 2 or ix.shape != w.shape or ix.shape[0] != fb.shape[0]:
             raise ValueError(f"nest_feedback_init: index and weights must both be ({fb.shape[0]}, m) arrays, got {ix.shape} and {w.shape}")
-        if any(a.size and np.abs(a).max() > 2**31 - 1 for a in (fb, sn, ix)):
-            raise ValueError("nest_feedback_init: index out of the int32 range")
-        fplanes = np.ascontiguousarray(fb.T.astype(np.int32))
-        splanes = np.ascontiguousarray(sn.T.astype(np.int32))
-        iplanes = np.ascontiguousarray(ix.T.astype(np.int32))
+        fplanes, splanes, iplanes = (_int32_planes(a, "nest_feedback_init") for a in (fb, sn, ix))
         wplanes = np.ascontiguousarray(w.T)
-        self._ck(self.lib.picles_nest_feedback_init(self.h, int(fb.shape[0]), fplanes.ctypes.data_as(K.c_int32_p), int(sn.shape[0]),
-                                                    splanes.ctypes.data_as(K.c_int32_p), int(ix.shape[1]), iplanes.ctypes.data_as(K.c_int32_p),
-                                                    K.dptr(wplanes)), "picles_nest_feedback_init")
+        self._ck(self.lib.picles_nest_feedback_init(self.h, fplanes.shape[1], _p32(fplanes), splanes.shape[1], _p32(splanes), iplanes.shape[0],
+                                                    _p32(iplanes), K.dptr(wplanes)), "picles_nest_feedback_init")
 
     def nest_feedback(self):
         """take one level at this model's clock into the parent's set; returns after enqueueing"""

@@ -39,7 +39,7 @@ import numpy as np
 
 from .boundary_forcing import BoundaryForcing, node_points, rim_nodes
 from .output_writers import PHASE_ORDER, in_phase, writers_of
-from .station_output import locate_points
+from .station_output import locate_points, wet_means
 
 RATIO_EPS = 1e-12          # |r Δt_child - Δt_parent| may be this fraction of Δt_parent
 
@@ -115,22 +115,9 @@ def restriction_stencil(parent_grid, child_grid, margin=1):
 def restrict_records(values, index, weight):
     """k_nest_restrict in NumPy, bit for bit: values float64 [n_src, 3] (e, m_x, m_y of the source nodes), index int [n_fb, m]
     into them, weight [n_fb, m] -> float64 [n_fb, 3], NaN rows where no entry is wet.  The station definition of
-    picles_amd/station_output.py over m entries in order; an entry whose weight is 0.0 is padding and is skipped"""
+    picles_amd/station_output.py (wet_means) over m entries in order; an entry whose weight is 0.0 is padding: it adds no bit"""
     v = np.asarray(values, dtype=np.float64).reshape(-1, 3)
-    index, weight = np.asarray(index, dtype=np.int64), np.asarray(weight, dtype=np.float64)
-    n = index.shape[0]
-    W = np.zeros(n); SE = np.zeros(n); SX = np.zeros(n); SY = np.zeros(n)
-    with np.errstate(all="ignore"):
-        for c in range(index.shape[1]):
-            e, mx, my = v[index[:, c], 0], v[index[:, c], 1], v[index[:, c], 2]
-            w = weight[:, c]
-            take = (w != 0.0) & np.isfinite(e) & np.isfinite(mx) & np.isfinite(my) & (e > 0.0) & (mx * mx + my * my > 0.0)
-            W = np.where(take, W + w, W)
-            SE = np.where(take, SE + w * e, SE)
-            SX = np.where(take, SX + w * mx, SX)
-            SY = np.where(take, SY + w * my, SY)
-        E, MX, MY = SE / W, SX / W, SY / W
-        valid = (W > 0.0) & (MX * MX + MY * MY > 0.0)
+    E, MX, MY, valid = wet_means(v.T, np.asarray(index, dtype=np.int64), np.asarray(weight, dtype=np.float64))
     out = np.stack([E, MX, MY], axis=1)
     out[~valid] = np.nan
     return out

@@ -113,25 +113,31 @@ def locate_points(grid, points):
     return corners, weights
 
 
-def station_records(values, index, weights, g, r_g):
-    """values [samples, 3, n_nodes] (probe samples), index int [n_stations, n_corners] into the node axis, weights
-    [n_stations, n_corners] -> float64 [samples, n_stations, 8] in the order of VAR_NAMES (the module docstring's arithmetic)"""
-    values = np.asarray(values, dtype=np.float64)
-    S = values.shape[0]
-    ns, nc = index.shape
-    W = np.zeros((S, ns)); SE = np.zeros((S, ns)); SX = np.zeros((S, ns)); SY = np.zeros((S, ns))
+def wet_means(values, index, weights):
+    """the accumulation of the module docstring, from the wet test to the means: values float64 [..., 3, n_nodes], index int
+    [n, n_entries] into the node axis, weights [n, n_entries] -> E, MX, MY, valid, each [..., n] (not yet NaN where not valid).
+    The mix and the restrict of a nest (k_nest.h, picles_amd/nesting.py) are this too; an entry of weight 0.0 needs no skipping:
+    W + 0.0 = W, and a sum that started at +0.0 keeps its bits when +-0.0 is added"""
+    W = SE = SX = SY = np.zeros(values.shape[:-2] + index.shape[:1])
     with np.errstate(all="ignore"):
-        for c in range(nc):
-            e, mx, my = values[:, 0, index[:, c]], values[:, 1, index[:, c]], values[:, 2, index[:, c]]
-            w = weights[None, :, c]
+        for c in range(index.shape[1]):
+            e, mx, my = values[..., 0, index[:, c]], values[..., 1, index[:, c]], values[..., 2, index[:, c]]
+            w = weights[:, c]
             wet = np.isfinite(e) & np.isfinite(mx) & np.isfinite(my) & (e > 0.0) & (mx * mx + my * my > 0.0)
             W = np.where(wet, W + w, W)
             SE = np.where(wet, SE + w * e, SE)
             SX = np.where(wet, SX + w * mx, SX)
             SY = np.where(wet, SY + w * my, SY)
         E, MX, MY = SE / W, SX / W, SY / W
+        return E, MX, MY, (W > 0.0) & (MX * MX + MY * MY > 0.0)
+
+
+def station_records(values, index, weights, g, r_g):
+    """values [samples, 3, n_nodes] (probe samples), index int [n_stations, n_corners] into the node axis, weights
+    [n_stations, n_corners] -> float64 [samples, n_stations, 8] in the order of VAR_NAMES (the module docstring's arithmetic)"""
+    E, MX, MY, valid = wet_means(np.asarray(values, dtype=np.float64), index, weights)
+    with np.errstate(all="ignore"):
         M2 = MX * MX + MY * MY
-        valid = (W > 0.0) & (M2 > 0.0)
         hs = 4.0 * np.sqrt(E)
         cgx = (MX * E) / (2.0 * M2)
         cgy = (MY * E) / (2.0 * M2)
