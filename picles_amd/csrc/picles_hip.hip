@@ -488,6 +488,56 @@ struct Cadence {
     }
 };
 
+/* The wind over one model step as the kernels see it: where its levels come from, its shape and [t0, t1], which time the
+ * (u1, v1) planes hold, and the plane pairs that exist only once a form has needed them.  publish() is the only writer of the wind
+ * fields of KParams and of A.um / A.vm; every pair is made whole or not at all (make_pair); the (u0, v0) / (u1, v1) / (uP, vP) planes
+ * change places in reuse_swap() and rotate() alone. */
+struct WindWindow {
+    enum Form { STATIC, TWO, PARABOLA, KNOT, POLYLINE };
+    /* three levels: the parabola through (t0, (t0 + t1)/2, t1), or two straight segments meeting at the knot tk[0]; a polyline has
+     * nk >= 2 knots at tk[0 .. nk) */
+    struct Shape { Form form = STATIC; int nk = 0; double tk[PICLES_MAX_KNOTS] = {}; };
+    /* the source: levels the caller uploads (picles_set_winds*), or a lattice that k_wind_sample takes them from */
+    bool lattice = false;
+    int mode = PICLES_LATTICE_LINEAR;
+    WindGrid wg{};
+    double *d_wgu = nullptr, *d_wgv = nullptr;
+    double lat_t0 = 0.0, lat_dt = 0.0;             /* the lattice's first time knot and spacing as the caller gave them (knot times are computed from these) */
+    /* the window on the device */
+    Shape shape;
+    double t0 = 0.0, t1 = 0.0;
+    bool held = false;                             /* (u1, v1) hold the lattice at time held_t */
+    double held_t = 0.0;
+    /* made on first use: the middle level (PARABOLA, KNOT); the polyline's levels at the knots (2 planes per knot) and coefficient
+     * planes (k_wind_poly), with room for poly_cap knots; level 0 of the previous window is A.uP / A.vP */
+    double *um_buf = nullptr, *vm_buf = nullptr;
+    double *lv_buf = nullptr, *xb_buf = nullptr;
+    int poly_cap = 0;
+
+    bool static_() const { return shape.form == STATIC; }
+    bool polyline() const { return shape.form == POLYLINE; }
+    bool from_lattice() const { return lattice; }
+    bool lattice_polyline_ahead(double t, double dt) const;      /* will the lattice's window over [t, t + dt] be a polyline? */
+    /* does the window start where the pending step started, with (u1, v1) holding the lattice at the clock: can prepare() follow it? */
+    bool contiguous_with(double pend_t, double clock) const { return held && held_t == clock && t0 == pend_t && !static_(); }
+    bool middle(const Arrays &A, const double *&u, const double *&v) const { u = A.um; v = A.vm; return u != nullptr; }
+
+    int make_pair(picles_ctx *c, double *&a, size_t a_bytes, double *&b, size_t b_bytes);
+    int need(picles_ctx *c, const Shape &sh, bool prev = false);      /* the pairs a window of this shape reads (prev: and the fused remesh) */
+    int set(picles_ctx *c, const Shape &sh, double t0_, double t1_, hipStream_t s) { shape = sh; t0 = t0_; t1 = t1_; return publish(c, s); }
+    int publish(picles_ctx *c, hipStream_t s);
+    int drop_middle(picles_ctx *c);
+    /* the three plane movements */
+    void reuse_swap(Arrays &A) { std::swap(A.u0, A.u1); std::swap(A.v0, A.v1); }      /* what (u1, v1) held becomes level 0 */
+    void rotate(Arrays &A) { std::swap(A.uP, A.u0); std::swap(A.vP, A.v0); reuse_swap(A); }      /* uP <- u0 <- u1 <- the spare pair */
+    void invalidate() { held = false; }            /* whatever (u1, v1) hold, the next lattice window samples both of its ends */
+    /* the lattice as a source */
+    int plan(picles_ctx *c, double t, double dt, Shape &sh) const;
+    int sample(picles_ctx *c, const Shape &sh, double t, double dt, bool with0, hipStream_t s);
+    int prepare(picles_ctx *c, double t, double dt, bool follow, hipStream_t s);
+    void release(Arrays &A);                       /* idempotent; the caller has drained the streams that read the planes */
+};
+
 struct picles_ctx {
     picles_grid g;
     picles_phys ph;
@@ -588,19 +638,9 @@ struct picles_ctx {
     struct Feedback *fb = nullptr;
     std::vector<picles_ctx *> nest_children;
     picles_ctx *fb_child = nullptr;
-    /* gridded winds */
-    bool wind_grid_on = false;
-    WindGrid wg{};
-    double *d_wgu = nullptr, *d_wgv = nullptr;
-    double wind_t1 = 0.0;          /* time level currently held in (u1, v1) */
-    bool wind_t1_valid = false;
-    int wind_grid_mode = PICLES_LATTICE_LINEAR;
-    double wg_t0 = 0.0, wg_dt = 0.0;   /* the lattice's first time knot and spacing as the caller gave them (knot times are computed from these) */
+    WindWindow wind;               /* the wind window: host-set levels or the device-sampled lattice */
     bool ord_valid = false;        /* the previous fused step filed a dispatch order (kernels.h: Arrays::ord) with ... */
     int ord_nblk = 0;              /* ... this many workgroups: the whole grid, or the interior rows of a slab */
-    double *um_buf = nullptr, *vm_buf = nullptr;   /* mid-window wind level (picles_set_winds3); A.um / A.vm point here while in use */
-    double *lv_buf = nullptr, *xb_buf = nullptr;   /* polyline windows: the levels at the knots (2 planes per knot) and the coefficient planes (k_wind_poly) */
-    int poly_cap = 0;                              /* knots the two buffers hold */
     bool ext_streams = false;      /* a caller-provided stream has been used: order across streams with device syncs */
     bool ring_orders = false;      /* inside picles_slab_run_steps: the ring orders its streams against the context stream with events */
     /* exact restart (picles_checkpoint_*): the device snapshot of the payload + its sum words, its pinned host copy */
@@ -877,7 +917,7 @@ PX_EXPORT int32_t picles_create(const picles_grid *g, const picles_phys *p, cons
     P.init_type = m->init_type;
     P.def_lne = m->default_particle[0]; P.def_cx = m->default_particle[1]; P.def_cy = m->default_particle[2];
     P.min_e = m->minimal_state[0]; P.min_m2 = m->minimal_state[1];
-    P.wind_static = 1; P.tw0 = 0.0; P.inv_dtw = 0.0; P.wind_sk = P.wind_isk = P.wind_i1sk = 0.0;
+    (void)c->wind.publish(c, nullptr);      /* a static window at t = 0 (nothing is launched for one) */
 
     GridP &G = c->G;
     G.Nx = g->Nx; G.Ny = g->Ny; G.periodic_x = (g->periodic_x != 0); G.periodic_y = (g->periodic_y == 1);
@@ -978,9 +1018,7 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     Arrays &A = c->A;
     hipFree(A.state); hipFree(A.movie); hipFree(A.z); hipFree(A.qold); hipFree(A.dtn); hipFree(A.asw); hipFree(A.on);
     hipFree(A.pflags); hipFree(A.status); hipFree(A.u0); hipFree(A.v0); hipFree(A.u1); hipFree(A.v1);
-    if (A.uP) { hipFree(A.uP); hipFree(A.vP); }
-    if (c->um_buf) { hipFree(c->um_buf); hipFree(c->vm_buf); }
-    if (c->lv_buf) { hipFree(c->lv_buf); hipFree(c->xb_buf); }
+    c->wind.release(A);
     hipFree(A.cnt); hipFree(A.rmap); hipFree(c->d_mask);
     if (A.ord) hipFree(A.ord);
     if (A.m11) { hipFree(A.m11); hipFree(A.m22); hipFree(A.pc); }
@@ -997,8 +1035,6 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     if (c->ck_ready) hipEventDestroy(c->ck_ready);
     if (c->ck_done) hipEventDestroy(c->ck_done);
     if (c->store_stream) hipStreamDestroy(c->store_stream);
-    if (c->d_wgu) hipFree(c->d_wgu);
-    if (c->d_wgv) hipFree(c->d_wgv);
     if (c->d_count) hipFree(c->d_count);
     if (c->d_start) hipFree(c->d_start);
     if (c->d_cursor) hipFree(c->d_cursor);
@@ -1025,41 +1061,58 @@ PX_EXPORT double picles_clock(const picles_ctx *c) { return c ? c->clock : 0.0; 
 
 static inline unsigned nblocks(long long n, int b) { return (unsigned)((n + b - 1) / b); }
 
-/* form of a three-level window: the parabola through (t0, (t0+t1)/2, t1), or two straight segments meeting at the knot tk */
-static void wind_window_form(picles_ctx *c, double t0, double t1, bool knot, double tk)
+/* ---- the wind window (struct WindWindow, above the context) ---- */
+/* a pair of device blocks, both or neither: a failed second allocation frees the first and leaves a and b as they were */
+int WindWindow::make_pair(picles_ctx *c, double *&a, size_t a_bytes, double *&b, size_t b_bytes)
 {
-    KParams &P = c->P;
-    P.tw0 = t0;
-    P.inv_dtw = 1.0 / (t1 - t0);
-    if (knot) {
-        P.wind_sk = (tk - t0) * P.inv_dtw;
-        P.wind_isk = 1.0 / P.wind_sk;
-        P.wind_i1sk = 1.0 / (1.0 - P.wind_sk);
-    } else {
-        P.wind_sk = P.wind_isk = P.wind_i1sk = 0.0;
-    }
-    P.wind_nk = knot ? 1 : 0;
-}
-
-/* a polyline window over [t0, t1] with knots tk[0 .. nk) (nk >= 2): the levels at the knots are in lv_buf, levels 0 and nk+1 in the
- * (u0, v0) / (u1, v1) planes; lays down the coefficient planes and sets the window's form.  (um, vm) = the first knot's level and the
- * one-knot scalars describe the first knot: whatever evaluates the window at its START without knowing about polylines — the fused
- * step's remesh reads level 0 from its plane — still gets level 0. */
-static int wind_poly_buffers(picles_ctx *c, int nk)
-{
-    if (nk <= c->poly_cap) return 0;
-    if (c->lv_buf) { hipFree(c->lv_buf); hipFree(c->xb_buf); c->lv_buf = c->xb_buf = nullptr; c->poly_cap = 0; }
-    const size_t n = (size_t)c->A.n;
-    HIPCHK(c, hipMalloc(&c->lv_buf, (size_t)2 * nk * n * 8));
-    HIPCHK(c, hipMalloc(&c->xb_buf, ((size_t)PICLES_MAX_KNOTS + (size_t)2 * (nk + 1) * n) * 8));
-    c->poly_cap = nk;
+    double *pa = nullptr, *pb = nullptr;
+    Undo undo{[&] { hipFree(pa); }};
+    HIPCHK(c, hipMalloc(&pa, a_bytes));
+    HIPCHK(c, hipMalloc(&pb, b_bytes));
+    undo.armed = false;
+    a = pa; b = pb;
     return 0;
 }
-static int wind_window_poly(picles_ctx *c, double t0, double t1, int nk, const double *tk, hipStream_t s)
+int WindWindow::need(picles_ctx *c, const Shape &sh, bool prev)
+{
+    const size_t n = (size_t)c->A.n, plane = n * 8;
+    int rc = 0;
+    if (prev && !c->A.uP) rc = make_pair(c, c->A.uP, plane, c->A.vP, plane);
+    if (!rc && (sh.form == PARABOLA || sh.form == KNOT) && !um_buf) rc = make_pair(c, um_buf, plane, vm_buf, plane);
+    if (rc || sh.form != POLYLINE || sh.nk <= poly_cap) return rc;
+    /* a longer polyline than the buffers hold.  The smaller pair goes first (both would not fit side by side on a large grid); a polyline
+     * on the device falls back to the straight line between its ends, which reads neither buffer */
+    if (polyline() && (rc = drop_middle(c))) return rc;
+    if (lv_buf) { hipFree(lv_buf); hipFree(xb_buf); }
+    lv_buf = xb_buf = nullptr;
+    poly_cap = 0;
+    rc = make_pair(c, lv_buf, (size_t)2 * sh.nk * plane, xb_buf, ((size_t)PICLES_MAX_KNOTS + (size_t)2 * (sh.nk + 1) * n) * 8);
+    if (rc == 0) poly_cap = sh.nk;
+    return rc;
+}
+
+/* Hand the window to the kernels.  A polyline has the levels at its knots in lv_buf, levels 0 and nk + 1 in the (u0, v0) / (u1, v1)
+ * planes, and its coefficient planes laid down on `s`; (um, vm) = the first knot's level and the one-knot scalars describe the first
+ * knot: whatever evaluates the window at its START without knowing about polylines — the fused step's remesh reads level 0 from its
+ * plane — still gets level 0.  wind_xb / wind_xn keep what the last polyline left there: nothing reads them while wind_nk < 2. */
+int WindWindow::publish(picles_ctx *c, hipStream_t s)
 {
     KParams &P = c->P;
     Arrays &A = c->A;
-    wind_window_form(c, t0, t1, true, tk[0]);
+    const Form f = shape.form;
+    const bool knot = f == KNOT || f == POLYLINE, three = f == PARABOLA || f == KNOT;
+    const int nk = shape.nk;
+    const double *tk = shape.tk;
+    P.wind_static = static_() ? 1 : 0;
+    P.tw0 = t0;
+    P.inv_dtw = static_() ? 0.0 : 1.0 / (t1 - t0);
+    P.wind_sk = knot ? (tk[0] - t0) * P.inv_dtw : 0.0;
+    P.wind_isk = knot ? 1.0 / P.wind_sk : 0.0;
+    P.wind_i1sk = knot ? 1.0 / (1.0 - P.wind_sk) : 0.0;
+    P.wind_nk = knot ? 1 : 0;
+    A.um = three ? um_buf : nullptr;           /* no middle level: linear in t (bit for bit the two-level arithmetic) */
+    A.vm = three ? vm_buf : nullptr;
+    if (!polyline()) return 0;
     WindPolyForm F;
     F.nk = nk;
     double sprev = 0.0;
@@ -1071,13 +1124,25 @@ static int wind_window_poly(picles_ctx *c, double t0, double t1, int nk, const d
         sprev = sn;
     }
     for (int k = nk + 1; k <= PICLES_MAX_KNOTS; k++) F.ilen[k] = 0.0;
-    hipLaunchKernelGGL(k_wind_poly, dim3(nblocks(A.n, 256)), dim3(256), 0, s, F, A.u0, A.v0, A.u1, A.v1, c->lv_buf, c->xb_buf, A.n);
+    hipLaunchKernelGGL(k_wind_poly, dim3(nblocks(A.n, 256)), dim3(256), 0, s, F, A.u0, A.v0, A.u1, A.v1, lv_buf, xb_buf, A.n);
     HIPCHK(c, hipGetLastError());
-    A.um = c->lv_buf; A.vm = c->lv_buf + A.n;
+    A.um = lv_buf; A.vm = lv_buf + A.n;
     P.wind_nk = nk;
-    P.wind_xb = c->xb_buf;
+    P.wind_xb = xb_buf;
     P.wind_xn = A.n;
     return 0;
+}
+/* back to no middle level, no knot: what is left is static, or the straight line between the window's ends */
+int WindWindow::drop_middle(picles_ctx *c)
+{
+    shape.form = static_() ? STATIC : TWO;
+    shape.nk = 0;
+    return publish(c, nullptr);
+}
+void WindWindow::release(Arrays &A)
+{
+    for (double **p : {&A.uP, &A.vP, &um_buf, &vm_buf, &lv_buf, &xb_buf, &d_wgu, &d_wgv}) { hipFree(*p); *p = nullptr; }
+    poly_cap = 0;
 }
 
 static int set_wind_levels(picles_ctx *c, const double *u0, const double *v0, double t0,
@@ -1088,36 +1153,28 @@ static int set_wind_levels(picles_ctx *c, const double *u0, const double *v0, do
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = flush(c); if (rc) return rc; }
     HIPCHK(c, hipDeviceSynchronize());   /* the previous step may still read the wind planes */
-    c->wind_grid_on = false;
+    const bool two = u1 && v1 && t1 != t0;
+    const bool three = two && um && vm;
+    WindWindow &W = c->wind;
+    WindWindow::Shape sh;
+    sh.form = !two ? WindWindow::STATIC : !three ? WindWindow::TWO : knot ? WindWindow::KNOT : WindWindow::PARABOLA;
+    sh.nk = sh.form == WindWindow::KNOT ? 1 : 0;
+    sh.tk[0] = tk;
+    { int rc = W.need(c, sh); if (rc) return rc; }      /* (first: a call that fails here has changed nothing) */
+    W.lattice = false;
     Arrays &A = c->A;
     size_t b = (size_t)A.n * 8;
     HIPCHK(c, hipMemcpyAsync(A.u0, u0, b, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(A.v0, v0, b, hipMemcpyHostToDevice, c->stream));
-    const bool two = u1 && v1 && t1 != t0;
-    const bool three = two && um && vm;
     if (two) {
         HIPCHK(c, hipMemcpyAsync(A.u1, u1, b, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(A.v1, v1, b, hipMemcpyHostToDevice, c->stream));
-        c->P.wind_static = 0;
-        wind_window_form(c, t0, t1, three && knot, tk);
-    } else {
-        c->P.wind_static = 1;
-        c->P.tw0 = t0;
-        c->P.inv_dtw = 0.0;
-        c->P.wind_sk = c->P.wind_isk = c->P.wind_i1sk = 0.0;
-        c->P.wind_nk = 0;
     }
-    if (three) {                         /* third level: the planes exist from the first three-level call on */
-        if (!c->um_buf) {
-            HIPCHK(c, hipMalloc(&c->um_buf, b));
-            HIPCHK(c, hipMalloc(&c->vm_buf, b));
-        }
-        HIPCHK(c, hipMemcpyAsync(c->um_buf, um, b, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->vm_buf, vm, b, hipMemcpyHostToDevice, c->stream));
-        A.um = c->um_buf; A.vm = c->vm_buf;
-    } else {
-        A.um = A.vm = nullptr;           /* two levels: linear in t (bit for bit the two-level arithmetic) */
+    if (three) {
+        HIPCHK(c, hipMemcpyAsync(W.um_buf, um, b, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(W.vm_buf, vm, b, hipMemcpyHostToDevice, c->stream));
     }
+    (void)W.set(c, sh, t0, t1, c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));   /* caller may reuse its host buffers */
     return 0;
 }
@@ -1165,13 +1222,18 @@ PX_EXPORT int32_t picles_set_winds_polyline(picles_ctx *c, int32_t nlev, const d
     /* levels 0, 1 and the last through the three-level path (the one-knot form of the first knot), then the further knots */
     int rc = set_wind_levels(c, u[0], v[0], times[0], u[1], v[1], true, times[1], u[nlev - 1], v[nlev - 1], times[nlev - 1]);
     if (rc) return rc;
-    if ((rc = wind_poly_buffers(c, nk))) return rc;
+    WindWindow &W = c->wind;
+    WindWindow::Shape sh;
+    sh.form = WindWindow::POLYLINE;
+    sh.nk = nk;
+    for (int k = 0; k < nk; k++) sh.tk[k] = times[k + 1];
+    if ((rc = W.need(c, sh))) return rc;
     const size_t b = (size_t)c->A.n * 8;
     for (int k = 0; k < nk; k++) {
-        HIPCHK(c, hipMemcpyAsync(c->lv_buf + (size_t)(2 * k) * c->A.n, u[k + 1], b, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->lv_buf + (size_t)(2 * k + 1) * c->A.n, v[k + 1], b, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(W.lv_buf + (size_t)(2 * k) * c->A.n, u[k + 1], b, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(W.lv_buf + (size_t)(2 * k + 1) * c->A.n, v[k + 1], b, hipMemcpyHostToDevice, c->stream));
     }
-    if ((rc = wind_window_poly(c, times[0], times[nlev - 1], nk, times + 1, c->stream))) return rc;
+    if ((rc = W.set(c, sh, times[0], times[nlev - 1], c->stream))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));   /* caller may reuse its host buffers */
     return 0;
 }
@@ -1206,25 +1268,24 @@ PX_EXPORT int32_t picles_set_wind_grid(picles_ctx *c, int32_t nx, int32_t ny, in
     HIPCHK(c, hipSetDevice(c->device));
     { int rc = flush(c); if (rc) return rc; }
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->d_wgu) { hipFree(c->d_wgu); hipFree(c->d_wgv); c->d_wgu = c->d_wgv = nullptr; }
+    WindWindow &W = c->wind;
+    if (W.d_wgu) { hipFree(W.d_wgu); hipFree(W.d_wgv); W.d_wgu = W.d_wgv = nullptr; }
+    W.lattice = false;                   /* (until the new one is up: a failed upload leaves the window on the device, not a freed lattice) */
     size_t nb = (size_t)nx * ny * nt * 8;
-    HIPCHK(c, hipMalloc(&c->d_wgu, nb));
-    HIPCHK(c, hipMalloc(&c->d_wgv, nb));
-    HIPCHK(c, hipMemcpy(c->d_wgu, u, nb, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_wgv, v, nb, hipMemcpyHostToDevice));
+    { int rc = W.make_pair(c, W.d_wgu, nb, W.d_wgv, nb); if (rc) return rc; }
+    HIPCHK(c, hipMemcpy(W.d_wgu, u, nb, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(W.d_wgv, v, nb, hipMemcpyHostToDevice));
     c->fp_lattice = fp_bytes(fp_bytes(FP_SEED, u, nb), v, nb);
-    WindGrid &w = c->wg;
+    WindGrid &w = W.wg;
     w.nx = nx; w.ny = ny; w.nt = nt;
     w.x0 = x0; w.inv_dx = 1.0 / dx; w.y0 = y0; w.inv_dy = 1.0 / dy; w.t0 = t0; w.inv_dt = 1.0 / dt;
     w.mesh_x0 = mesh_x0; w.mesh_y0 = mesh_y0; w.mesh_dx = c->g.dx; w.mesh_dy = c->g.dy;
-    w.u = c->d_wgu; w.v = c->d_wgv;
-    c->wg_t0 = t0; c->wg_dt = dt;
-    c->A.um = c->A.vm = nullptr;
-    c->P.wind_sk = c->P.wind_isk = c->P.wind_i1sk = 0.0;
-    c->P.wind_nk = 0;
-    c->wind_grid_on = true;
-    c->wind_grid_mode = PICLES_LATTICE_LINEAR;
-    c->wind_t1_valid = false;
+    w.u = W.d_wgu; w.v = W.d_wgv;
+    W.lat_t0 = t0; W.lat_dt = dt;
+    (void)W.drop_middle(c);
+    W.lattice = true;
+    W.mode = PICLES_LATTICE_LINEAR;
+    W.invalidate();
     return 0;
 }
 
@@ -1232,10 +1293,10 @@ PX_EXPORT int32_t picles_set_wind_grid_mode(picles_ctx *c, int32_t mode)
 {
     if (!c) return -1;
     if (mode != PICLES_LATTICE_LINEAR && mode != PICLES_LATTICE_SMOOTH3) return fail(c, -2, "unknown wind lattice mode");
-    if (!c->wind_grid_on) return fail(c, -2, "picles_set_wind_grid first");
+    if (!c->wind.from_lattice()) return fail(c, -2, "picles_set_wind_grid first");
     { int rc = flush(c); if (rc) return rc; }
-    c->wind_grid_mode = mode;
-    c->wind_t1_valid = false;
+    c->wind.mode = mode;
+    c->wind.invalidate();
     return 0;
 }
 
@@ -1265,94 +1326,71 @@ PX_EXPORT int32_t picles_lattice_knot_times(double lat_t0, double lat_dt, double
     return n;
 }
 
-/* what the step window [t, t + dt] over the lattice looks like: levels, form, time of the middle level; nk >= 2: a polyline window
- * with knots at tk[0 .. nk) */
-struct WindowPlan { bool three; bool knot; double tm; int nk; double tk[PICLES_MAX_KNOTS]; };
-static int wind_window_plan(picles_ctx *c, double t, double dt, WindowPlan &W)
+bool WindWindow::lattice_polyline_ahead(double t, double dt) const
 {
-    W = WindowPlan{};
-    if (c->wind_grid_mode == PICLES_LATTICE_SMOOTH3) {
-        W.three = true;
-        W.tm = t + 0.5 * dt;
-        return 0;
-    }
-    const int nk = picles_lattice_knot_times(c->wg_t0, c->wg_dt, t, dt, W.tk, PICLES_MAX_KNOTS);
-    if (nk > PICLES_MAX_KNOTS) {
+    return lattice && mode != PICLES_LATTICE_SMOOTH3 && picles_lattice_knot_times(lat_t0, lat_dt, t, dt, nullptr, 0) >= 2;
+}
+/* the shape of the step window [t, t + dt] over the lattice: smooth3, the parabola; linear, by the time knots strictly inside */
+int WindWindow::plan(picles_ctx *c, double t, double dt, Shape &sh) const
+{
+    sh = Shape{};
+    sh.form = PARABOLA;
+    if (mode == PICLES_LATTICE_SMOOTH3) return 0;
+    sh.nk = picles_lattice_knot_times(lat_t0, lat_dt, t, dt, sh.tk, PICLES_MAX_KNOTS);
+    if (sh.nk > PICLES_MAX_KNOTS) {
         char buf[360];
         snprintf(buf, sizeof buf, "the model step [%.17g, %.17g] contains %d time knots of the wind lattice (spacing %.17g s); a window carries at most %d: "
                  "take shorter model steps, or picles_set_wind_grid_mode(PICLES_LATTICE_SMOOTH3) if the lattice tabulates a smooth closure",
-                 t, t + dt, nk, c->wg_dt, PICLES_MAX_KNOTS);
+                 t, t + dt, sh.nk, lat_dt, PICLES_MAX_KNOTS);
         return fail(c, -7, buf);
     }
-    if (nk >= 1) { W.three = true; W.knot = true; W.tm = W.tk[0]; }
-    W.nk = nk;
+    sh.form = sh.nk == 0 ? TWO : sh.nk == 1 ? KNOT : POLYLINE;
     return 0;
 }
 
-/* sample the levels of the window [t, t + dt] that are not on the device yet: level 1 at t + dt into (u1, v1), the middle level
- * (the knot, or t + dt/2) into (um, vm) when the window has one, level 0 into (u0, v0) when `with0`; sets the window's form */
-static int wind_window_sample(picles_ctx *c, const WindowPlan &W, double t, double dt, bool with0, hipStream_t s)
+/* sample the levels of the window [t, t + dt] that are not on the device yet — level 0 into (u0, v0) when `with0`; then the middle
+ * level (the knot, or t + dt/2) into (um, vm), or the levels at a polyline's knots into lv_buf, and level 1 at t + dt into (u1, v1),
+ * two levels a launch — and publish the window.  The pairs the shape reads exist (need) */
+int WindWindow::sample(picles_ctx *c, const Shape &sh, double t, double dt, bool with0, hipStream_t s)
 {
     Arrays &A = c->A;
     dim3 grid(nblocks(A.n, 256)), block(256);
-    if (W.three && W.nk < 2 && !c->um_buf) {
-        HIPCHK(c, hipMalloc(&c->um_buf, (size_t)A.n * 8));
-        HIPCHK(c, hipMalloc(&c->vm_buf, (size_t)A.n * 8));
-    }
+    const size_t n = (size_t)A.n;
+    struct { double t; double *u, *v; } L[PICLES_MAX_KNOTS + 1];
+    int m = 0;
+    if (sh.form == PARABOLA || sh.form == KNOT) L[m++] = {sh.form == KNOT ? sh.tk[0] : t + 0.5 * dt, um_buf, vm_buf};
+    for (int k = 0; sh.form == POLYLINE && k < sh.nk; k++) L[m++] = {sh.tk[k], lv_buf + (size_t)(2 * k) * n, lv_buf + (size_t)(2 * k + 1) * n};
+    L[m++] = {t + dt, A.u1, A.v1};
     if (with0) {
         WindSampleOut O = {{t, 0.0}, {A.u0, nullptr}, {A.v0, nullptr}};
-        hipLaunchKernelGGL(k_wind_sample<1>, grid, block, 0, s, c->G, c->wg, O, A.n);
+        hipLaunchKernelGGL(k_wind_sample<1>, grid, block, 0, s, c->G, wg, O, A.n);
     }
-    if (W.nk >= 2) {       /* a polyline: the levels at the knots, the level at the window's end, then the coefficient planes */
-        { int rc = wind_poly_buffers(c, W.nk); if (rc) return rc; }
-        const size_t n = (size_t)A.n;
-        for (int k = 0; k < W.nk; k += 2) {
-            const bool two = k + 1 < W.nk;
-            WindSampleOut O = {{W.tk[k], two ? W.tk[k + 1] : t + dt},
-                               {c->lv_buf + (size_t)(2 * k) * n, two ? c->lv_buf + (size_t)(2 * k + 2) * n : A.u1},
-                               {c->lv_buf + (size_t)(2 * k + 1) * n, two ? c->lv_buf + (size_t)(2 * k + 3) * n : A.v1}};
-            hipLaunchKernelGGL(k_wind_sample<2>, grid, block, 0, s, c->G, c->wg, O, A.n);
+    for (int k = 0; k < m; k += 2) {
+        if (k + 1 < m) {
+            WindSampleOut O = {{L[k].t, L[k + 1].t}, {L[k].u, L[k + 1].u}, {L[k].v, L[k + 1].v}};
+            hipLaunchKernelGGL(k_wind_sample<2>, grid, block, 0, s, c->G, wg, O, A.n);
+        } else {
+            WindSampleOut O = {{L[k].t, 0.0}, {L[k].u, nullptr}, {L[k].v, nullptr}};
+            hipLaunchKernelGGL(k_wind_sample<1>, grid, block, 0, s, c->G, wg, O, A.n);
         }
-        if (W.nk % 2 == 0) {
-            WindSampleOut O = {{t + dt, 0.0}, {A.u1, nullptr}, {A.v1, nullptr}};
-            hipLaunchKernelGGL(k_wind_sample<1>, grid, block, 0, s, c->G, c->wg, O, A.n);
-        }
-        HIPCHK(c, hipGetLastError());
-        c->wind_t1 = t + dt;
-        c->wind_t1_valid = true;
-        c->P.wind_static = 0;
-        return wind_window_poly(c, t, t + dt, W.nk, W.tk, s);
-    }
-    if (W.three) {
-        WindSampleOut O = {{W.tm, t + dt}, {c->um_buf, A.u1}, {c->vm_buf, A.v1}};
-        hipLaunchKernelGGL(k_wind_sample<2>, grid, block, 0, s, c->G, c->wg, O, A.n);
-        A.um = c->um_buf; A.vm = c->vm_buf;
-    } else {
-        WindSampleOut O = {{t + dt, 0.0}, {A.u1, nullptr}, {A.v1, nullptr}};
-        hipLaunchKernelGGL(k_wind_sample<1>, grid, block, 0, s, c->G, c->wg, O, A.n);
-        A.um = A.vm = nullptr;
     }
     HIPCHK(c, hipGetLastError());
-    c->wind_t1 = t + dt;
-    c->wind_t1_valid = true;
-    c->P.wind_static = 0;
-    wind_window_form(c, t, t + dt, W.knot, W.tm);
-    return 0;
+    held_t = t + dt;
+    held = true;
+    return set(c, sh, t, t + dt, s);
 }
 
-/* sample the lattice for the step [t, t+dt] into (u0,v0) / (u1,v1) (+ the middle level); reuses the level the previous
- * step left in (u1,v1) by swapping the plane pointers */
-static int wind_grid_prepare(picles_ctx *c, double t, double dt, hipStream_t s)
+/* the window of the step [t, t + dt].  follow: behind a pending step whose window it is contiguous with — the planes rotate and only
+ * the new level 1 is sampled; else the level the previous step left in (u1, v1), if it is this step's start, is reused as level 0 */
+int WindWindow::prepare(picles_ctx *c, double t, double dt, bool follow, hipStream_t s)
 {
-    Arrays &A = c->A;
-    WindowPlan W;
-    { int rc = wind_window_plan(c, t, dt, W); if (rc) return rc; }
-    const bool reuse = c->wind_t1_valid && c->wind_t1 == t;
-    if (reuse) {
-        std::swap(A.u0, A.u1);
-        std::swap(A.v0, A.v1);
-    }
-    return wind_window_sample(c, W, t, dt, !reuse, s);
+    Shape sh;
+    { int rc = plan(c, t, dt, sh); if (rc) return rc; }
+    { int rc = need(c, sh, follow); if (rc) return rc; }      /* (before a plane moves: a call that fails here can be made again) */
+    const bool reuse = !follow && held && held_t == t;
+    if (follow) rotate(c->A);
+    else if (reuse) reuse_swap(c->A);
+    return sample(c, sh, t, dt, !follow && !reuse, s);
 }
 
 PX_EXPORT int32_t picles_get_winds(picles_ctx *c, double *u0, double *v0, double *u1, double *v1)
@@ -1371,12 +1409,13 @@ PX_EXPORT int32_t picles_get_winds(picles_ctx *c, double *u0, double *v0, double
 PX_EXPORT int32_t picles_get_winds_mid(picles_ctx *c, double *um, double *vm)
 {
     if (!c) return -1;
-    if (!c->A.um) return 1;
+    const double *mu, *mv;
+    if (!c->wind.middle(c->A, mu, mv)) return 1;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
     size_t b = (size_t)c->A.n * 8;
-    if (um) HIPCHK(c, hipMemcpy(um, c->A.um, b, hipMemcpyDeviceToHost));
-    if (vm) HIPCHK(c, hipMemcpy(vm, c->A.vm, b, hipMemcpyDeviceToHost));
+    if (um) HIPCHK(c, hipMemcpy(um, mu, b, hipMemcpyDeviceToHost));
+    if (vm) HIPCHK(c, hipMemcpy(vm, mv, b, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1386,12 +1425,13 @@ PX_EXPORT int32_t picles_seed(picles_ctx *c, double t0)
     HIPCHK(c, hipSetDevice(c->device));
     if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* earlier steps may still run on caller / ring streams */
     c->clock = t0;
-    if (c->wind_grid_on) {   /* winds at t = 0.0 seed the particles (run.jl:213-215) */
+    if (c->wind.from_lattice()) {   /* winds at t = 0.0 seed the particles (run.jl:213-215) */
         /* only level 0 is read (k_seed evaluates the window at its start); the window's end is sampled at the seed time scale, whatever
          * lies between: a plain two-level window, replaced by the first step's own */
-        c->wind_t1_valid = false;
-        const WindowPlan two = WindowPlan{};
-        int rc = wind_window_sample(c, two, 0.0, c->od.timestep, true, c->stream);
+        c->wind.invalidate();
+        WindWindow::Shape two;
+        two.form = WindWindow::TWO;
+        int rc = c->wind.sample(c, two, 0.0, c->od.timestep, true, c->stream);
         if (rc) return rc;
     }
     c->pending = false;
@@ -1433,23 +1473,29 @@ PX_EXPORT int32_t picles_tick(picles_ctx *c, double dt)
     return 0;
 }
 
-static int begin_step(picles_ctx *c, double dt, int32_t flags)
+/* a model step begins: its length and flags, and the buffers that rotate with the steps */
+static void step_begun(picles_ctx *c, double dt, int flags)
 {
-    if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
-    { int rc = flush(c); if (rc) return rc; }
-    if (c->wind_grid_on) {  /* (first: a window the lattice cannot carry is refused before the step has changed anything) */
-        HIPCHK(c, hipSetDevice(c->device));
-        if (c->ext_streams && !c->ring_orders) HIPCHK(c, hipDeviceSynchronize());   /* previous step (any stream) done with the wind planes */
-        int rc = wind_grid_prepare(c, c->clock, dt, c->stream);
-        if (rc) return rc;
-        /* caller-stream launches wait for the sampler through ev_ctx (step_prologue) */
-    }
     c->step_dt = dt;
     c->step_flags = flags;
     c->edge_pending = false;
     c->cur ^= 1;            /* this step's records go to (and are scattered from) rec_buf[cur] */
     c->mr_w = (c->mr_w + 1) % 5;
     if (c->cmap_hot > 0) c->cmap_hot--;
+}
+
+static int begin_step(picles_ctx *c, double dt, int32_t flags)
+{
+    if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
+    { int rc = flush(c); if (rc) return rc; }
+    if (c->wind.from_lattice()) {  /* (first: a window the lattice cannot carry is refused before the step has changed anything) */
+        HIPCHK(c, hipSetDevice(c->device));
+        if (c->ext_streams && !c->ring_orders) HIPCHK(c, hipDeviceSynchronize());   /* previous step (any stream) done with the wind planes */
+        int rc = c->wind.prepare(c, c->clock, dt, false, c->stream);
+        if (rc) return rc;
+        /* caller-stream launches wait for the sampler through ev_ctx (step_prologue) */
+    }
+    step_begun(c, dt, flags);
     return 0;
 }
 
@@ -1571,9 +1617,9 @@ PX_EXPORT int32_t picles_advance_rows(picles_ctx *c, int32_t which, void *stream
     {
         const KParams &P = c->P;
         bool fast = physics_fast(P);
-        if (!P.wind_static && P.wind_nk > 1) fast = false;     /* a polyline window: the general flavours carry it (same bits: the oracle's one arithmetic) */
+        if (c->wind.polyline()) fast = false;     /* a polyline window: the general flavours carry it (same bits: the oracle's one arithmetic) */
         StepLaunch L = {dim3(nblocks(nt, 256)), dim3(256), s, &c->P, &c->G, &A, 0.0, 0.0, c->clock, c->step_dt, r0, n0, r1, n1};
-        launch_k_advance(L, fast, P.solver, P.wind_static != 0, c->A.pc != nullptr);      /* k_advance.hip */
+        launch_k_advance(L, fast, P.solver, c->wind.static_(), c->A.pc != nullptr);      /* k_advance.hip */
     }
     timing_end(c, s);
     HIPCHK(c, hipGetLastError());
@@ -1592,14 +1638,14 @@ static bool step_fusable(const picles_ctx *c, int flags, double dt)
     const KParams &P = c->P;
     /* a polyline window (two or more lattice knots inside the step; host levels set by picles_set_winds_polyline) takes the plain
      * phases: only the general flavours of the stand-alone advance evaluate one */
-    if (c->wind_grid_on ? (c->wind_grid_mode != PICLES_LATTICE_SMOOTH3 && picles_lattice_knot_times(c->wg_t0, c->wg_dt, c->clock, dt, nullptr, 0) >= 2)
-                        : (!P.wind_static && P.wind_nk > 1)) return false;
+    const WindWindow &W = c->wind;
+    if (W.from_lattice() ? W.lattice_polyline_ahead(c->clock, dt) : W.polyline()) return false;
     const bool fast = physics_fast(P);
     /* the time-varying-wind and per-node-metric flavours of the fused kernel exist for the specialised physics */
-    if (c->wind_grid_on) return fast;
-    if (c->A.pc) return fast && P.wind_static != 0;
-    if (P.solver == 2) return fast && P.wind_static != 0;   /* the auto-switching flavour exists for the specialised physics */
-    return P.wind_static != 0;
+    if (W.from_lattice()) return fast;
+    if (c->A.pc) return fast && W.static_();
+    if (P.solver == 2) return fast && W.static_();   /* the auto-switching flavour exists for the specialised physics */
+    return W.static_();
 }
 
 /* does the fused launch of these rows take k_step_waverow? */
@@ -1614,7 +1660,7 @@ static bool step_rows_waverow(const picles_ctx *c, int which)
 /* the flavours the default mode hands to k_step_waverow: those timed against k_step, same session, and found faster.
  * The Tsit5, time-varying-wind and default-solver flavours give the same bits (tests/test_gpu_waverow.py) but have not been timed:
  * they stay on k_step unless PICLES_WAVEROW=require asks for them */
-static bool waverow_measured(const KParams &P) { return P.solver == 0 && P.wind_static != 0; }
+static bool waverow_measured(const picles_ctx *c) { return c->P.solver == 0 && c->wind.static_(); }
 
 /* fused phase launcher: scatter+remesh of the pending step and advance of the current one for the
  * selected rows (records of the pending step: rec_buf[1-cur], of this step: rec_buf[cur]) */
@@ -1649,16 +1695,16 @@ static int launch_step_rows(picles_ctx *c, int which, hipStream_t s)
     }
     /* (the four-wave static flavours of k_step_waverow fetch u0, v0 and ln q_old sixteen bytes at a time: kernels.h, stage_aligned;
      * planes that are not so aligned take k_step, same bits) */
-    const bool staged = P.wind_static != 0 && !(fast && P.solver == 2);
-    const bool waverow = (c->waverow_mode == 2 || (c->waverow_mode == 1 && waverow_measured(P))) && step_rows_waverow(c, which) &&
+    const bool staged = c->wind.static_() && !(fast && P.solver == 2);
+    const bool waverow = (c->waverow_mode == 2 || (c->waverow_mode == 1 && waverow_measured(c))) && step_rows_waverow(c, which) &&
                          (!staged || stage_aligned(A));
     if (waverow && c->pull_class) c->cmap_hot = 4;       /* its entries live in buffer mr_w until the step after next but one clears them */
     else if (!waverow && c->cmap_hot > 0 && (rc = class_map_clear_rows(c, s, r0, n0, r1, n1))) return rc;
     timing_begin(c, s, 0);
     {
         StepLaunch L = {dim3(nblocks(nt, 256)), dim3(256), s, &c->P, &c->G, &A, c->pend_t, c->pend_dt, c->clock, c->step_dt, r0, n0, r1, n1, waverow};
-        if (fast && P.solver == 2) launch_k_step_auto(L, P.wind_static != 0, c->A.pc != nullptr);          /* k_step_auto.hip */
-        else launch_k_step_explicit(L, fast, P.solver, P.wind_static != 0, c->A.pc != nullptr);             /* k_step_explicit.hip */
+        if (fast && P.solver == 2) launch_k_step_auto(L, c->wind.static_(), c->A.pc != nullptr);          /* k_step_auto.hip */
+        else launch_k_step_explicit(L, fast, P.solver, c->wind.static_(), c->A.pc != nullptr);             /* k_step_explicit.hip */
     }
     timing_end(c, s);
     HIPCHK(c, hipGetLastError());
@@ -1683,40 +1729,18 @@ PX_EXPORT int32_t picles_begin_fused_step(picles_ctx *c, double dt)
         return fail(c, -5, "PICLES_WAVEROW=require: a fused launch of this step does not qualify for k_step_waverow (one row range, "
                            "Nx a multiple of 64, rows a multiple of 4, specialised physics without the per-node metric)");
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->wind_grid_on) {
-        /* device-sampled winds.  With a step pending, its remesh (done by this step's launches) needs the wind
-         * at ITS clock: level 0 of its window.  The three level planes rotate — previous level 0 -> (uP, vP),
-         * previous level 1 -> level 0 — and only the new level 1 is sampled. */
-        Arrays &A = c->A;
-        if (c->pending && !(c->wind_t1_valid && c->wind_t1 == c->clock && c->P.tw0 == c->pend_t && !c->P.wind_static))
+    if (c->wind.from_lattice()) {
+        /* device-sampled winds.  With a step pending, its remesh (done by this step's launches) needs the wind at ITS clock: level 0
+         * of its window, which prepare() keeps in (uP, vP) */
+        if (c->pending && !c->wind.contiguous_with(c->pend_t, c->clock))
             return 1;   /* the windows are not contiguous: take the plain phases (they flush first) */
         /* earlier launches on other streams read the planes (the native slab ring orders its own streams with events) */
         if (c->ext_streams && !c->ring_orders) HIPCHK(c, hipDeviceSynchronize());
-        if (c->pending) {
-            WindowPlan W;
-            { int rc = wind_window_plan(c, c->clock, dt, W); if (rc) return rc; }
-            if (!A.uP) {
-                HIPCHK(c, hipMalloc(&A.uP, (size_t)A.n * 8));
-                HIPCHK(c, hipMalloc(&A.vP, (size_t)A.n * 8));
-            }
-            double *tu = A.uP, *tv = A.vP;
-            A.uP = A.u0; A.vP = A.v0;
-            A.u0 = A.u1; A.v0 = A.v1;
-            A.u1 = tu; A.v1 = tv;
-            int rc = wind_window_sample(c, W, c->clock, dt, false, c->stream);
-            if (rc) return rc;
-        } else {
-            int rc = wind_grid_prepare(c, c->clock, dt, c->stream);
-            if (rc) return rc;
-        }
+        int rc = c->wind.prepare(c, c->clock, dt, c->pending, c->stream);
+        if (rc) return rc;
         if (c->ext_streams && !c->ring_orders) HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    c->step_dt = dt;
-    c->step_flags = PICLES_STEP_ZERO_FIRST;
-    c->edge_pending = false;
-    c->cur ^= 1;
-    c->mr_w = (c->mr_w + 1) % 5;
-    if (c->cmap_hot > 0) c->cmap_hot--;
+    step_begun(c, dt, PICLES_STEP_ZERO_FIRST);
     return 0;
 }
 
@@ -3470,7 +3494,7 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
         /* the context stream (wind-lattice sampler of this step) must come after the previous step's launches on E and
          * M, and this step's launches after it (step_prologue: ev_ctx); a flush synchronises the device by itself */
         HIPCHK(c, hipEventRecord(R->evM, R->sM));
-        if (c->wind_grid_on) {
+        if (c->wind.from_lattice()) {
             HIPCHK(c, hipEventRecord(R->evE, R->sE));
             HIPCHK(c, hipStreamWaitEvent(c->stream, R->evM, 0));
             HIPCHK(c, hipStreamWaitEvent(c->stream, R->evE, 0));
@@ -3753,11 +3777,11 @@ static uint64_t ckpt_fingerprint(const picles_ctx *c)
     h = fp_bytes(h, c->h_mask.data(), c->h_mask.size());
     h = fp_val(h, c->G.single_slab); h = fp_val(h, c->halo0);
     h = fp_val(h, (int32_t)(c->A.m11 != nullptr)); h = fp_val(h, c->fp_metric);
-    h = fp_val(h, (int32_t)c->wind_grid_on);
-    if (c->wind_grid_on) {
-        const WindGrid &w = c->wg;
-        h = fp_val(h, c->wind_grid_mode); h = fp_val(h, w.nx); h = fp_val(h, w.ny); h = fp_val(h, w.nt);
-        for (double v : {w.x0, w.inv_dx, w.y0, w.inv_dy, c->wg_t0, c->wg_dt, w.mesh_x0, w.mesh_y0}) h = fp_val(h, v);
+    h = fp_val(h, (int32_t)c->wind.from_lattice());
+    if (c->wind.from_lattice()) {
+        const WindGrid &w = c->wind.wg;
+        h = fp_val(h, c->wind.mode); h = fp_val(h, w.nx); h = fp_val(h, w.ny); h = fp_val(h, w.nt);
+        for (double v : {w.x0, w.inv_dx, w.y0, w.inv_dy, c->wind.lat_t0, c->wind.lat_dt, w.mesh_x0, w.mesh_y0}) h = fp_val(h, v);
         h = fp_val(h, c->fp_lattice);
     }
     return h;
@@ -3923,6 +3947,6 @@ PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t 
     c->seeded = true;
     c->edge_pending = false;
     c->ord_valid = false;     /* the dispatch order is scheduling only: the first fused step after a load runs in natural order */
-    c->wind_t1_valid = false; /* a lattice window is sampled afresh (the same bits: the sampler is a function of the time alone) */
+    c->wind.invalidate();     /* a lattice window is sampled afresh (the same bits: the sampler is a function of the time alone) */
     return 0;
 }

@@ -14,6 +14,8 @@
 //   * fake_hip_fail_alloc(k): the k-th next hipMalloc / hipHostMalloc / event or stream creation fails, once (k <= 0: off); returns
 //     what was left of the previous count (> 0: that failure never came).  fake_hip_live(): device and pinned blocks plus events
 //     alive now — a failed call that gives the same number back as before has left nothing behind.
+//   * fake_hip_launch_hook(f): f (nullptr: none) is called at every kernel launch with the kernel's (mangled) name and its argument
+//     array, behind the launch's own trace line; fake_hip_trace_line(text) lets it append a line of its own to the trace.
 // TEST INFRASTRUCTURE ONLY (tests/test_host_asan.py).  Never linked into, shipped with or loaded by the product.
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
@@ -110,6 +112,10 @@ void fake_free(void *p)
 
 extern "C" long fake_hip_fail_alloc(long k) { return g_fail_in.exchange(k); }
 extern "C" long fake_hip_live(void) { return g_live.load(); }
+typedef void (*fake_hip_hook)(const char *kernel, void **args);
+static fake_hip_hook g_launch_hook = nullptr;
+extern "C" void fake_hip_launch_hook(fake_hip_hook f) { g_launch_hook = f; }
+extern "C" void fake_hip_trace_line(const char *text) { trace("%s", text); }
 
 extern "C" {
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
@@ -257,10 +263,10 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned)
 }
 
 /* kernel launches: accepted, not executed */
-hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **, size_t, hipStream_t s)
+hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, size_t, hipStream_t s)
 {
     if (!ok_stream(s)) return fail(hipErrorInvalidHandle);
-    if (trace_file()) {
+    if (trace_file() || g_launch_hook) {
         std::string name = "?";
         {
             std::lock_guard<std::mutex> lk(g_trace_mu);
@@ -268,6 +274,7 @@ hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **, size_
             if (it != kernel_names().end()) name = it->second;
         }
         trace("hipLaunchKernel %s grid %u,%u,%u block %u,%u,%u s%d", name.c_str(), grid.x, grid.y, grid.z, block.x, block.y, block.z, sid(s));
+        if (g_launch_hook) g_launch_hook(name.c_str(), args);
     }
     if (grid.x == 0 || grid.y == 0 || grid.z == 0 || block.x == 0 || block.x * block.y * block.z > 1024) return fail(hipErrorInvalidConfiguration);
     return hipSuccess;
