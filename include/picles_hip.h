@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 13
+#define PICLES_ABI_VERSION 14
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -577,6 +577,57 @@ int32_t picles_nest_feedback_init(picles_ctx *child, int32_t n_fb, const int32_t
 int32_t picles_nest_feedback(picles_ctx *child);
 int32_t picles_nest_feedback_info(const picles_ctx *child, int32_t *n_fb, int32_t *n_src, int32_t *m, int64_t *taken);
 int32_t picles_nest_feedback_free(picles_ctx *child);
+
+/* ---- track samples (ABI 14): sea state along moving platforms — altimeter passes, ships, drifting buoys — sampled on
+ * the device.  Every observation is an EVENT with its own time and place (t_k, x_k, y_k); this output is addressed by event, not by node
+ * and cadence: behind each step only the events whose time lies next to the clock are sampled, and their four corners are mixed on the
+ * device into a table that stays in device memory. ----
+ * THE SET.  A context holds at most one track set of m >= 1 events: t[m] the event times, finite and nondecreasing; ij[8 m] the corner
+ * nodes as planes — ij[c m + k] the global 0-based i of corner c of event k, ij[(4 + c) m + k] its j, c = 0..3 in the visiting order of
+ * picles_amd.station_output.locate_points —; w[4 m] the weights, w[c m + k], finite and >= 0; and the HORIZON H > 0, the longest step
+ * that will be taken while the set lives.  The geometry is the host's: no coordinate arithmetic on the device.
+ * THE TABLE.  Per event 8 doubles, as 8 planes of m: planes 0-3 e_b, mx_b, my_b, t_b (the BEFORE slot), planes 4-7 e_a, mx_a, my_a, t_a
+ * (the AFTER slot).  Every entry is NaN after init.
+ * A TRACK SAMPLE at the clock T visits exactly the events with  T - H < t_k < T + H  (T - H and T + H one IEEE operation each): the
+ * library keeps a host copy of t and finds that contiguous range by binary search; when it is empty nothing is launched.  Per visited
+ * event (E, MX, MY) is the station definition of the nesting section above over its four corners in order — a corner is WET when e, m_x,
+ * m_y are finite, e > 0 and m_x*m_x + m_y*m_y > 0;  W = SE = SX = SY = +0.0;  for c = 0..3, if wet:  W = W + w;  SE = SE + w*e;
+ * SX = SX + w*m_x;  SY = SY + w*m_y;  E = SE / W;  MX = SX / W;  MY = SY / W;  valid when W > 0 and MX*MX + MY*MY > 0, otherwise NaN in
+ * all three; every operation one IEEE operation — where a corner's value is what picles_get_state would return for that node at that
+ * moment.  Then
+ *     if t_k >= T:                         the before slot becomes (E, MX, MY, T), overwriting what was there
+ *     if t_k <= T and t_a is still NaN:    the after slot becomes (E, MX, MY, T)
+ * With sample clocks no farther apart than H, an event inside the sampled span ends with before = the latest sample at a clock <= t_k
+ * and after = the earliest sample at a clock >= t_k; an event on a clock gets both slots from that one sample.  The host interpolates.
+ * Taking a sample has the rules of a probe sample: it does NOT complete a pending fused step, does not synchronise the host, and leaves
+ * State, particles, counters, reach counters, class map, dispatch order and clock untouched; with a fused step pending the corner
+ * values are formed from that step's scatter records by the pull k_scatter would run for the node, otherwise read from State.
+ * AUTOMATIC SAMPLING: picles_time_step and picles_run_steps take a sample behind every model step they complete, at the clock after the
+ * tick, on the context stream, where the automatic probe sample sits.  A step longer than H is refused (-2) before anything is enqueued;
+ * picles_run_steps checks up front.  The split-phase calls do not sample.
+ *
+ *   init:        refuses (context unchanged, picles_last_error set) m < 1, 8 m beyond INT32_MAX, t unsorted or not finite, a node off
+ *                the grid, a weight that is negative or not finite, a horizon that is not finite or <= 0, a second init without
+ *                picles_track_free, and a context that is a slab, is in slab mode, is on the native ring, has j_begin > 0 or fewer rows
+ *                than the grid.  Everything the set needs is allocated here (the fetch staging apart); the arrays are free on return
+ *   sample:      one sample now at picles_clock(ctx), on `stream` (NULL: the context stream): picles_probe_sample's semantics.
+ *                Refuses: no set
+ *   fetch_begin: behind the work enqueued on the context stream so far, gathers the 8 planes of the events [k0, k0 + n) — as they are
+ *                at that point of the stream — and starts their copy into pinned staging (grown lazily) on the store stream behind an
+ *                event.  Refuses: no set, a fetch already open, a range outside [0, m)
+ *   fetch_end:   waits for that copy only and hands out 8 n doubles, [plane][event]; steps enqueued after fetch_begin overlap the copy
+ *                and are not waited for.  Refuses: no set, no fetch open
+ *   info:        m, the horizon, the samples taken so far — those that visited no event included — (any pointer may be NULL; -1, and
+ *                -1 in *m, without a set; no device work)
+ *   free:        drops the set so that a new one may be created; picles_destroy does it too, an open fetch included
+ * The set is no part of the checkpoint blob or its fingerprint; picles_checkpoint_load and picles_seed leave the set and its table as
+ * they are.  picles_set_slab_mode(on) and picles_slab_comm_init refuse (-5) a context that holds a set. */
+int32_t picles_track_init(picles_ctx *ctx, int32_t m, const double *t, const int32_t *ij, const double *w, double horizon);
+int32_t picles_track_sample(picles_ctx *ctx, void *stream);
+int32_t picles_track_fetch_begin(picles_ctx *ctx, int32_t k0, int32_t n);
+int32_t picles_track_fetch_end(picles_ctx *ctx, double *out);
+int32_t picles_track_info(const picles_ctx *ctx, int32_t *m, double *horizon, int64_t *samples_taken);
+int32_t picles_track_free(picles_ctx *ctx);
 
 /* particles (own rows; z is 5 planes: lne, c̄x, c̄y, x, y). Any pointer may be NULL.
  * The state vector of a switched-off particle (on == 0) is dead storage: its content is unspecified. */

@@ -101,7 +101,7 @@ LATTICE_LINEAR, LATTICE_SMOOTH3 = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 13
+ABI_VERSION = 14
 SLAB_ID_BYTES = 128
 PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
 
@@ -192,6 +192,12 @@ SYMBOLS = {
     "picles_nest_feedback": (C.c_int32, [_VP]),
     "picles_nest_feedback_info": (C.c_int32, [_VP, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_int64)]),
     "picles_nest_feedback_free": (C.c_int32, [_VP]),
+    "picles_track_init": (C.c_int32, [_VP, C.c_int32, c_double_p, c_int32_p, c_double_p, C.c_double]),
+    "picles_track_sample": (C.c_int32, [_VP, _VP]),
+    "picles_track_fetch_begin": (C.c_int32, [_VP, C.c_int32, C.c_int32]),
+    "picles_track_fetch_end": (C.c_int32, [_VP, c_double_p]),
+    "picles_track_info": (C.c_int32, [_VP, c_int32_p, c_double_p, C.POINTER(C.c_int64)]),
+    "picles_track_free": (C.c_int32, [_VP]),
     "picles_get_particles": (C.c_int32, [_VP, c_double_p, c_uint8_p, c_uint8_p, c_int32_p]),
     "picles_set_particles": (C.c_int32, [_VP, c_double_p, c_uint8_p]),
     "picles_get_counters": (C.c_int32, [_VP, C.POINTER(PiclesCounters)]),

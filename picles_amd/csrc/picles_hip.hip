@@ -61,6 +61,7 @@
 #include "k_probe.h"
 #include "k_stat.h"
 #include "k_nest.h"
+#include "k_track.h"
 
 /* ------------------------------------------------------------------------------------------
  * k_seed — init_particles! / SeedParticle / InitParticleValues / init_z0_to_State!
@@ -605,6 +606,7 @@ struct picles_ctx {
     int probe_n = 0;
     int *probe_nodes = nullptr;                    /* device: i plane, then the LOCAL row plane */
     Cadence probe_cad;                             /* steps: model steps completed since picles_probe_init */
+    struct Track *trk = nullptr;                   /* track samples (picles_track_*; struct Track behind the station probes): nullptr without a set */
     /* run statistics (picles_stat_*): one device block of accumulator planes — the fp64 planes of the selected groups first (PEAK,
      * then MEAN), then the uint32 planes (n_wet, then n_exc[k]) —, the host-side scalars, and the event behind the latest
      * operation on the planes (update, reset, upload): operations on another stream wait for it, and so does picles_stat_get */
@@ -768,6 +770,10 @@ static int launch_scatter(picles_ctx *c, hipStream_t s, bool remesh);
 static int probe_room(picles_ctx *c, long long n_steps, const char *who);
 static int probe_take(picles_ctx *c, hipStream_t s);
 static void probe_release(picles_ctx *c);
+/* track samples (defined behind the station probes) */
+static int track_step_ok(picles_ctx *c, double dt, const char *who);
+static int track_take(picles_ctx *c, hipStream_t s);
+static void track_release(picles_ctx *c);
 /* run statistics (defined behind the station probes) */
 static int stat_update(picles_ctx *c, hipStream_t s);
 static void stat_release(picles_ctx *c);
@@ -1027,6 +1033,8 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     c->store.release();
     c->diag_ring.release();
     probe_release(c);
+    if (c->trk) hipDeviceSynchronize();         /* samples issued on caller streams write the table about to go */
+    track_release(c);
     if (c->stat_on) hipDeviceSynchronize();     /* updates issued on caller streams read and write the planes about to go */
     stat_release(c);
     bforce_release(c);
@@ -1842,11 +1850,14 @@ PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     { int rc = probe_room(c, 1, "picles_time_step"); if (rc) return rc; }      /* refused before anything has changed */
     { int rc = bforce_window(c, dt, 1, "picles_time_step"); if (rc) return rc; }
+    { int rc = track_step_ok(c, dt, "picles_time_step"); if (rc) return rc; }
     int rc = time_step_phases(c, dt, flags);
     if (rc) return rc;
     /* the sample of this step: directly behind its launch on the context stream.  The next step's launch reads the record buffer
      * the probe reads and writes the other one: stream order is all the ordering there is */
     if (c->probe_n && c->probe_cad.due(c->probe_cad.steps)) { if ((rc = probe_take(c, c->stream))) return rc; }
+    /* the track sample of this step, at the clock after the tick: the same place, the same ordering */
+    if (c->trk && (rc = track_take(c, c->stream))) return rc;
     /* the statistics update of this step: the same place, the same ordering */
     if (c->stat_on && c->stat_cad.due(c->stat_cad.steps)) return stat_update(c, c->stream);
     return 0;
@@ -1857,6 +1868,7 @@ PX_EXPORT int32_t picles_run_steps(picles_ctx *c, double dt, int32_t n_steps)
     if (!c || n_steps < 0) return -1;
     if (c->G.single_slab && dt > 0.0) { int rc = probe_room(c, n_steps, "picles_run_steps"); if (rc) return rc; }   /* up front, not half-way */
     if (c->G.single_slab && dt > 0.0) { int rc = bforce_window(c, dt, n_steps, "picles_run_steps"); if (rc) return rc; }   /* every start time, before anything is enqueued */
+    if (n_steps > 0) { int rc = track_step_ok(c, dt, "picles_run_steps"); if (rc) return rc; }
     const bool region = c->timing && c->timing_mode == 2 && n_steps > 0;
     if (region) {      /* one event pair around the whole call, on the stream the launches go to */
         HIPCHK(c, hipSetDevice(c->device));
@@ -2362,6 +2374,187 @@ PX_EXPORT int32_t picles_probe_free(picles_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());       /* probe launches and copies in flight read and write the buffers about to go */
     probe_release(c);
+    return 0;
+}
+
+/* ---- track samples (the contract: include/picles_hip.h; the kernel: k_track.h) ---- */
+struct Track {
+    int m = 0;
+    double H = 0.0;                                /* the horizon: the longest step taken while the set lives */
+    long long samples = 0;                         /* samples taken, those that visited no event included */
+    std::vector<double> t;                         /* host copy of the event times: the range of a sample is found here */
+    double *d_t = nullptr, *d_w = nullptr, *table = nullptr;      /* device: m times, 4 m weights, the 8 planes of m */
+    int *d_ij = nullptr;                           /* device: 8 planes of m, i of the four corners, then their row */
+    /* the fetch: a device block the range is gathered into on the context stream, its pinned twin, the ring's two events */
+    double *stage_dev = nullptr, *stage_host = nullptr;
+    size_t stage_cap = 0;                          /* doubles either block holds */
+    hipEvent_t ready = nullptr, done = nullptr;
+    bool open = false;
+    int fetch_n = 0;
+};
+
+/* is a step of dt allowed under the set's horizon?  Asked by the step entry points before they change anything */
+static int track_step_ok(picles_ctx *c, double dt, const char *who)
+{
+    if (!c->trk || !(dt > c->trk->H)) return 0;
+    return fail(c, -2, std::string(who) + ": a step of " + std::to_string(dt) + " s is longer than the horizon of the track set (" +
+                           std::to_string(c->trk->H) + " s): events between two samples would be missed");
+}
+
+/* one sample at the clock as it stands, on stream s: the events with T - H < t_k < T + H, a contiguous range of the sorted times.
+ * probe_launch's choice between the records of a pending fused step and State; nothing of the model is touched, the host does not wait */
+static int track_take(picles_ctx *c, hipStream_t s)
+{
+    Track *K = c->trk;
+    const double T = c->clock, lo = T - K->H, hi = T + K->H;
+    const int k0 = (int)(std::upper_bound(K->t.begin(), K->t.end(), lo) - K->t.begin());      /* the first t_k > T - H */
+    const int k1 = (int)(std::lower_bound(K->t.begin(), K->t.end(), hi) - K->t.begin());      /* the first t_k >= T + H */
+    K->samples++;
+    if (k1 <= k0) return 0;
+    const dim3 grid(nblocks(4LL * (k1 - k0), TRACK_BLOCK)), block(TRACK_BLOCK);
+    if (c->pending)
+        hipLaunchKernelGGL(k_track<true>, grid, block, 0, s, c->G, arrays_for(c, c->cur, c->cur), k0, k1, K->m, T, (const double *)K->d_t,
+                           (const int *)K->d_ij, (const double *)K->d_w, K->table);
+    else
+        hipLaunchKernelGGL(k_track<false>, grid, block, 0, s, c->G, c->A, k0, k1, K->m, T, (const double *)K->d_t, (const int *)K->d_ij,
+                           (const double *)K->d_w, K->table);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+static void track_release(picles_ctx *c)
+{
+    Track *K = c->trk;
+    if (!K) return;
+    if (K->d_t) hipFree(K->d_t);
+    if (K->d_w) hipFree(K->d_w);
+    if (K->d_ij) hipFree(K->d_ij);
+    if (K->table) hipFree(K->table);
+    if (K->stage_dev) hipFree(K->stage_dev);
+    if (K->stage_host) hipHostFree(K->stage_host);
+    if (K->ready) hipEventDestroy(K->ready);
+    if (K->done) hipEventDestroy(K->done);
+    delete K;
+    c->trk = nullptr;
+}
+
+PX_EXPORT int32_t picles_track_init(picles_ctx *c, int32_t m, const double *t, const int32_t *ij, const double *w, double horizon)
+{
+    if (!c) return -1;
+    if (c->trk) return fail(c, -2, "picles_track_init: a track set exists (picles_track_free first)");
+    const GridP &G = c->G;
+    if (!G.single_slab || c->ring || G.j_begin > 0 || G.ny_loc < G.Ny)
+        return fail(c, -5, "picles_track_init: track samples need a whole-grid context (no slab, no slab mode, no native ring): the corners of an event may lie on two slabs");
+    if (m < 1 || !t || !ij || !w) return fail(c, -2, "picles_track_init: m must be >= 1 and times, corners and weights given");
+    if ((long long)m * 8 > (long long)INT32_MAX) return fail(c, -2, "picles_track_init: 8 m must not exceed INT32_MAX");
+    if (!std::isfinite(horizon) || !(horizon > 0.0)) return fail(c, -2, "picles_track_init: the horizon must be finite and positive");
+    for (int k = 0; k < m; k++)
+        if (!std::isfinite(t[k]) || (k > 0 && t[k] < t[k - 1]))
+            return fail(c, -2, "picles_track_init: event " + std::to_string(k) + ": times must be finite and nondecreasing");
+    for (int q = 0; q < 4; q++)
+        for (int k = 0; k < m; k++) {
+            const int i = ij[(size_t)q * m + k], j = ij[(size_t)(4 + q) * m + k];
+            if (i < 0 || i >= G.Nx || j < 0 || j >= G.Ny)
+                return fail(c, -2, "picles_track_init: event " + std::to_string(k) + ", corner " + std::to_string(q) + " = (" + std::to_string(i) +
+                                       ", " + std::to_string(j) + ") lies outside the grid");
+            const double wk = w[(size_t)q * m + k];
+            if (!std::isfinite(wk) || wk < 0.0)
+                return fail(c, -2, "picles_track_init: event " + std::to_string(k) + ", corner " + std::to_string(q) + ": weights must be finite and >= 0");
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    Track *K = new Track();
+    c->trk = K;
+    Undo undo{[c] { track_release(c); }};
+    { int rc = store_stream_get(c); if (rc) return rc; }
+    const size_t M = (size_t)m;
+    HIPCHK(c, hipMalloc(&K->d_t, M * sizeof(double)));
+    HIPCHK(c, hipMalloc(&K->d_ij, 8 * M * sizeof(int)));
+    HIPCHK(c, hipMalloc(&K->d_w, 4 * M * sizeof(double)));
+    HIPCHK(c, hipMalloc(&K->table, 8 * M * sizeof(double)));
+    HIPCHK(c, hipEventCreateWithFlags(&K->ready, hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&K->done, hipEventDisableTiming));
+    /* blocking uploads: the caller's arrays are free on return (whole-grid context: a global row is the local row) */
+    HIPCHK(c, hipMemcpy(K->d_t, t, M * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(K->d_ij, ij, 8 * M * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(K->d_w, w, 4 * M * sizeof(double), hipMemcpyHostToDevice));
+    /* every entry NaN: a double of all-one bits is one.  Complete on return, whatever stream the first sample rides */
+    HIPCHK(c, hipMemsetAsync(K->table, 0xFF, 8 * M * sizeof(double), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    K->t.assign(t, t + m);
+    K->m = m;
+    K->H = horizon;
+    undo.armed = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_track_info(const picles_ctx *c, int32_t *m, double *horizon, int64_t *samples_taken)
+{
+    if (!c || !c->trk) { if (m) *m = -1; return -1; }
+    if (m) *m = c->trk->m;
+    if (horizon) *horizon = c->trk->H;
+    if (samples_taken) *samples_taken = (int64_t)c->trk->samples;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_track_sample(picles_ctx *c, void *stream)
+{
+    if (!c) return -1;
+    if (!c->trk) return fail(c, -2, "picles_track_init first");
+    HIPCHK(c, hipSetDevice(c->device));
+    return track_take(c, stream ? (hipStream_t)stream : c->stream);
+}
+
+PX_EXPORT int32_t picles_track_fetch_begin(picles_ctx *c, int32_t k0, int32_t n)
+{
+    if (!c) return -1;
+    Track *K = c->trk;
+    if (!K) return fail(c, -2, "picles_track_init first");
+    if (K->open) return fail(c, -2, "picles_track_fetch_begin: a fetch is open (picles_track_fetch_end first)");
+    if (k0 < 0 || n < 1 || (long long)k0 + n > (long long)K->m)
+        return fail(c, -2, "picles_track_fetch_begin: events [" + std::to_string(k0) + ", " + std::to_string((long long)k0 + n) + ") lie outside [0, " +
+                               std::to_string(K->m) + ")");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t need = (size_t)8 * n;
+    if (need > K->stage_cap) {      /* grown lazily; no copy is in flight: the last fetch was ended */
+        if (K->stage_dev) hipFree(K->stage_dev);
+        if (K->stage_host) hipHostFree(K->stage_host);
+        K->stage_dev = K->stage_host = nullptr;
+        K->stage_cap = 0;
+        HIPCHK(c, hipMalloc(&K->stage_dev, need * sizeof(double)));
+        HIPCHK(c, hipHostMalloc(&K->stage_host, need * sizeof(double), hipHostMallocDefault));
+        K->stage_cap = need;
+    }
+    /* the range as it is at this point of the context stream, gathered into the staging block behind the samples enqueued so far;
+     * the leg to the host rides the store stream beside whatever is enqueued next (samples that rewrite the table included) */
+    for (int p = 0; p < 8; p++)
+        HIPCHK(c, hipMemcpyAsync(K->stage_dev + (size_t)p * n, K->table + (size_t)p * K->m + k0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    { int rc = ship_d2h(c, c->stream, K->ready, K->done, K->stage_host, K->stage_dev, need * sizeof(double)); if (rc) return rc; }
+    K->fetch_n = n;
+    K->open = true;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_track_fetch_end(picles_ctx *c, double *out)
+{
+    if (!c) return -1;
+    Track *K = c->trk;
+    if (!K) return fail(c, -2, "picles_track_init first");
+    if (!K->open) return fail(c, -2, "picles_track_fetch_end: no fetch is open (picles_track_fetch_begin first)");
+    if (!out) return fail(c, -2, "picles_track_fetch_end: out must be given");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipEventSynchronize(K->done));      /* this copy alone: later steps stay enqueued */
+    memcpy(out, K->stage_host, (size_t)8 * K->fetch_n * sizeof(double));
+    K->open = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_track_free(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->trk) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());       /* samples and copies in flight read and write the buffers about to go */
+    track_release(c);
     return 0;
 }
 
@@ -3229,6 +3422,7 @@ PX_EXPORT int32_t picles_set_slab_mode(picles_ctx *c, int32_t on)
     if (!(G.j_begin == 0 && G.ny_loc == G.Ny)) return on ? 0 : fail(c, -2, "a partial slab cannot resolve the y wrap locally");
     if (c->pending || c->seeded) return fail(c, -2, "picles_set_slab_mode: call before picles_seed");
     if (on && c->bf_n) return fail(c, -5, std::string("picles_set_slab_mode") + BFORCE_NO_SLABS);
+    if (on && c->trk) return fail(c, -5, "picles_set_slab_mode: the context holds a track set (picles_track_free first): the corners of an event may lie on two slabs");
     if (on && !c->nest_children.empty()) return fail(c, -5, "picles_set_slab_mode: the context is the parent of a nest (picles_nest_free on its children first)");
     if (on) {
         if ((G.periodic_y && G.Ny <= 2 * G.R) || G.ny_loc < G.R)
@@ -3385,6 +3579,7 @@ PX_EXPORT int32_t picles_slab_comm_init(picles_ctx *c, const void *id128, int32_
     if (world < 1 || rank < 0 || rank >= world) return fail(c, -2, "slab ring: need 0 <= rank < world");
     if (c->ring) return fail(c, -2, "slab ring already initialised");
     if (c->bf_n) return fail(c, -5, std::string("picles_slab_comm_init") + BFORCE_NO_SLABS);
+    if (c->trk) return fail(c, -5, "picles_slab_comm_init: the context holds a track set (picles_track_free first): the corners of an event may lie on two slabs");
     if (!c->nest_children.empty()) return fail(c, -5, "picles_slab_comm_init: the context is the parent of a nest (picles_nest_free on its children first)");
     if (c->G.single_slab && world > 1) return fail(c, -2, "slab ring of several ranks needs slab contexts (j_begin, j_end)");
     if (c->G.tripolar) return fail(c, -5, "slab ring: the tripolar fold is not wired into the native ring (use picles_amd.parallel)");

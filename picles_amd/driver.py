@@ -523,6 +523,51 @@ class HipModel:
     def probe_free(self):
         self._ck(self.lib.picles_probe_free(self.h), "picles_probe_free")
 
+    # ---- track samples (picles_track_*: sea state at events along moving platforms, kept in a table on the device) ----
+    def track_init(self, times, corners_ij, weights, horizon):
+        """times: (m,) nondecreasing; corners_ij: (8, m) int, the i of the four corners then their j (global, 0-based, in the
+        visiting order of station_output.locate_points); weights: (4, m), finite and >= 0; horizon: the longest step to come"""
+        t = np.ascontiguousarray(times, dtype=np.float64)
+        ij = np.asarray(corners_ij, dtype=np.int64)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        m = t.shape[0] if t.ndim == 1 else -1
+        if m < 0 or ij.shape != (8, m) or w.shape != (4, m):
+            raise ValueError("track_init: times (m,), corners_ij (8, m) and weights (4, m) are needed")
+        if ij.size and np.abs(ij).max() > 2**31 - 1:
+            raise ValueError("track_init: node index out of the int32 range")
+        if m > (2**31 - 1) // 8:
+            raise ValueError("track_init: 8 m must not exceed INT32_MAX")
+        planes = np.ascontiguousarray(ij.astype(np.int32))
+        self._ck(self.lib.picles_track_init(self.h, int(m), K.dptr(t), planes.ctypes.data_as(K.c_int32_p), K.dptr(w), float(horizon)),
+                 "picles_track_init")
+
+    def track_info(self):
+        """(m, horizon, samples taken) of the track set; no device work"""
+        m, h, s = C.c_int32(), C.c_double(), C.c_int64()
+        if self.lib.picles_track_info(self.h, C.byref(m), C.byref(h), C.byref(s)) != 0:
+            raise K.PiclesError("picles_track_info failed: track_init first")
+        return m.value, h.value, s.value
+
+    def track_sample(self, stream=None):
+        """one sample now, at the model clock (the seeded state; callers of the split-phase API, on the stream their step is ordered on)"""
+        self._ck(self.lib.picles_track_sample(self.h, stream), "picles_track_sample")
+
+    def track_fetch_begin(self, k0, n):
+        """start the copy of the table's 8 planes of the events [k0, k0 + n), as they are behind the work enqueued so far"""
+        self._ck(self.lib.picles_track_fetch_begin(self.h, int(k0), int(n)), "picles_track_fetch_begin")
+        self._track_fetch_n = int(n)
+
+    def track_fetch_end(self):
+        """wait for that copy alone: (8, n) float64, rows e_b, mx_b, my_b, t_b, e_a, mx_a, my_a, t_a"""
+        out = np.empty((8, getattr(self, "_track_fetch_n", 0) or 1))
+        self._ck(self.lib.picles_track_fetch_end(self.h, K.dptr(out)), "picles_track_fetch_end")
+        self._track_fetch_n = 0
+        return out
+
+    def track_free(self):
+        self._track_fetch_n = 0
+        self._ck(self.lib.picles_track_free(self.h), "picles_track_free")
+
     # ---- run statistics (picles_stat_*: per-node peak / mean / exceedance accumulators kept on the device, the fused path kept) ----
     def stat_init(self, groups=K.STAT_ALL, thresholds=(), every=1, first=1):
         """groups: PICLES_STAT_* bits or names ("peak", "mean", "exceed"); thresholds: 1 ... 4 ascending Hs values with "exceed";

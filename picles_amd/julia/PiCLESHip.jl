@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(13)
+const PICLES_ABI_VERSION = Int32(14)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -499,6 +499,53 @@ function probe_pop!(model::WaveGrowth2DHIP; max_samples::Integer=typemax(Int32))
 end
 
 probe_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_probe_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_probe_free")
+
+"""
+    track_init!(model, times, corners, weights, horizon)
+    track_sample!(model); track_fetch_begin!(model, k0, n); track_fetch_end!(model, n); track_info(model); track_free!(model)
+
+Track samples (`picles_track_*`, the contract is in include/picles_hip.h): the sea state at events `(t_k, x_k, y_k)` along moving
+platforms.  `times` is sorted; `corners` is an `m × 4` matrix of 1-based `(i, j)` tuples and `weights` an `m × 4` matrix, in the
+visiting order of `locate_points` (picles_amd/station_output.py); `horizon` is the longest step to come.  Behind every step the
+library samples the events whose time lies next to the clock and keeps, per event, the latest sample before and the earliest after
+it in a table on the device.  `track_fetch_begin!` (0-based first event `k0`, `n` events) starts the copy of a range of the table,
+`track_fetch_end!` hands it out as an `n × 8` matrix (columns e_b, mx_b, my_b, t_b, e_a, mx_a, my_a, t_a).
+"""
+function track_init!(model::WaveGrowth2DHIP, times::AbstractVector{<:Real}, corners::AbstractMatrix, weights::AbstractMatrix{<:Real}, horizon::Real)
+    m = length(times)
+    size(corners) == (m, 4) && size(weights) == (m, 4) || error("track_init!: corners and weights must be m × 4")
+    t = Vector{Float64}(times)
+    ij = Vector{Int32}(undef, 8m)
+    w = Vector{Float64}(undef, 4m)
+    for c in 1:4, k in 1:m
+        ij[(c - 1) * m + k] = Int32(corners[k, c][1] - 1); ij[(3 + c) * m + k] = Int32(corners[k, c][2] - 1)
+        w[(c - 1) * m + k] = Float64(weights[k, c])
+    end
+    check(model.ctx, ccall((:picles_track_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Float64), model.ctx, m, t, ij, w, horizon), "picles_track_init")
+    nothing
+end
+
+track_sample!(model::WaveGrowth2DHIP) =
+    check(model.ctx, ccall((:picles_track_sample, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), model.ctx, C_NULL), "picles_track_sample")
+
+track_fetch_begin!(model::WaveGrowth2DHIP, k0::Integer, n::Integer) =
+    check(model.ctx, ccall((:picles_track_fetch_begin, libpicles), Int32, (Ptr{Cvoid}, Int32, Int32), model.ctx, k0, n), "picles_track_fetch_begin")
+
+function track_fetch_end!(model::WaveGrowth2DHIP, n::Integer)
+    out = Matrix{Float64}(undef, n, 8)
+    check(model.ctx, ccall((:picles_track_fetch_end, libpicles), Int32, (Ptr{Cvoid}, Ptr{Float64}), model.ctx, out), "picles_track_fetch_end")
+    out
+end
+
+"`(m, horizon, samples_taken)` of the track set"
+function track_info(model::WaveGrowth2DHIP)
+    m, h, s = Ref{Int32}(0), Ref{Float64}(0.0), Ref{Int64}(0)
+    ccall((:picles_track_info, libpicles), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}, Ref{Int64}), model.ctx, m, h, s) == 0 ||
+        error("picles_track_info failed: track_init! first")
+    Int(m[]), h[], Int(s[])
+end
+
+track_free!(model::WaveGrowth2DHIP) = check(model.ctx, ccall((:picles_track_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_track_free")
 
 """
     bforce_init!(model, nodes; band=false, weights=nothing)
