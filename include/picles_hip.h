@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 14
+#define PICLES_ABI_VERSION 15
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -533,6 +533,30 @@ int32_t picles_nest_init(picles_ctx *child, picles_ctx *parent, int32_t n_corner
 int32_t picles_nest_sample(picles_ctx *child);
 int32_t picles_nest_info(const picles_ctx *child, int32_t *n_corner, int64_t *samples);
 int32_t picles_nest_free(picles_ctx *child);
+
+/* ---- a child started from its parent (ABI 15): the State of `parent` at its clock t, prolonged onto EVERY node of `child`,
+ * and the child's particles made from it — a child switched on beside a parent that has been running, instead of seeded cold at t = 0. ----
+ * THE GEOMETRY is the host's and separable: per child column i the parent columns ix0[i], ix1[i] and the weight wx[i] (ncx entries, the
+ * child's Nx), per child row j the parent rows iy0[j], iy1[j] and wy[j] (ncy entries) — picles_amd.station_output._axis of the child's
+ * node coordinates in the parent.  A periodic parent's wrap cell is ix0 = Nx - 1, ix1 = 0.  Per child node (i, j), every operation one
+ * IEEE operation in the order written:
+ *     gx = 1 - wx[i];  gy = 1 - wy[j];  the corners in visiting order (ix0, iy0), (ix1, iy0), (ix0, iy1), (ix1, iy1) with the weights
+ *     gx*gy, wx*gy, gx*wy, wx*wy;  over them the station definition of "one-way nesting" above: the wet test, the serial sums, E, MX, MY
+ *     a VALID node's State is (E, MX, MY); any other node's is (0, 0, 0) — a calm node, whose particle the remesh makes from the local
+ *     wind.  Every child node is written, whatever its mask class.
+ * THE CALL, in this order: completes the parent's pending step (on the parent's stream; the host waits as picles_get_state would not:
+ * nothing is copied); resets the child as picles_seed(child, t) resets it — clock t, no step pending, record buffers, reach words,
+ * class map and counters zeroed, every particle seeded under the wind at t with fresh controller memory; a child under a wind lattice
+ * samples the two-level window [t, t + dt] first, as picles_seed does at 0.0, a child under host-set winds keeps the window it holds
+ * —; orders the child's stream behind the parent's with an event; writes the child's State (k_nest_prolong, picles_amd/csrc/k_nest.h)
+ * and remeshes it (picles_remesh(child, dt): branches A-D at clock t).  It returns after enqueueing.  What the child holds afterwards
+ * is, bit for bit, what picles_seed(child, t), picles_set_state(child, <the prolonged State>), picles_remesh(child, dt) leave.
+ *   refuses (-2 / -5, both contexts as they were, picles_last_error(child) has the text): child == parent, different devices, either
+ *   context a slab, in slab mode or on a native ring, either context that has run on caller-provided streams, dt <= 0, a table that
+ *   is missing, an index outside the parent's grid, a weight that is not finite or lies outside [0, 1].  The tables are free on
+ *   return; the child keeps a device copy until the next call or picles_destroy.  A forcing set or a nest of the child is not touched. */
+int32_t picles_nest_prolong(picles_ctx *child, picles_ctx *parent, const int32_t *ix0, const int32_t *ix1, const double *wx,
+                            const int32_t *iy0, const int32_t *iy1, const double *wy, double dt);
 
 /* ---- two-way nesting: the child's sea state fed back into its parent.  A nested child (picles_nest_init) may feed back: the library
  * makes a forcing set on the PARENT — its ocean nodes under the child — whose one level is the child's State restricted onto them,

@@ -71,4 +71,49 @@ __global__ void __launch_bounds__(NEST_BLOCK) k_nest_restrict(int n, int n_src, 
     nest_stencil<0>(n, n_src, m, index, weight, src, out);
 }
 
+/*
+ * k_nest_prolong (picles_nest_prolong: a child started from its parent): the parent's State, in memory, onto EVERY
+ * node of the child.  One lane per child node, i fastest; the stencil is separable, so a lane loads the table row of its column
+ * (ix0, ix1, wx) and of its row (iy0, iy1, wy) once and forms the four weights itself, in locate_points' order and with its
+ * operations: gx = 1 - wx, gy = 1 - wy; gx*gy, wx*gy, gx*wy, wx*wy.  The twelve parent values are gathers from the parent's State
+ * planes (neighbouring lanes share corners); three coalesced plane stores.  The station definition above, restated here and not
+ * shared with nest_stencil (so that k_nest_mix and k_nest_restrict compile to what they were): the same wet test, serial sums and
+ * three divisions, one rounding each.  A node that is not VALID is written as (0, 0, 0), not NaN: State is read by the remesh,
+ * which makes a calm node's particle from the local wind, as it does for a node nothing was deposited on after any step.
+ * np_x: the parent's Nx; n_par = its node count (the plane stride); the indices were checked on the host.
+ */
+__global__ void __launch_bounds__(NEST_BLOCK) k_nest_prolong(int ncx, int ncy, int np_x, long long n_par, const int *__restrict__ ix0,
+                                                             const int *__restrict__ ix1, const double *__restrict__ wx, const int *__restrict__ iy0,
+                                                             const int *__restrict__ iy1, const double *__restrict__ wy,
+                                                             const double *__restrict__ src, double *__restrict__ out)
+{
+    const long long n = (long long)ncx * ncy;
+    const long long p = (long long)blockIdx.x * NEST_BLOCK + threadIdx.x;
+    if (p < n) {
+        const int i = (int)(p % ncx), j = (int)(p / ncx);
+        const int a0 = ix0[i], a1 = ix1[i], b0 = iy0[j], b1 = iy1[j];
+        const double fx = wx[i], fy = wy[j];
+        const double gx = 1.0 - fx, gy = 1.0 - fy;
+        const double w4[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+        const long long q4[4] = {(long long)b0 * np_x + a0, (long long)b0 * np_x + a1, (long long)b1 * np_x + a0, (long long)b1 * np_x + a1};
+        double W = 0.0, SE = 0.0, SX = 0.0, SY = 0.0;
+        for (int c = 0; c < 4; c++) {
+            const double w = w4[c];
+            const double e = src[q4[c]], mx = src[n_par + q4[c]], my = src[2 * n_par + q4[c]];
+            if (pm_isfinite(e) && pm_isfinite(mx) && pm_isfinite(my) && e > 0.0 && mx * mx + my * my > 0.0) {
+                W = W + w;
+                SE = SE + w * e;
+                SX = SX + w * mx;
+                SY = SY + w * my;
+            }
+        }
+        const double E = SE / W, MX = SX / W, MY = SY / W;
+        const double M2 = MX * MX + MY * MY;
+        const bool valid = W > 0.0 && M2 > 0.0;
+        out[p] = valid ? E : 0.0;
+        out[n + p] = valid ? MX : 0.0;
+        out[2 * n + p] = valid ? MY : 0.0;
+    }
+}
+
 #endif /* PICLES_K_NEST_H */

@@ -640,7 +640,9 @@ struct picles_ctx {
     struct Feedback *fb = nullptr;
     std::vector<picles_ctx *> nest_children;
     picles_ctx *fb_child = nullptr;
-    WindWindow wind;               /* the wind window: host-set levels or the device-sampled lattice */
+    double *prolong_tab = nullptr; /* picles_nest_prolong: wx, wy, then ix0, ix1, iy0, iy1 of the latest call (a launch may still read them) */
+    size_t prolong_cap = 0;        /* its size in bytes */
+    WindWindow wind;              /* the wind window: host-set levels or the device-sampled lattice */
     bool ord_valid = false;        /* the previous fused step filed a dispatch order (kernels.h: Arrays::ord) with ... */
     int ord_nblk = 0;              /* ... this many workgroups: the whole grid, or the interior rows of a slab */
     bool ext_streams = false;      /* a caller-provided stream has been used: order across streams with device syncs */
@@ -1038,6 +1040,7 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     if (c->stat_on) hipDeviceSynchronize();     /* updates issued on caller streams read and write the planes about to go */
     stat_release(c);
     bforce_release(c);
+    if (c->prolong_tab) hipFree(c->prolong_tab);
     if (c->ck_dev) hipFree(c->ck_dev);
     if (c->ck_host) hipHostFree(c->ck_host);
     if (c->ck_ready) hipEventDestroy(c->ck_ready);
@@ -1427,9 +1430,10 @@ PX_EXPORT int32_t picles_get_winds_mid(picles_ctx *c, double *um, double *vm)
     return 0;
 }
 
-PX_EXPORT int32_t picles_seed(picles_ctx *c, double t0)
+/* picles_seed at clock t0; a lattice is sampled as the two-level window [wind_t, wind_t + wind_dt] (picles_seed: at 0.0 with the seed
+ * time scale; picles_nest_prolong: at t0 with the step to come) */
+static int seed_at(picles_ctx *c, double t0, double wind_t, double wind_dt)
 {
-    if (!c) return -1;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* earlier steps may still run on caller / ring streams */
     c->clock = t0;
@@ -1439,7 +1443,7 @@ PX_EXPORT int32_t picles_seed(picles_ctx *c, double t0)
         c->wind.invalidate();
         WindWindow::Shape two;
         two.form = WindWindow::TWO;
-        int rc = c->wind.sample(c, two, 0.0, c->od.timestep, true, c->stream);
+        int rc = c->wind.sample(c, two, wind_t, wind_dt, true, c->stream);
         if (rc) return rc;
     }
     c->pending = false;
@@ -1455,11 +1459,21 @@ PX_EXPORT int32_t picles_seed(picles_ctx *c, double t0)
     HIPCHK(c, hipMemsetAsync(c->mr_buf[0] + 5, 0, 11 * sizeof(int), c->stream));      /* running maximum + the "calm waves" words (kernels.h: order_wanted) */
     HIPCHK(c, hipMemsetAsync(c->A.rmap, 0, (size_t)5 * c->A.ntile * sizeof(int), c->stream));
     { int rc = class_map_zero(c); if (rc) return rc; }
-    hipLaunchKernelGGL(k_seed, dim3(nblocks(c->A.n, 256)), dim3(256), 0, c->stream, c->P, c->G, arrays_for(c, 0, 0), c->d_mask, c->od.timestep);
+    /* k_seed reads the window at time 0.0 (run.jl:213-215).  A child started from its parent is seeded under the wind at wind_t: its
+     * copy of the parameters carries the window's start moved back by wind_t (picles_seed: by 0.0, the same bits) */
+    KParams seedP = c->P;
+    seedP.tw0 = c->P.tw0 - wind_t;
+    hipLaunchKernelGGL(k_seed, dim3(nblocks(c->A.n, 256)), dim3(256), 0, c->stream, seedP, c->G, arrays_for(c, 0, 0), c->d_mask, c->od.timestep);
     HIPCHK(c, hipGetLastError());
     c->state_zero = false;
     c->seeded = true;
     return 0;
+}
+
+PX_EXPORT int32_t picles_seed(picles_ctx *c, double t0)
+{
+    if (!c) return -1;
+    return seed_at(c, t0, 0.0, c->od.timestep);
 }
 
 PX_EXPORT int32_t picles_zero_state(picles_ctx *c)
@@ -3293,6 +3307,83 @@ PX_EXPORT int32_t picles_nest_free(picles_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     if (c->fb) { int rc = fb_release(c); if (rc) return rc; }      /* the feedback lives on the nest */
     return nest_release(c, true);
+}
+
+/* one axis of picles_nest_prolong's tables, held as stencil_check holds a stencil: indices inside [0, n_par), weights finite and in [0, 1] */
+static int prolong_axis_check(picles_ctx *c, const char *axis, int n_child, int n_par, const int32_t *i0, const int32_t *i1, const double *w)
+{
+    const std::string who = "picles_nest_prolong: ";
+    for (int k = 0; k < n_child; k++) {
+        for (int v : {i0[k], i1[k]})
+            if (v < 0 || v >= n_par)
+                return fail(c, -2, who + "index " + std::to_string(v) + " of the child's " + axis + " " + std::to_string(k) + " lies outside the parent's grid [0, " +
+                                   std::to_string(n_par) + ")");
+        if (!std::isfinite(w[k]) || w[k] < 0.0 || w[k] > 1.0)
+            return fail(c, -2, who + "the weight of the child's " + axis + " " + std::to_string(k) + " is not finite or lies outside [0, 1]");
+    }
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_prolong(picles_ctx *c, picles_ctx *p, const int32_t *ix0, const int32_t *ix1, const double *wx,
+                                      const int32_t *iy0, const int32_t *iy1, const double *wy, double dt)
+{
+    if (!c) return -1;
+    if (!p) return fail(c, -2, "picles_nest_prolong: no parent context given");
+    if (c == p) return fail(c, -2, "picles_nest_prolong: child and parent are the same context: a child is started from another model");
+    if (c->device != p->device)
+        return fail(c, -5, "picles_nest_prolong: child on device " + std::to_string(c->device) + ", parent on device " + std::to_string(p->device) +
+                           ": create both contexts on one device");
+    if (!c->G.single_slab || c->ring || !p->G.single_slab || p->ring)
+        return fail(c, -5, "picles_nest_prolong: slabs, slab mode and the native ring do not nest: both contexts must be whole-grid contexts");
+    if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string("picles_nest_prolong") + NEST_NO_EXT_STREAMS);
+    if (!p->seeded) return fail(c, -2, "picles_nest_prolong: the parent was never seeded: it holds no sea state to start a child from");
+    if (!(dt > 0.0)) return fail(c, -2, "picles_nest_prolong: dt must be positive (the child's step: the remesh and a lattice's first window use it)");
+    if (!ix0 || !ix1 || !wx || !iy0 || !iy1 || !wy) return fail(c, -2, "picles_nest_prolong: the six tables ix0, ix1, wx, iy0, iy1, wy must be given");
+    const int ncx = c->G.Nx, ncy = c->G.Ny;
+    { int rc = prolong_axis_check(c, "column", ncx, p->G.Nx, ix0, ix1, wx); if (rc) return rc; }
+    { int rc = prolong_axis_check(c, "row", ncy, p->G.Ny, iy0, iy1, wy); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    /* the tables, one block: wx, wy, then ix0, ix1, iy0, iy1 */
+    const size_t nd = (size_t)ncx + ncy, bytes = nd * sizeof(double) + 2 * nd * sizeof(int);
+    if (c->prolong_tab) HIPCHK(c, hipStreamSynchronize(c->stream));      /* the launch of an earlier call may still read them */
+    if (c->prolong_cap < bytes) {
+        double *q = nullptr;
+        HIPCHK(c, hipMalloc(&q, bytes));
+        if (c->prolong_tab) hipFree(c->prolong_tab);
+        c->prolong_tab = q;
+        c->prolong_cap = bytes;
+    }
+    std::vector<unsigned char> h(bytes);
+    {
+        double *hd = (double *)h.data();
+        int *hi = (int *)(hd + nd);
+        std::copy(wx, wx + ncx, hd);
+        std::copy(wy, wy + ncy, hd + ncx);
+        std::copy(ix0, ix0 + ncx, hi);
+        std::copy(ix1, ix1 + ncx, hi + ncx);
+        std::copy(iy0, iy0 + ncy, hi + 2 * ncx);
+        std::copy(iy1, iy1 + ncy, hi + 2 * ncx + ncy);
+    }
+    HIPCHK(c, hipMemcpy(c->prolong_tab, h.data(), bytes, hipMemcpyHostToDevice));       /* blocking: the caller's tables are free on return */
+    {   /* the parent's State at its clock, whole: its pending step completed on its own stream */
+        const std::string keep = p->err;
+        int rc = flush(p);
+        if (rc) { const std::string why = p->err; p->err = keep; return fail(c, rc, "picles_nest_prolong: the parent's pending step: " + why); }
+    }
+    /* from here on the child changes: what picles_seed resets, at the parent's clock and under the wind there */
+    { int rc = seed_at(c, p->clock, p->clock, dt); if (rc) return rc; }
+    HIPCHK(c, hipEventRecord(p->ev_ctx, p->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, p->ev_ctx, 0));
+    const double *dwx = c->prolong_tab, *dwy = dwx + ncx;
+    const int *dix0 = (const int *)(c->prolong_tab + nd), *dix1 = dix0 + ncx, *diy0 = dix1 + ncx, *diy1 = diy0 + ncy;
+    hipLaunchKernelGGL(k_nest_prolong, dim3(nblocks(c->A.n, NEST_BLOCK)), dim3(NEST_BLOCK), 0, c->stream, ncx, ncy, p->G.Nx, p->A.n, dix0, dix1, dwx, diy0, diy1,
+                       dwy, (const double *)p->A.state, c->A.state);
+    HIPCHK(c, hipGetLastError());
+    /* the parent's next step overwrites the State this kernel reads: its stream goes on behind it */
+    HIPCHK(c, hipEventRecord(c->ev_ctx, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(p->stream, c->ev_ctx, 0));
+    c->state_zero = false;
+    return picles_remesh(c, dt);
 }
 
 PX_EXPORT int32_t picles_nest_feedback_init(picles_ctx *c, int32_t n_fb, const int32_t *fb_ij, int32_t n_src, const int32_t *src_ij, int32_t m,

@@ -709,6 +709,24 @@ class HipModel:
         self._feedback_goes()
         self._ck(self.lib.picles_nest_free(self.h), "picles_nest_free")
 
+    def nest_prolong(self, parent, ix0, ix1, wx, iy0, iy1, wy, dt):
+        """this model started from `parent` (a HipModel) at the parent's clock: the parent's State prolonged onto every node of this
+        model, and the particles the remesh makes of it with step `dt` (picles_nest_prolong; nesting.prolong_tables gives the six
+        per-axis tables: 0-based parent columns / rows and weights in [0, 1] per child column / row)"""
+        ph = getattr(parent, "h", parent)
+        ints = [np.ascontiguousarray(a, dtype=np.int64) for a in (ix0, ix1, iy0, iy1)]
+        w = [np.ascontiguousarray(a, dtype=np.float64) for a in (wx, wy)]
+        for a, b, n, axis in ((ints[0], ints[1], self.Nx, "x"), (ints[2], ints[3], self.ny_loc, "y")):
+            if not (a.shape == b.shape == (n,)):
+                raise ValueError(f"nest_prolong: the {axis} index tables must hold {n} entries each, got {a.shape} and {b.shape}")
+        if w[0].shape != (self.Nx,) or w[1].shape != (self.ny_loc,):
+            raise ValueError(f"nest_prolong: the weight tables must hold {self.Nx} and {self.ny_loc} entries, got {w[0].shape} and {w[1].shape}")
+        a0, a1, b0, b1 = (_int32_planes(a.reshape(-1, 1), "nest_prolong").reshape(-1) for a in ints)
+        # (State is replaced too: the model layer resets its lazy view after the start — nesting.start_from_parent — as after a step)
+        self.gen += 1
+        self._ck(self.lib.picles_nest_prolong(self.h, ph, _p32(a0), _p32(a1), K.dptr(w[0]), _p32(b0), _p32(b1), K.dptr(w[1]), float(dt)),
+                 "picles_nest_prolong")
+
     # ---- two-way nesting (picles_nest_feedback_*: this nested model's State restricted onto ocean nodes of its parent, on the device) ----
     def nest_feedback_init(self, fb_nodes, src_nodes, index, weights):
         """fb_nodes (n_fb, 2): 0-based (i, j) of the parent's ocean nodes to feed; src_nodes (n_src, 2): distinct 0-based (i, j) of

@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(14)
+const PICLES_ABI_VERSION = Int32(15)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -640,6 +640,22 @@ end
 nest_sample!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_sample, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_sample")
 
 nest_free!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_free, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_free")
+
+"""
+    nest_prolong!(child, parent, ix0, ix1, wx, iy0, iy1, wy, dt)
+
+A child started from its parent (`picles_nest_prolong`, ABI 15; the contract is in include/picles_hip.h): the State of `parent` at its
+clock `t`, prolonged onto every node of `child`, and the child's particles made from it with the library's remesh at clock `t` and step
+`dt`; the child is reset as `picles_seed(child, t)` resets it.  Per child column `i` the 1-based parent columns `ix0[i]`, `ix1[i]` and
+the weight `wx[i]`, per child row `j` the parent rows `iy0[j]`, `iy1[j]` and `wy[j]` (weights in `[0, 1]`; a periodic parent's wrap
+cell is `ix0 = Nx`, `ix1 = 1`).  Returns after enqueueing.
+"""
+function nest_prolong!(child::WaveGrowth2DHIP, parent::WaveGrowth2DHIP, ix0, ix1, wx, iy0, iy1, wy, dt::Real)
+    a0, a1, b0, b1 = (Vector{Int32}(v .- 1) for v in (ix0, ix1, iy0, iy1))
+    fx, fy = Vector{Float64}(wx), Vector{Float64}(wy)
+    check(child.ctx, ccall((:picles_nest_prolong, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Float64), child.ctx, parent.ctx, a0, a1, fx, b0, b1, fy, Float64(dt)), "picles_nest_prolong")
+    nothing
+end
 
 """
     nest_feedback_init!(child, fb_nodes, src_nodes, index, weights)

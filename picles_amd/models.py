@@ -338,6 +338,16 @@ class WaveGrowth2D:
             self._winds_static = bool(all(np.array_equal(a[k], b[k]) and np.array_equal(a[k], c[k]) for k in (0, 1)))
         return self._winds_static
 
+    def runs_chunked(self, dt, detect=False):
+        """do these winds let run() enqueue whole chunks of steps (picles_run_steps)?  Static winds, or a GriddedWinds lattice that
+        the device samples itself every step (a backend with set_wind_grid).  Closures that vary in time are sampled by the host in
+        front of every step: the per-step loop.  `detect`: winds not declared static or varying are sampled to find out, as
+        _is_static does (nesting asks that way before anything is seeded); run() reads the declaration alone"""
+        from .wind_emulator import GriddedWinds
+        if isinstance(self.winds, GriddedWinds) and hasattr(self.backend, "set_wind_grid"):
+            return True
+        return bool(self._is_static(dt) if detect else self._winds_static)
+
     def upload_winds(self, t, dt, seeding=False):
         """node-sample the wind closures for the step [t, t+dt]: three levels (t, t+dt/2, t+dt), interpolated in t by the kernel.
         `seeding`: the window is init_particles!'s, which reads its level 0 only (winds at t = 0.0, run.jl:213-215)"""

@@ -29,7 +29,17 @@ feedback is taken exactly when a parent step is taken, with both clocks equal, i
 BoundaryForcing of its own.
 
 Not for slabs, not together with a Checkpointer or `pickup=` (a restart of a pair whose parent is a step ahead is not defined yet),
-and only where run() takes its chunked path on both models: static winds, no `store`, no `cash_store`.
+and only where run() takes its chunked path on both models: no `store`, no `cash_store`, and winds that are static or a
+GriddedWinds lattice the device samples itself (`WaveGrowth2D.runs_chunked`).  Either model, or both, may run under a lattice, the
+same object or different ones: each context samples its own copy at its own node coordinates, in stream order on its own stream,
+so a level taken from the parent and a step of the child see the winds their clocks name.  Wind closures that vary in time are
+sampled by the host in front of every step and stay refused.
+
+A CHILD SWITCHED ON LATE (`start_from_parent(child_sim, parent_sim)`).  A hindcast spins the parent up alone and
+switches the child on when the storm nears: the parent's State at its clock t is prolonged onto every node of the child on the
+device (`prolong_state` is the definition, picles_nest_prolong the call, k_nest_prolong in picles_amd/csrc/k_nest.h the kernel),
+the child's particles are remeshed from it under the child's wind at t, and both clocks read t: `run(child_sim)` with a
+NestForcing then proceeds as from a common cold start.
 """
 from __future__ import annotations
 
@@ -39,7 +49,7 @@ import numpy as np
 
 from .boundary_forcing import BoundaryForcing, node_points, rim_nodes
 from .output_writers import PHASE_ORDER, in_phase, writers_of
-from .station_output import locate_points, wet_means
+from .station_output import _axis, _kind, locate_points, wet_means
 
 RATIO_EPS = 1e-12          # |r Δt_child - Δt_parent| may be this fraction of Δt_parent
 
@@ -123,6 +133,73 @@ def restrict_records(values, index, weight):
     return out
 
 
+def prolong_tables(parent_grid, child_grid):
+    """(ix0, ix1 int32 [Ncx], wx float64 [Ncx], iy0, iy1 int32 [Ncy], wy float64 [Ncy]): per child column and per child row the two
+    parent columns / rows around it and the weight of the second — `station_output._axis` of the child's node coordinates on the
+    parent's axes, which is what `locate_points(parent_grid, [(x, y)])` does per point: the bilinear stencil is separable.  The
+    tables picles_nest_prolong takes.  A child node outside the parent is locate_points' ValueError"""
+    xs, ys = np.asarray(parent_grid.data.x)[:, 0], np.asarray(parent_grid.data.y)[0, :]
+    cx, cy = np.asarray(child_grid.data.x)[:, 0], np.asarray(child_grid.data.y)[0, :]
+    out = []
+    for pc, cc, N, what in ((xs, cx, parent_grid.stats.Nx, "x"), (ys, cy, parent_grid.stats.Ny, "y")):
+        rows = [_axis(float(c), float(pc[0]), float(pc[-1]), int(N), _kind(N), what) for c in cc]
+        out += [np.array([r[0] for r in rows], dtype=np.int32), np.array([r[1] for r in rows], dtype=np.int32),
+                np.array([r[2] for r in rows], dtype=np.float64)]
+    return tuple(out)
+
+
+def prolong_state(S_parent, parent_grid, child_grid):
+    """k_nest_prolong in NumPy, bit for bit: the parent's State float64 [Npx, Npy, 3] onto every node of the child -> float64
+    [Ncx, Ncy, 3].  Per child node the four parent corners in locate_points' visiting order with its weights (1-wx)(1-wy),
+    wx(1-wy), (1-wx)wy, wx wy, and over them the station definition (wet_means); a node that is not valid — no wet corner, or zero
+    momentum — is (0, 0, 0): a calm node, whose particle the remesh makes from the local wind.  No case depends on a mask"""
+    S = np.asarray(S_parent, dtype=np.float64)
+    ix0, ix1, wx, iy0, iy1, wy = prolong_tables(parent_grid, child_grid)
+    Npx = S.shape[0]
+    ncx, ncy = len(wx), len(wy)
+    gx, gy = 1.0 - wx, 1.0 - wy
+    I0, I1, J0, J1 = (a.astype(np.int64) for a in (ix0[:, None], ix1[:, None], iy0[None, :], iy1[None, :]))
+    index = np.stack([J0 * Npx + I0, J0 * Npx + I1, J1 * Npx + I0, J1 * Npx + I1], axis=-1).reshape(ncx * ncy, 4)
+    weight = np.stack([gx[:, None] * gy[None, :], wx[:, None] * gy[None, :], gx[:, None] * wy[None, :], wx[:, None] * wy[None, :]],
+                      axis=-1).reshape(ncx * ncy, 4)
+    values = S.reshape(-1, 3, order="F").T                  # [3, n_nodes], node j Npx + i
+    E, MX, MY, valid = wet_means(values, index, weight)
+    out = np.where(valid[:, None], np.stack([E, MX, MY], axis=1), 0.0)
+    return out.reshape(ncx, ncy, 3)
+
+
+def start_from_parent(child_sim, parent_sim):
+    """A child started from its spun-up parent, before `run(child_sim)`: the parent has been run to some clock t; afterwards the
+    child's State is the parent's prolonged onto the child's nodes (`prolong_state`), its particles are what the library's remesh
+    makes of that State under the child's wind at t with the step `child_sim.Δt` and fresh controller memory, the library's clock
+    for the child is t, `child.clock.time = t`, `child.clock.iteration = 0` and `child_sim.initialized` is true: `run(child_sim)`
+    with a `NestForcing(parent=parent_sim, ...)` finds equal clocks and proceeds.  All on the device (picles_nest_prolong,
+    DESIGN.md §23).  The child's winds are static or a lattice the device samples; the parent's pending step is completed."""
+    cm, pm = child_sim.model, parent_sim.model
+    if type(cm).__name__ == "SlabModel" or type(pm).__name__ == "SlabModel":
+        raise NotImplementedError("start_from_parent: slabs do not nest: use whole-grid models")
+    if cm is pm:
+        raise ValueError("start_from_parent: the parent must be another model")
+    if not parent_sim.initialized:
+        raise ValueError("start_from_parent: the parent was never run: it holds no sea state to start a child from "
+                         "(run(parent_sim) to the clock at which the child is switched on first)")
+    if not cm.runs_chunked(child_sim.Δt, detect=True):
+        raise NotImplementedError(f"start_from_parent: the child's wind closures vary in time: {WINDS_REFUSAL}")
+    tables = prolong_tables(pm.grid, cm.grid)             # a child node outside the parent: ValueError, nothing touched
+    if not hasattr(cm.backend, "nest_prolong"):
+        raise NotImplementedError("start_from_parent needs a backend with nest_prolong (the HIP library, ABI 15)")
+    t = float(pm.clock.time)
+    cm._wind_window = None
+    cm.upload_winds(t, child_sim.Δt, seeding=True)        # static: the level at t; a lattice: uploaded once, sampled by the library at t
+    cm.backend.nest_prolong(pm.backend, *tables, float(child_sim.Δt))
+    st = getattr(cm, "_state", None)
+    if st is not None:
+        st.after_step()                  # the device field was replaced: no host mirror, no recorded write survives the start
+    cm.clock.time, cm.clock.iteration = t, 0
+    child_sim.initialized = True
+    child_sim.running = False
+
+
 def default_feedback_margin(width, dx_child, dx_parent):
     """1 + ceil(width dx_child / dx_parent) parent cells: no node of the child's band is among the sources"""
     return 1 + int(math.ceil(float(width) * float(dx_child) / float(dx_parent) - 1e-12))
@@ -142,8 +219,13 @@ def check_ratio(ratio, dt_child, dt_parent):
 
 
 def _chunked(model, dt):
-    """would run() take picles_run_steps on this model?  (time-constant winds; evaluated on the host, nothing is uploaded)"""
-    return hasattr(model.backend, "run_steps") and bool(model._is_static(dt))
+    """would run() take picles_run_steps on this model?  (WaveGrowth2D.runs_chunked: time-constant winds, or a lattice the device
+    samples itself; evaluated on the host, nothing is uploaded)"""
+    return hasattr(model.backend, "run_steps") and bool(model.runs_chunked(dt, detect=True))
+
+
+WINDS_REFUSAL = ("a nest needs static winds on both models, or a GriddedWinds lattice on a backend that samples it on the device "
+                 "(set_wind_grid)")
 
 
 class NestForcing(BoundaryForcing):
@@ -213,8 +295,8 @@ class NestForcing(BoundaryForcing):
         check_ratio(self.ratio, float(sim.Δt), float(self.parent.Δt))
         for m, dt, who in ((sim.model, sim.Δt, "child"), (self.parent.model, self.parent.Δt, "parent")):
             if not _chunked(m, dt):
-                raise NotImplementedError(f"NestForcing: the {who} model would leave picles_run_steps (winds that vary in time, or a backend "
-                                          "without run_steps): a nest needs static winds on both models")
+                raise NotImplementedError(f"NestForcing: the {who} model would leave picles_run_steps (wind closures that vary in time, or a "
+                                          f"backend without run_steps): {WINDS_REFUSAL}")
         for w in pw:
             if not hasattr(self.parent.model.backend, w.needs):
                 raise NotImplementedError(w.refusal)
@@ -222,6 +304,11 @@ class NestForcing(BoundaryForcing):
 
     # ---- the parent, driven as run(parent) would drive it, one step per chunk ----
     def _parent_begin(self, n_parent):
+        """the parent's side of begin_run.  A parent that has not been initialised is seeded; one that has been run already (a
+        spin-up in front of `start_from_parent`) goes on from its clock, and its writers are begun for the nested leg as a second
+        `run(parent_sim)` would begin them: files sized for `n_parent` steps, the record of the parent's current iteration first.
+        Point them at another path for the nested leg (`writer.path = ...` on the same objects: a
+        StationWriter owns the parent's probe set), or they overwrite what the spin-up wrote"""
         from .simulations import initialize_simulation
         ps, pm = self.parent, self.parent.model
         if not ps.initialized:
@@ -309,7 +396,7 @@ class NestForcing(BoundaryForcing):
         raise NotImplementedError("NestForcing: a nested pair cannot be picked up yet")
 
     def before_step(self, backend):
-        raise NotImplementedError("NestForcing: run() left its chunked path (store=True, cash_store=True or winds that vary in time)")
+        raise NotImplementedError("NestForcing: run() left its chunked path (store=True, cash_store=True or wind closures that vary in time)")
 
     def at_iteration(self, model, writers):
         """the step actually taken is held against the ratio once it can be read off the clock; the next pair is steps_allowed's
