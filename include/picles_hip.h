@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 15
+#define PICLES_ABI_VERSION 16
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -528,11 +528,24 @@ int32_t picles_bforce_init_band(picles_ctx *ctx, int32_t n, const int32_t *ij, c
  * With a nest, picles_bforce_set_levels is refused (-2: the levels come from the parent; picles_nest_free first).
  * picles_bforce_free and picles_destroy on a nested child release the nest first.  picles_destroy(parent) detaches its children:
  * each keeps its set and its last levels and goes on stepping under them; a later picles_nest_sample on it fails with a text.
- * A parent may serve several children.  The nest is no part of a checkpoint. */
+ * A parent may serve several children.  The nest is no part of a checkpoint.
+ * A NEST RESUMED (ABI 16).  The blob holds nothing of a nest, so a checkpointed PAIR is restarted from three things the
+ * host kept: the child's blob, the parent's blob at the parent's clock — which is t1 of the pair the child held — and that pair
+ * itself, as picles_bforce_info / picles_bforce_get_levels(child) gave it when the blobs were taken.  Load both blobs, make the
+ * child's set and the nest again (picles_bforce_init[_band], picles_nest_init), and put the pair back:
+ *   set_levels: v0, v1 are 3 planes of n doubles each, the layout of picles_bforce_get_levels; copied verbatim (NaN payloads
+ *            survive) into the slots the pair names, in stream order on the child's stream; blocking: the buffers are free on
+ *            return.  Afterwards levels = 2 over [t0, t1] and picles_nest_info reports 2 samples: the next picles_nest_sample
+ *            rotates as a third sample does, and is refused until the parent's clock has moved past t1.  No seed sample and, with
+ *            feedback, no seed feedback is taken: the next feedback stands in front of the next parent step, on a common clock.
+ *            Refuses (-2, both contexts unchanged and usable, picles_last_error(child) has the text) a child without a nest, a
+ *            nest whose parent was destroyed, a nest that has taken a sample, v0 or v1 NULL, times that are not finite or not
+ *            t1 > t0, a parent whose clock is not exactly t1, and contexts that have run on caller-provided streams. */
 int32_t picles_nest_init(picles_ctx *child, picles_ctx *parent, int32_t n_corner, const int32_t *corner_ij, const int32_t *index, const double *weight);
 int32_t picles_nest_sample(picles_ctx *child);
 int32_t picles_nest_info(const picles_ctx *child, int32_t *n_corner, int64_t *samples);
 int32_t picles_nest_free(picles_ctx *child);
+int32_t picles_nest_set_levels(picles_ctx *child, double t0, const double *v0, double t1, const double *v1);
 
 /* ---- a child started from its parent (ABI 15): the State of `parent` at its clock t, prolonged onto EVERY node of `child`,
  * and the child's particles made from it — a child switched on beside a parent that has been running, instead of seeded cold at t = 0. ----

@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _capi as K
-from .output_writers import OutputWriter, find_writer
+from .output_writers import OutputWriter, find_writer, writers_of
 
 FILE_MAGIC = b"PICLESCF"
 FILE_VERSION = 1
@@ -198,10 +198,17 @@ def resolve_pickup(sim, pickup):
         ck = find_writer(sim, Checkpointer)
         if ck is None:
             raise K.CheckpointError(0, "run(sim, pickup=True) needs a Checkpointer in sim.output_writers (or pass pickup=<path>)")
-        path = ck.latest()
-        if path is None:
+        others = [w for w in writers_of(sim) if w is not ck]
+        found = list_checkpoints(ck.dir, ck.prefix, ck.rank)
+        if not found:
             raise K.CheckpointError(0, f"run(sim, pickup=True): no checkpoint file '{ck.prefix}_iteration*{SUFFIX}' in {ck.dir}")
-        return path
+        # the latest file whose companions (the parent's file and the link side-car of a nested pair) are complete: a job killed
+        # between two of them leaves a file that is passed over
+        for it in sorted(found, reverse=True):
+            if all(Path(f).is_file() for w in others for f in w.pickup_companions(found[it])):
+                return found[it]
+        lacking = [str(f) for w in others for f in w.pickup_companions(found[max(found)]) if not Path(f).is_file()]
+        raise K.CheckpointError(0, f"run(sim, pickup=True): no checkpoint of '{ck.prefix}' in {ck.dir} is complete (the latest lacks {', '.join(lacking)})")
     return Path(pickup)
 
 

@@ -3292,6 +3292,45 @@ PX_EXPORT int32_t picles_nest_sample(picles_ctx *c)
     return 0;
 }
 
+/* a nest resumed: the pair a checkpointed child held goes back into the slots (i0, i1) name, as if two samples had been taken.  The
+ * copies ride on the CHILD's stream, behind the launches nest_init marked as readers of slots 0 and 1 (read[0], read[1] were recorded
+ * on that stream), and the call waits for them: both marks are spent as the claims of two real samples spend them, and nothing was
+ * published — no event the child's next launch could wait for in vain.  The third sample marks slot i0 and writes slot 2, unclaimed */
+PX_EXPORT int32_t picles_nest_set_levels(picles_ctx *c, double t0, const double *v0, double t1, const double *v1)
+{
+    if (!c) return -1;
+    Nest *N = c->nest;
+    if (!N) return fail(c, -2, "picles_nest_set_levels: picles_nest_init first (a set without a nest takes picles_bforce_set_levels)");
+    picles_ctx *p = N->parent;
+    if (!p) return fail(c, -2, "picles_nest_set_levels: the parent context was destroyed: picles_nest_free, then picles_nest_init with a living parent");
+    if (c->ext_streams || p->ext_streams) return fail(c, -2, std::string("picles_nest_set_levels") + NEST_NO_EXT_STREAMS);
+    if (N->samples > 0)
+        return fail(c, -2, "picles_nest_set_levels: this nest has taken " + std::to_string(N->samples) + " sample(s): a pair is put back into a fresh nest "
+                           "(picles_nest_free, picles_nest_init), in front of the first picles_nest_sample");
+    if (!v0 || !v1) return fail(c, -2, "picles_nest_set_levels: both levels must be given (a resumed nest holds a pair)");
+    if (!(std::isfinite(t0) && std::isfinite(t1))) return fail(c, -2, "picles_nest_set_levels: the level times must be finite");
+    if (!(t1 > t0)) return fail(c, -2, "picles_nest_set_levels: the pair needs t1 > t0");
+    if (!(p->clock == t1)) {
+        char b[256];
+        snprintf(b, sizeof b, "picles_nest_set_levels: the parent's clock (%.17g) is not t1 (%.17g): level 1 is the parent's State at its clock "
+                              "(load the parent's checkpoint first)", p->clock, t1);
+        return fail(c, -2, b);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t b = (size_t)3 * c->bf_n * sizeof(double);
+    HIPCHK(c, hipMemcpyAsync(N->slot[N->i0], v0, b, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(N->slot[N->i1], v1, b, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      /* the caller's buffers are free when this returns */
+    N->sync.live[N->i0] = N->sync.live[N->i1] = false;      /* their readers lie behind the copies, which are complete */
+    c->bf_levels = 2;
+    c->bf_t0 = t0;
+    c->bf_t1 = t1;
+    c->bf_v0 = N->slot[N->i0];
+    c->bf_v1 = N->slot[N->i1];
+    N->samples = 2;
+    return 0;
+}
+
 PX_EXPORT int32_t picles_nest_info(const picles_ctx *c, int32_t *n_corner, int64_t *samples)
 {
     if (!c || !c->nest) return -1;

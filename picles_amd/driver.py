@@ -698,6 +698,18 @@ class HipModel:
         """rotate the levels and take a new one from the parent as it stands now; returns after enqueueing"""
         self._ck(self.lib.picles_nest_sample(self.h), "picles_nest_sample")
 
+    def nest_set_levels(self, t0, v0, t1, v1):
+        """a nest resumed: the pair a checkpointed child held — v0, v1 (n, 3) as bforce_get_levels gave them, NaN rows included,
+        over [t0, t1] — put back into a fresh nest as if two samples had been taken; the parent's clock must be t1"""
+        n = self.bforce_info()[0]
+        def planes(v):
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape != (n, 3):
+                raise ValueError(f"nest_set_levels: expected an ({n}, 3) array of (e, m_x, m_y), got {v.shape}")
+            return np.ascontiguousarray(v.T)
+        a, b = planes(v0), planes(v1)
+        self._ck(self.lib.picles_nest_set_levels(self.h, float(t0), K.dptr(a), float(t1), K.dptr(b)), "picles_nest_set_levels")
+
     def nest_info(self):
         """(n_corner, samples taken) of this model's nest"""
         nc, s = C.c_int32(), C.c_int64()

@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(15)
+const PICLES_ABI_VERSION = Int32(16)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -640,6 +640,22 @@ end
 nest_sample!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_sample, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_sample")
 
 nest_free!(child::WaveGrowth2DHIP) = check(child.ctx, ccall((:picles_nest_free, libpicles), Int32, (Ptr{Cvoid},), child.ctx), "picles_nest_free")
+
+"""
+    nest_set_levels!(child, t0, v0, t1, v1)
+
+A nest resumed (`picles_nest_set_levels`, ABI 16; the contract is in include/picles_hip.h): the pair a checkpointed child held —
+`n x 3` matrices of `(e, m_x, m_y)` as `bforce_get_levels(child)` returned them, NaN rows included, over `[t0, t1]` — put back into
+a fresh nest as if two samples had been taken.  Load both models' blobs first (`pickup!`); the parent's clock must be `t1`.
+"""
+function nest_set_levels!(child::WaveGrowth2DHIP, t0::Real, v0::AbstractMatrix, t1::Real, v1::AbstractMatrix)
+    a, b = Matrix{Float64}(v0), Matrix{Float64}(v1)
+    size(a, 2) == 3 && size(b) == size(a) || error("nest_set_levels!: levels are n x 3 matrices of (e, m_x, m_y)")
+    GC.@preserve a b begin
+        check(child.ctx, ccall((:picles_nest_set_levels, libpicles), Int32, (Ptr{Cvoid}, Float64, Ptr{Float64}, Float64, Ptr{Float64}), child.ctx, Float64(t0), pointer(a), Float64(t1), pointer(b)), "picles_nest_set_levels")
+    end
+    nothing
+end
 
 """
     nest_prolong!(child, parent, ix0, ix1, wx, iy0, iy1, wy, dt)

@@ -28,8 +28,15 @@ inside the child's band, become a forcing set of the parent whose one level is t
 feedback is taken exactly when a parent step is taken, with both clocks equal, in front of that step.  Not for a parent that carries a
 BoundaryForcing of its own.
 
-Not for slabs, not together with a Checkpointer or `pickup=` (a restart of a pair whose parent is a step ahead is not defined yet),
-and only where run() takes its chunked path on both models: no `store`, no `cash_store`, and winds that are static or a
+RESTART.  A Checkpointer in the CHILD's output_writers checkpoints the pair: next to every child file the parent's
+file at the parent's own clock — t1 of the pair of levels the child holds; between two levels the parent is a step ahead —
+(`parent_checkpoint_path`, loadable on its own) and the pair itself with the counters and a hash of the geometry (`link_path`,
+`<child file>.nest.npz`), the link last.  `run(child_sim, pickup=True)` takes the latest child iteration whose three files are
+complete (`pickup=<path>` names the child's file), loads both models, makes the set and the nest and puts the pair back
+(picles_nest_set_levels) without a seed sample or a seed feedback; the ordinary loop follows, and both models continue with the bits
+of the uninterrupted run.  A Checkpointer on the parent stays refused, and so does a backend without nest_set_levels.
+
+Not for slabs, and only where run() takes its chunked path on both models: no `store`, no `cash_store`, and winds that are static or a
 GriddedWinds lattice the device samples itself (`WaveGrowth2D.runs_chunked`).  Either model, or both, may run under a lattice, the
 same object or different ones: each context samples its own copy at its own node coordinates, in stream order on its own stream,
 so a level taken from the parent and a step of the child see the winds their clocks name.  Wind closures that vary in time are
@@ -43,15 +50,55 @@ NestForcing then proceeds as from a common cold start.
 """
 from __future__ import annotations
 
+import hashlib
 import math
+import os
+import re
+from pathlib import Path
 
 import numpy as np
 
+from ._capi import CheckpointError
 from .boundary_forcing import BoundaryForcing, node_points, rim_nodes
+from .checkpointing import _HEAD, load_checkpoint, write_checkpoint_file
 from .output_writers import PHASE_ORDER, in_phase, writers_of
 from .station_output import _axis, _kind, locate_points, wet_means
 
 RATIO_EPS = 1e-12          # |r Δt_child - Δt_parent| may be this fraction of Δt_parent
+LINK_SUFFIX = ".nest.npz"   # the link side-car of a pair checkpoint, next to the child's file
+
+
+def parent_checkpoint_path(child_file):
+    """the parent's file of a pair checkpoint, next to the child's `{prefix}_iteration{i}.picles`: `{prefix}_parent_iteration{i}.picles`
+    (a name `list_checkpoints(dir, prefix)` does not match); a child file of another name gets `<stem>_parent<suffix>`"""
+    f = Path(child_file)
+    m = re.fullmatch(r"(.*)_iteration(\d+)(\.[^.]+)", f.name)
+    return f.with_name(f"{m.group(1)}_parent_iteration{m.group(2)}{m.group(3)}" if m else f"{f.stem}_parent{f.suffix}")
+
+
+def link_path(child_file):
+    """the link side-car of a pair checkpoint: `<child file>.nest.npz`"""
+    return Path(str(child_file) + LINK_SUFFIX)
+
+
+def _write_link(path, **arrays):
+    """atomic, like the checkpoint files: temporary name, flush + fsync, rename"""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    tmp = path.with_name(f".{path.name}.tmp-{os.getpid()}")
+    try:
+        with open(tmp, "wb") as f:
+            np.savez(f, **arrays)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        raise
+    return path
 
 
 def rim_points(model, side=None, *, nodes=None, width=1):
@@ -174,7 +221,9 @@ def start_from_parent(child_sim, parent_sim):
     makes of that State under the child's wind at t with the step `child_sim.Δt` and fresh controller memory, the library's clock
     for the child is t, `child.clock.time = t`, `child.clock.iteration = 0` and `child_sim.initialized` is true: `run(child_sim)`
     with a `NestForcing(parent=parent_sim, ...)` finds equal clocks and proceeds.  All on the device (picles_nest_prolong,
-    DESIGN.md §23).  The child's winds are static or a lattice the device samples; the parent's pending step is completed."""
+    DESIGN.md §23).  The child's winds are static or a lattice the device samples; the parent's pending step is completed.
+    A run begun this way is checkpointed and picked up like any nested pair: the picked-up program builds both
+    models and calls `run(child_sim, pickup=...)` — neither the spin-up nor this call is repeated."""
     cm, pm = child_sim.model, parent_sim.model
     if type(cm).__name__ == "SlabModel" or type(pm).__name__ == "SlabModel":
         raise NotImplementedError("start_from_parent: slabs do not nest: use whole-grid models")
@@ -274,14 +323,37 @@ class NestForcing(BoundaryForcing):
         self._set_on = None
         self._k = None
         self._mark = None
+        self._pair = None             # the pair checkpoint whose parent blob is being copied out: (parent file, link file, clock, iteration, link)
+        self._link = None             # the link side-car check_pickup read
+        self._resume = None           # ... handed to begin_run by load_pickup: the run resumes instead of starting cold
+        self.pairs_written = []       # the child files whose companions were completed
+
+    def geometry_hash(self):
+        """what a link side-car is held against: the forcing set's nodes and weights, the corner geometry and, two-way, the feedback's"""
+        h = hashlib.sha256()
+        parts = [self.nodes, np.zeros(0) if self.node_weights is None else self.node_weights, self.corner_nodes, self.index, self.weights]
+        if self.feedback:
+            parts += [self.fb_nodes, self.src_nodes, self.fb_index, self.fb_weights]
+        for a in parts:
+            a = np.ascontiguousarray(a)
+            h.update(f"{a.dtype.str}{a.shape}".encode())
+            h.update(a.tobytes())
+        return h.hexdigest()
 
     # ---- before anything is seeded ----
     def check_run(self, sim, writers, store=False, cash_store=False, pickup=False):
         super().check_run(sim, writers, store=store, cash_store=cash_store, pickup=pickup)
         pw = writers_of(self.parent)
-        if pickup or any(w.kind == "checkpointer" for w in list(writers) + pw):
-            raise NotImplementedError("NestForcing: a nested pair cannot be checkpointed or picked up yet (the parent is a step ahead of the "
-                                      "child): run without a Checkpointer and without pickup=")
+        if any(w.kind == "checkpointer" for w in pw):
+            raise NotImplementedError("NestForcing: a Checkpointer in the parent's output_writers: a nested pair is checkpointed through the "
+                                      "child's Checkpointer, which writes the parent's file next to the child's")
+        ck = any(w.kind == "checkpointer" for w in writers)
+        if ck or pickup:
+            b, pb = sim.model.backend, self.parent.model.backend
+            if not (hasattr(b, "nest_set_levels") and hasattr(pb, "checkpoint_begin") and hasattr(pb, "checkpoint_load")):
+                raise NotImplementedError("NestForcing: " + " and ".join((["a Checkpointer is attached"] if ck else []) + (["the run is to be picked up"] if pickup else []))
+                                          + ", but a nested pair is checkpointed and picked up only on a backend with nest_set_levels and checkpoint_begin / "
+                                          "checkpoint_load on both models (the HIP library, ABI 16)")
         if self.feedback:
             if not hasattr(self.parent.model.backend, "bforce_init_band"):
                 raise NotImplementedError(self.FEEDBACK_REFUSAL)
@@ -368,6 +440,8 @@ class NestForcing(BoundaryForcing):
         return k
 
     def begin_run(self, model, n_steps: int):
+        if self._resume is not None:
+            return self._begin_resumed(model, n_steps)
         b = model.backend
         ps, pm = self.parent, self.parent.model
         n_parent = max(1, -(-int(n_steps) // self.ratio))
@@ -382,6 +456,7 @@ class NestForcing(BoundaryForcing):
         self._set_on = b
         self.times, self._have, self._k = np.zeros(0), -1, None
         self._mark = (self._time(b), int(model.clock.iteration))
+        self._cit0 = int(model.clock.iteration)
         b.nest_sample()                   # level 0: the parent at the common clock
         self._took_level(b)
         if self.feedback:
@@ -392,8 +467,121 @@ class NestForcing(BoundaryForcing):
         self._parent_step(b)              # the parent is one step ahead from here on
         self._took_level(b)
 
+    # ---- a pair checkpoint: the child's file, the parent's at ITS clock — t1 of the pair held — and the pair ----
+    def checkpoint_begun(self, backend, checkpoint_file):
+        """the child's Checkpointer has taken the child's snapshot: the parent's is taken now, at the parent's clock, the pair is read
+        as the child holds it, and the parent's writers hear of the parent's file; the blob is fetched one chunk later"""
+        self._pair_finish()
+        pm = self.parent.model
+        pb = pm.backend
+        pb.checkpoint_begin()
+        _, levels, t0, t1 = backend.bforce_info()
+        if levels != 2 or float(pm.clock.time) != t1:
+            raise CheckpointError(0, f"NestForcing: the child holds {levels} level(s) up to {t1!r} and the parent's clock is {pm.clock.time!r}: "
+                                     "a pair checkpoint needs the pair whose later level is the parent's State at its clock")
+        v0, v1 = backend.bforce_get_levels()
+        pfile = parent_checkpoint_path(checkpoint_file)
+        for w in self._pw:
+            w.checkpoint_begun(pb, pfile)
+        link = dict(t0=np.float64(t0), t1=np.float64(t1), v0=v0, v1=v1, ratio=np.int64(self.ratio), feedback=np.bool_(self.feedback),
+                    child_time=np.float64(self.model.clock.time), child_iteration=np.int64(self.model.clock.iteration),
+                    parent_time=np.float64(pm.clock.time), parent_iteration=np.int64(pm.clock.iteration),
+                    uploads=np.int64(self.uploads), parent_steps=np.int64(self.parent_steps), feedbacks=np.int64(self.feedbacks),
+                    times=np.asarray(self.times, dtype=np.float64), have=np.int64(self._have),
+                    parent_time0=np.float64(self._ptime0), parent_iteration0=np.int64(self._pit0), child_iteration0=np.int64(self._cit0),
+                    hash=np.str_(self.geometry_hash()))
+        self._pair = (pfile, link_path(checkpoint_file), float(pm.clock.time), int(pm.clock.iteration), link, Path(checkpoint_file))
+
+    def _pair_finish(self):
+        """the parent's blob, whose copy-out ran beside the chunk, then the link: the side-car is the last of the three files"""
+        if self._pair is None:
+            return
+        pfile, lfile, time, iteration, link, cfile = self._pair
+        self._pair = None
+        write_checkpoint_file(pfile, self.parent.model.backend.checkpoint_end(), time, iteration)
+        _write_link(lfile, **link)
+        self.pairs_written.append(cfile)
+
+    def after_chunk(self, backend):
+        self._pair_finish()
+
+    def pickup_companions(self, checkpoint_file):
+        return (parent_checkpoint_path(checkpoint_file), link_path(checkpoint_file))
+
+    def check_pickup(self, checkpoint_file):
+        """the parent's file and the link side-car are there and were written under this NestForcing; nothing is loaded"""
+        for f in (Path(checkpoint_file),) + tuple(self.pickup_companions(checkpoint_file)):
+            if not f.is_file():
+                raise CheckpointError(0, f"NestForcing: {f} is missing: a nested pair is picked up from the child's file, the parent's file and the "
+                                         "link side-car next to it")
+        pfile, lfile = self.pickup_companions(checkpoint_file)
+        try:
+            with np.load(lfile) as z:
+                link = {k: z[k] for k in z.files}
+            have = {"t0", "t1", "v0", "v1", "ratio", "feedback", "hash", "times", "have", "child_time", "child_iteration", "parent_time",
+                    "parent_iteration", "uploads", "parent_steps", "feedbacks", "parent_time0", "parent_iteration0", "child_iteration0"} <= set(link)
+        except Exception as e:
+            raise CheckpointError(0, f"NestForcing: {lfile} is not a link side-car ({e})") from None
+        if not have:
+            raise CheckpointError(0, f"NestForcing: {lfile} is not a link side-car (entries are missing)")
+        for what, got, want in (("ratio", int(link["ratio"]), self.ratio), ("feedback", bool(link["feedback"]), self.feedback),
+                                ("geometry hash", str(link["hash"]), self.geometry_hash())):
+            if got != want:
+                raise CheckpointError(0, f"NestForcing: {lfile} was written by another nest: its {what} is {got!r}, this NestForcing's {want!r}")
+        n = len(self.nodes)
+        if link["v0"].shape != (n, 3) or link["v1"].shape != (n, 3):
+            raise CheckpointError(0, f"NestForcing: {lfile}: the pair's levels are not ({n}, 3) arrays")
+        with open(pfile, "rb") as f:
+            head = f.read(_HEAD.size)
+        if len(head) == _HEAD.size:
+            _, _, _, it, time, _ = _HEAD.unpack(head)
+            if it != int(link["parent_iteration"]) or time != float(link["parent_time"]):
+                raise CheckpointError(0, f"NestForcing: {pfile} holds the parent at iteration {it}, t = {time!r}; the side-car {lfile.name} names "
+                                         f"iteration {int(link['parent_iteration'])}, t = {float(link['parent_time'])!r}")
+        self._link = (Path(checkpoint_file), link)
+
     def load_pickup(self, checkpoint_file):
-        raise NotImplementedError("NestForcing: a nested pair cannot be picked up yet")
+        """the child has been loaded: the parent is loaded from its file next to the child's, its writers take what they stored next
+        to that, and the pair is remembered for begin_run"""
+        if self._link is None or self._link[0] != Path(checkpoint_file):
+            self.check_pickup(checkpoint_file)
+        link, self._link = self._link[1], None
+        ps = self.parent
+        pfile = parent_checkpoint_path(checkpoint_file)
+        load_checkpoint(ps.model, pfile, ps.Δt)
+        ps.initialized = True
+        ps.running = False
+        for w in writers_of(ps):
+            w.load_pickup(pfile)
+        self._resume = link
+
+    def _begin_resumed(self, model, n_steps: int):
+        """begin_run after a pickup: the set and the nest are made again and the pair is put back (nest_set_levels) — no seed sample
+        and no seed feedback: the ordinary loop steps the parent where the uninterrupted run would have, its feedback in front"""
+        link, self._resume = self._resume, None
+        b = model.backend
+        ps, pm = self.parent, self.parent.model
+        done = int(model.clock.iteration) - int(link["child_iteration0"])          # child steps since the nest began
+        n_parent = max(0, -(-(done + int(n_steps)) // self.ratio) - int(link["parent_steps"]))
+        self._parent_begin(n_parent)
+        for who, m, tag in (("child", model, "child"), ("parent", pm, "parent")):
+            if float(m.clock.time) != float(link[tag + "_time"]) or int(m.clock.iteration) != int(link[tag + "_iteration"]):
+                raise CheckpointError(0, f"NestForcing: the {who}'s clock ({m.clock.time!r}, iteration {m.clock.iteration}) is not the link side-car's "
+                                         f"({float(link[tag + '_time'])!r}, iteration {int(link[tag + '_iteration'])})")
+        if self._set_on is b:
+            b.bforce_free()
+            self._fb_on = None
+        self._init_set(b)
+        b.nest_init(pm.backend, self.corner_nodes, self.index, self.weights)
+        self._set_on = b
+        b.nest_set_levels(float(link["t0"]), link["v0"], float(link["t1"]), link["v1"])
+        self.times, self._have, self._k = np.asarray(link["times"], dtype=np.float64), int(link["have"]), None
+        self.uploads, self.parent_steps, self.feedbacks = int(link["uploads"]), int(link["parent_steps"]), int(link["feedbacks"])
+        self._ptime0, self._pit0, self._cit0 = float(link["parent_time0"]), int(link["parent_iteration0"]), int(link["child_iteration0"])
+        self._mark = (self._time(b), int(model.clock.iteration))
+        if self.feedback:
+            b.nest_feedback_init(self.fb_nodes, self.src_nodes, self.fb_index, self.fb_weights)
+            self._fb_on = b
 
     def before_step(self, backend):
         raise NotImplementedError("NestForcing: run() left its chunked path (store=True, cash_store=True or wind closures that vary in time)")
@@ -409,6 +597,7 @@ class NestForcing(BoundaryForcing):
 
     def finish(self, backend, iteration=None):
         """the parent's writers finish with the child's; the nest and the set go with the run"""
+        self._pair_finish()
         if getattr(self, "_pw", None) is not None:
             pm = self.parent.model
             for w in self._pphase["finish"]:

@@ -28,6 +28,15 @@ class OutputWriter:
         """run(sim, ...) is about to start with these arguments and these writers: raise for a combination this writer cannot
         serve — nothing has been loaded or seeded yet"""
 
+    def pickup_companions(self, checkpoint_file):
+        """the files this writer cannot continue without next to `checkpoint_file`: run(sim, pickup=True) takes the latest
+        checkpoint for which every writer's companions are complete"""
+        return ()
+
+    def check_pickup(self, checkpoint_file):
+        """run(sim, pickup=...) has chosen `checkpoint_file` and every check_run has passed: raise a CheckpointError for
+        companions that are missing or were written by another configuration — nothing has been loaded yet"""
+
     def load_pickup(self, checkpoint_file):
         """run(sim, pickup=...) has loaded `checkpoint_file`: take what this writer stored next to it"""
 

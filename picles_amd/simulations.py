@@ -110,6 +110,8 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         w.check_run(sim, writers, store=store, cash_store=cash_store, pickup=picked is not None)
     phase = {p: in_phase(writers, p) for p in PHASE_ORDER}
     if picked is not None:
+        for w in writers:
+            w.check_pickup(picked)             # e.g. the parent's file and the link side-car of a nested pair: nothing is loaded yet
         load_checkpoint(m, picked, sim.Δt)
         sim.initialized = True
         for w in writers:
