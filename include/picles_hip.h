@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 16
+#define PICLES_ABI_VERSION 17
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -203,6 +203,50 @@ int32_t picles_lattice_knots(double lat_t0, double lat_dt, double t, double dt, 
 /* All of them: returns the number of lattice time knots strictly inside (t, t+dt) by the same rule and writes the times of the first
  * `cap` into tks (tks may be NULL with cap = 0). */
 int32_t picles_lattice_knot_times(double lat_t0, double lat_dt, double t, double dt, double *tks, int32_t cap);
+/* ---- streamed winds: a lattice whose time levels arrive one at a time, from device memory, in stream order (ABI 17) ---
+ * The third source of the wind window, for a coupled run: an atmosphere hands over one level per coupling interval and does not know
+ * the next.  A WIND STREAM is a lattice with regular (x, y) axes as in picles_set_wind_grid (the periodic continuation in x and y stays),
+ * a time axis t_k = t0 + k dt, k = 0, 1, ... WITHOUT periodic continuation, and a ring of n_slots >= 2 level pairs (u, v) in HBM:
+ * level k lives in slot k % n_slots.
+ *
+ * THE TIME RULE.  c = (t - t0) * (1 / dt), evaluated as the lattice sampler evaluates it; if |c - rint(c)| <= 1e-9, c := rint(c) (the
+ * slack of picles_lattice_knots); k = floor(c), f = c - k.  A sample with f == 0 reads level k alone; otherwise it is, per corner,
+ * L_k + (L_k+1 - L_k) f in exactly the operation order of the lattice sampler.  The host computes (k, f) once per sampled time and
+ * hands slot indices and f to the kernel (k_wind_sample_ring).  A result never depends on WHEN a level was pushed.
+ * picles_wind_stream_coord is that rule, host arithmetic only (returns -2 for dt <= 0 or a time before t0).
+ *
+ *   init   replaces whatever winds the context had, as picles_set_wind_grid does; the mode is PICLES_LATTICE_LINEAR and
+ *          picles_set_wind_grid_mode works on it.  Refused: nx, ny < 2, non-positive spacing, n_slots < 2, slab mode, slabs, a nest
+ *          (streamed nests are not carried).  picles_set_slab_mode(1) and picles_nest_init are refused while a stream exists.
+ *   push   level k from planes of nx * ny values, x fastest; dtype PICLES_WIND_F64 | PICLES_WIND_F32, where PICLES_WIND_HOST |
+ *          PICLES_WIND_DEVICE.  A DEVICE push records an event on caller_stream, lets the context's stream wait for it, fills the slot
+ *          (a device-to-device copy for f64, k_wind_ingest for f32: widening is exact) and records an event that caller_stream waits
+ *          for: the caller may overwrite its buffer in stream order.  caller_stream == NULL: the caller has synchronised already, and
+ *          keeps the buffer until the context's stream has passed the copy.  A HOST push is complete on return.  Neither completes a
+ *          pending fused step.  Refused before anything has changed: k is not newest + 1 (the first push of an empty ring may be any
+ *          k >= 0; a level once held is not pushed again or corrected); the slot holds a level the clock's interval still needs,
+ *          k - n_slots >= floor(c(clock)); NULL planes, unknown dtype / where.
+ *   info   n_slots, the oldest and newest level held (-1, -1: none), pushes so far; any pointer may be NULL
+ *   reset  completes a pending fused step (as picles_set_wind_grid_mode does), empties the ring and invalidates the window
+ *
+ * STEPS.  The window of a step is classified by the knots t_k strictly inside it with the rule of picles_lattice_knots: the TWO, KNOT,
+ * POLYLINE and (PICLES_LATTICE_SMOOTH3) PARABOLA forms come out as for an uploaded lattice.  picles_time_step, picles_run_steps,
+ * picles_advance, picles_begin_step and picles_begin_fused_step check BEFORE they enqueue anything that every level the windows of
+ * the next n steps read is held, and refuse with -2 and a text that names the first missing k and its time.  A step with nk interior
+ * knots reads nk + 2 levels: n_slots < nk + 2 is refused with its own text.  picles_seed reads the level(s) bracketing the seed time.
+ * CHECKPOINT.  The fingerprint takes "stream", the geometry, t0, dt, the mode and n_slots, not the contents; the blob holds no levels.
+ * picles_checkpoint_load invalidates the window; levels still in the ring stay valid; a fresh context needs the levels bracketing the
+ * restored clock pushed again before it steps.  Irregular coupling intervals are not carried. */
+#define PICLES_WIND_F64    0
+#define PICLES_WIND_F32    1
+#define PICLES_WIND_HOST   0
+#define PICLES_WIND_DEVICE 1
+int32_t picles_wind_stream_init(picles_ctx *ctx, int32_t nx, int32_t ny, double x0, double dx, double y0, double dy,
+                                double t0, double dt, double mesh_x0, double mesh_y0, int32_t n_slots);
+int32_t picles_wind_stream_push(picles_ctx *ctx, int64_t k, const void *u, const void *v, int32_t dtype, int32_t where, void *caller_stream);
+int32_t picles_wind_stream_info(const picles_ctx *ctx, int32_t *n_slots, int64_t *oldest, int64_t *newest, int64_t *pushes);
+int32_t picles_wind_stream_reset(picles_ctx *ctx);
+int32_t picles_wind_stream_coord(double t0, double dt, double t, int64_t *k, double *f);
 /* node winds currently on the device (own rows); any pointer may be NULL */
 int32_t picles_get_winds(picles_ctx *ctx, double *u0, double *v0, double *u1, double *v1);
 /* the mid-window level of three-level winds; returns 1 (and writes nothing) when the current winds have two levels */
@@ -302,6 +346,11 @@ int32_t picles_diag_shape(const picles_ctx *ctx, int32_t *nxc, int32_t *nyc_loc,
 int32_t picles_diag_push(picles_ctx *ctx);
 int32_t picles_diag_pop(picles_ctx *ctx, void *fields, double *partials, double *time);
 int32_t picles_diag_pending(const picles_ctx *ctx);
+/* export: what push does up to the kernel launch — a pending fused step is completed on the context stream — with the kernel writing
+ * into the CALLER's device buffers: fields_dev (bytes of picles_diag_shape) and partials_dev (n_partials * 7 doubles; may be NULL), the
+ * layout of pop.  No ring slot, no copy to the host; an event recorded behind the kernel is waited for by caller_stream (NULL: the
+ * caller orders itself, e.g. picles_sync).  The same bits as push + pop.  Refuses: not initialised, fields_dev NULL */
+int32_t picles_diag_export(picles_ctx *ctx, void *fields_dev, double *partials_dev, void *caller_stream);
 
 /* ---- station probes: the State value of chosen nodes after every step, with the fused path kept --------------------------------
  * Point output — the series of the sea state at buoys, platforms, validation points — is what the reference's scripts cut out of

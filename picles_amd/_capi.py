@@ -98,10 +98,12 @@ class PiclesSlabPhases(C.Structure):
 
 
 LATTICE_LINEAR, LATTICE_SMOOTH3 = 0, 1
+WIND_F64, WIND_F32 = 0, 1            # picles_wind_stream_push: dtype, where (include/picles_hip.h "streamed winds")
+WIND_HOST, WIND_DEVICE = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 16
+ABI_VERSION = 17
 SLAB_ID_BYTES = 128
 PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
 
@@ -144,6 +146,12 @@ SYMBOLS = {
     "picles_set_wind_grid_mode": (C.c_int32, [_VP, C.c_int32]),
     "picles_lattice_knots": (C.c_int32, [C.c_double, C.c_double, C.c_double, C.c_double, c_double_p]),
     "picles_lattice_knot_times": (C.c_int32, [C.c_double, C.c_double, C.c_double, C.c_double, c_double_p, C.c_int32]),
+    "picles_wind_stream_init": (C.c_int32, [_VP, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, C.c_double, C.c_int32]),
+    "picles_wind_stream_push": (C.c_int32, [_VP, C.c_int64, _VP, _VP, C.c_int32, C.c_int32, _VP]),
+    "picles_wind_stream_info": (C.c_int32, [_VP, c_int32_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "picles_wind_stream_reset": (C.c_int32, [_VP]),
+    "picles_wind_stream_coord": (C.c_int32, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int64), c_double_p]),
     "picles_get_winds": (C.c_int32, [_VP, c_double_p, c_double_p, c_double_p, c_double_p]),
     "picles_seed": (C.c_int32, [_VP, C.c_double]),
     "picles_time_step": (C.c_int32, [_VP, C.c_double, C.c_int32]),
@@ -165,6 +173,7 @@ SYMBOLS = {
     "picles_diag_push": (C.c_int32, [_VP]),
     "picles_diag_pop": (C.c_int32, [_VP, _VP, c_double_p, c_double_p]),
     "picles_diag_pending": (C.c_int32, [_VP]),
+    "picles_diag_export": (C.c_int32, [_VP, _VP, c_double_p, _VP]),
     "picles_probe_init": (C.c_int32, [_VP, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32]),
     "picles_probe_sample": (C.c_int32, [_VP, _VP]),
     "picles_probe_pop": (C.c_int32, [_VP, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int64), c_int32_p]),

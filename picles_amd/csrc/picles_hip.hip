@@ -399,6 +399,58 @@ __global__ void __launch_bounds__(256) k_wind_sample(GridP G, WindGrid Wg, WindS
     }
 }
 
+/* k_wind_sample_ring — the same sample from a wind stream (picles_wind_stream_*): the lattice's time levels live in a ring of slots,
+ * Wg.u / Wg.v are the ring's bases and a slot is one (x, y) plane.  The host has worked out, per level q, the slots of the two time
+ * levels and the weight f (include/picles_hip.h, "the time rule"): uniform over the launch.  f == 0 reads slot s0 alone; otherwise the
+ * operations are k_wind_sample's, in its order */
+struct WindRingOut { int s0[2], s1[2]; double f[2]; double *u[2], *v[2]; };
+template <int NT>
+__global__ void __launch_bounds__(256) k_wind_sample_ring(GridP G, WindGrid Wg, WindRingOut O, long long n)
+{
+    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    int i = (int)(k % G.Nx), j = (int)(k / G.Nx) + G.j_begin;
+    double x = Wg.mesh_x0 + (double)i * Wg.mesh_dx, y = Wg.mesh_y0 + (double)j * Wg.mesh_dy;
+    int ix, iy;
+    double fx, fy;
+    lattice_coord((x - Wg.x0) * Wg.inv_dx, Wg.nx, ix, fx);
+    lattice_coord((y - Wg.y0) * Wg.inv_dy, Wg.ny, iy, fy);
+    size_t sx = 1, sy = (size_t)Wg.nx, st = (size_t)Wg.nx * Wg.ny;
+    const double *F[2] = {Wg.u, Wg.v};
+#pragma unroll
+    for (int q = 0; q < NT; q++) {
+        const double ft = O.f[q];
+        size_t b0 = ix * sx + iy * sy + (size_t)O.s0[q] * st, b1 = ix * sx + iy * sy + (size_t)O.s1[q] * st;
+        double out[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            const double *f = F[c];
+            double c00 = f[b0] + (f[b0 + sx] - f[b0]) * fx;
+            double c10 = f[b0 + sy] + (f[b0 + sy + sx] - f[b0 + sy]) * fx;
+            double c0 = c00 + (c10 - c00) * fy;
+            if (ft != 0.0) {
+                double c01 = f[b1] + (f[b1 + sx] - f[b1]) * fx;
+                double c11 = f[b1 + sy] + (f[b1 + sy + sx] - f[b1 + sy]) * fx;
+                double c1 = c01 + (c11 - c01) * fy;
+                c0 = c0 + (c1 - c0) * ft;
+            }
+            out[c] = c0;
+        }
+        O.u[q][k] = out[0];
+        O.v[q][k] = out[1];
+    }
+}
+
+/* k_wind_ingest — a float32 level of a wind stream into its slot: both planes, widened (exact) */
+__global__ void __launch_bounds__(256) k_wind_ingest(const float *__restrict__ u, const float *__restrict__ v,
+                                                     double *__restrict__ du, double *__restrict__ dv, long long n)
+{
+    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    du[k] = (double)u[k];
+    dv[k] = (double)v[k];
+}
+
 /* ------------------------------------------------------------------------------------------
  * k_wind_poly — coefficients of a polyline window (KParams::wind_nk >= 2; physics.h, wind_eval): from the node's levels
  * L_0 (u0 plane), L_1 .. L_nk (lv planes, one pair per knot), L_nk+1 (u1 plane) the segment slopes per unit s,
@@ -504,6 +556,14 @@ struct WindWindow {
     WindGrid wg{};
     double *d_wgu = nullptr, *d_wgv = nullptr;
     double lat_t0 = 0.0, lat_dt = 0.0;             /* the lattice's first time knot and spacing as the caller gave them (knot times are computed from these) */
+    /* a wind stream (picles_wind_stream_*): a lattice (`lattice` is set too: the step paths are the lattice's) whose
+     * time levels arrive one at a time.  d_wgu / d_wgv are then rings of ring_slots (x, y) planes, level k in slot k % ring_slots;
+     * the levels [ring_oldest(), ring_newest] are held (ring_newest < 0: none).  Everything that reads or writes a slot is enqueued
+     * on the context stream: stream order is all the ordering the ring needs */
+    bool ring = false;
+    int ring_slots = 0;
+    long long ring_first = -1, ring_newest = -1, ring_pushes = 0;
+    hipEvent_t ring_in = nullptr, ring_out = nullptr;      /* a device push: caller stream -> context stream -> caller stream */
     /* the window on the device */
     Shape shape;
     double t0 = 0.0, t1 = 0.0;
@@ -518,6 +578,12 @@ struct WindWindow {
     bool static_() const { return shape.form == STATIC; }
     bool polyline() const { return shape.form == POLYLINE; }
     bool from_lattice() const { return lattice; }
+    bool streamed() const { return ring; }
+    long long ring_oldest() const { return ring_newest < 0 ? -1 : std::max(ring_first, ring_newest - ring_slots + 1); }
+    bool ring_holds(long long k) const { return ring_newest >= 0 && k >= ring_oldest() && k <= ring_newest; }
+    int ring_levels(picles_ctx *c, double t, double dt, long long n_steps, const char *who) const;      /* are the levels of the next steps' windows held? */
+    int ring_seed_levels(picles_ctx *c, double t) const;
+    void ring_off() { ring = false; ring_slots = 0; ring_first = ring_newest = -1; }
     bool lattice_polyline_ahead(double t, double dt) const;      /* will the lattice's window over [t, t + dt] be a polyline? */
     /* does the window start where the pending step started, with (u1, v1) holding the lattice at the clock: can prepare() follow it? */
     bool contiguous_with(double pend_t, double clock) const { return held && held_t == clock && t0 == pend_t && !static_(); }
@@ -603,6 +669,7 @@ struct picles_ctx {
     DiagP diag{};
     int diag_nfields = 0, diag_npart = 0;
     size_t diag_field_bytes = 0, diag_part_off = 0, diag_slot_bytes = 0;
+    double *diag_scratch = nullptr;                /* picles_diag_export without a partials buffer: where the kernel's partials go */
     int probe_n = 0;
     int *probe_nodes = nullptr;                    /* device: i plane, then the LOCAL row plane */
     Cadence probe_cad;                             /* steps: model steps completed since picles_probe_init */
@@ -1034,6 +1101,7 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
 
     c->store.release();
     c->diag_ring.release();
+    if (c->diag_scratch) hipFree(c->diag_scratch);
     probe_release(c);
     if (c->trk) hipDeviceSynchronize();         /* samples issued on caller streams write the table about to go */
     track_release(c);
@@ -1154,6 +1222,8 @@ void WindWindow::release(Arrays &A)
 {
     for (double **p : {&A.uP, &A.vP, &um_buf, &vm_buf, &lv_buf, &xb_buf, &d_wgu, &d_wgv}) { hipFree(*p); *p = nullptr; }
     poly_cap = 0;
+    for (hipEvent_t *e : {&ring_in, &ring_out}) { if (*e) hipEventDestroy(*e); *e = nullptr; }
+    ring_off();
 }
 
 static int set_wind_levels(picles_ctx *c, const double *u0, const double *v0, double t0,
@@ -1173,6 +1243,7 @@ static int set_wind_levels(picles_ctx *c, const double *u0, const double *v0, do
     sh.tk[0] = tk;
     { int rc = W.need(c, sh); if (rc) return rc; }      /* (first: a call that fails here has changed nothing) */
     W.lattice = false;
+    W.ring_off();
     Arrays &A = c->A;
     size_t b = (size_t)A.n * 8;
     HIPCHK(c, hipMemcpyAsync(A.u0, u0, b, hipMemcpyHostToDevice, c->stream));
@@ -1282,6 +1353,7 @@ PX_EXPORT int32_t picles_set_wind_grid(picles_ctx *c, int32_t nx, int32_t ny, in
     WindWindow &W = c->wind;
     if (W.d_wgu) { hipFree(W.d_wgu); hipFree(W.d_wgv); W.d_wgu = W.d_wgv = nullptr; }
     W.lattice = false;                   /* (until the new one is up: a failed upload leaves the window on the device, not a freed lattice) */
+    W.ring_off();
     size_t nb = (size_t)nx * ny * nt * 8;
     { int rc = W.make_pair(c, W.d_wgu, nb, W.d_wgv, nb); if (rc) return rc; }
     HIPCHK(c, hipMemcpy(W.d_wgu, u, nb, hipMemcpyHostToDevice));
@@ -1372,6 +1444,36 @@ int WindWindow::sample(picles_ctx *c, const Shape &sh, double t, double dt, bool
     if (sh.form == PARABOLA || sh.form == KNOT) L[m++] = {sh.form == KNOT ? sh.tk[0] : t + 0.5 * dt, um_buf, vm_buf};
     for (int k = 0; sh.form == POLYLINE && k < sh.nk; k++) L[m++] = {sh.tk[k], lv_buf + (size_t)(2 * k) * n, lv_buf + (size_t)(2 * k + 1) * n};
     L[m++] = {t + dt, A.u1, A.v1};
+    if (ring) {
+        /* the same launches from the ring: (slots, f) per level by the time rule.  The entry points have checked that the levels are held */
+        auto put = [&](WindRingOut &O, int q, double tq, double *u, double *v) {
+            int64_t k = 0;
+            double f = 0.0;
+            (void)picles_wind_stream_coord(lat_t0, lat_dt, tq, &k, &f);
+            O.s0[q] = (int)(k % ring_slots);
+            O.s1[q] = f != 0.0 ? (int)((k + 1) % ring_slots) : O.s0[q];
+            O.f[q] = f;
+            O.u[q] = u; O.v[q] = v;
+        };
+        if (with0) {
+            WindRingOut O{};
+            put(O, 0, t, A.u0, A.v0);
+            hipLaunchKernelGGL(k_wind_sample_ring<1>, grid, block, 0, s, c->G, wg, O, A.n);
+        }
+        for (int k = 0; k < m; k += 2) {
+            WindRingOut O{};
+            put(O, 0, L[k].t, L[k].u, L[k].v);
+            if (k + 1 < m) {
+                put(O, 1, L[k + 1].t, L[k + 1].u, L[k + 1].v);
+                hipLaunchKernelGGL(k_wind_sample_ring<2>, grid, block, 0, s, c->G, wg, O, A.n);
+            } else
+                hipLaunchKernelGGL(k_wind_sample_ring<1>, grid, block, 0, s, c->G, wg, O, A.n);
+        }
+        HIPCHK(c, hipGetLastError());
+        held_t = t + dt;
+        held = true;
+        return set(c, sh, t, t + dt, s);
+    }
     if (with0) {
         WindSampleOut O = {{t, 0.0}, {A.u0, nullptr}, {A.v0, nullptr}};
         hipLaunchKernelGGL(k_wind_sample<1>, grid, block, 0, s, c->G, wg, O, A.n);
@@ -1402,6 +1504,200 @@ int WindWindow::prepare(picles_ctx *c, double t, double dt, bool follow, hipStre
     if (follow) rotate(c->A);
     else if (reuse) reuse_swap(c->A);
     return sample(c, sh, t, dt, !follow && !reuse, s);
+}
+
+/* ---- the wind stream (the contract: include/picles_hip.h, "streamed winds") ---- */
+/* the time rule: host arithmetic only */
+PX_EXPORT int32_t picles_wind_stream_coord(double t0, double dt, double t, int64_t *k, double *f)
+{
+    if (!(dt > 0.0)) return -2;
+    const double inv_dt = 1.0 / dt;
+    double cc = (t - t0) * inv_dt;               /* as k_wind_sample forms it */
+    const double r = __builtin_rint(cc);
+    if (__builtin_fabs(cc - r) <= 1e-9) cc = r;
+    if (!(cc >= 0.0) || !(cc < 9.0e15)) return -2;
+    const double fl = __builtin_floor(cc);
+    if (k) *k = (int64_t)fl;
+    if (f) *f = cc - fl;
+    return 0;
+}
+
+/* every level the windows of the next n_steps steps of length dt from time t read — [floor(c(t)), ceil(c(t + dt))] of each — must be
+ * held, and one window's levels must fit the ring together.  Asked before anything is enqueued (the style of bforce_window) */
+int WindWindow::ring_levels(picles_ctx *c, double t, double dt, long long n_steps, const char *who) const
+{
+    if (!ring || n_steps <= 0 || !(dt > 0.0)) return 0;
+    char b[512];
+    for (long long s = 0; s < n_steps; s++, t += dt) {
+        int64_t k0 = 0, k1 = 0;
+        double f0 = 0.0, f1 = 0.0;
+        if (picles_wind_stream_coord(lat_t0, lat_dt, t, &k0, &f0) || picles_wind_stream_coord(lat_t0, lat_dt, t + dt, &k1, &f1)) {
+            snprintf(b, sizeof b, "%s: step %lld of this call, [%.17g, %.17g], starts before the first time level of the wind stream (t0 = %.17g): "
+                                  "a stream has no periodic continuation in t", who, s + 1, t, t + dt, lat_t0);
+            return fail(c, -2, b);
+        }
+        if (f1 != 0.0) k1++;
+        if (k1 - k0 + 1 > ring_slots) {
+            snprintf(b, sizeof b, "%s: step %lld of this call, [%.17g, %.17g], has %lld time knots of the wind stream (interval %.17g s) inside and reads "
+                                  "%lld levels, the ring holds %d: a step with nk interior knots needs n_slots >= nk + 2 "
+                                  "(picles_wind_stream_init with more slots, or shorter steps)",
+                     who, s + 1, t, t + dt, (long long)(k1 - k0 - 1), lat_dt, (long long)(k1 - k0 + 1), ring_slots);
+            return fail(c, -2, b);
+        }
+        for (long long k = k0; k <= k1; k++)
+            if (!ring_holds(k)) {
+                snprintf(b, sizeof b, "%s: step %lld of this call, [%.17g, %.17g], reads level k = %lld (t = %.17g) of the wind stream, which is not held "
+                                      "(levels held: %lld .. %lld): picles_wind_stream_push it first, or take fewer steps per call",
+                         who, s + 1, t, t + dt, k, lat_t0 + (double)k * lat_dt, ring_oldest(), ring_newest);
+                return fail(c, -2, b);
+            }
+    }
+    return 0;
+}
+/* picles_seed reads level 0 of its window alone: the level(s) bracketing time t */
+int WindWindow::ring_seed_levels(picles_ctx *c, double t) const
+{
+    if (!ring) return 0;
+    int64_t k = 0;
+    double f = 0.0;
+    char b[384];
+    if (picles_wind_stream_coord(lat_t0, lat_dt, t, &k, &f)) {
+        snprintf(b, sizeof b, "picles_seed: the seed reads the wind at t = %.17g, before the first time level of the wind stream (t0 = %.17g)", t, lat_t0);
+        return fail(c, -2, b);
+    }
+    for (long long q = k; q <= k + (f != 0.0 ? 1 : 0); q++)
+        if (!ring_holds(q)) {
+            snprintf(b, sizeof b, "picles_seed: the seed reads the wind at t = %.17g: level k = %lld (t = %.17g) of the wind stream is not held "
+                                  "(levels held: %lld .. %lld): picles_wind_stream_push it first",
+                     t, q, lat_t0 + (double)q * lat_dt, ring_oldest(), ring_newest);
+            return fail(c, -2, b);
+        }
+    return 0;
+}
+
+PX_EXPORT int32_t picles_wind_stream_init(picles_ctx *c, int32_t nx, int32_t ny, double x0, double dx, double y0, double dy,
+                                          double t0, double dt, double mesh_x0, double mesh_y0, int32_t n_slots)
+{
+    if (!c) return -1;
+    if (nx < 2 || ny < 2 || !(dx > 0) || !(dy > 0) || !(dt > 0)) return fail(c, -2, "picles_wind_stream_init: the lattice needs >= 2 knots per space axis and positive spacing");
+    if (n_slots < 2 || n_slots > 4096) return fail(c, -2, "picles_wind_stream_init: n_slots must be 2 ... 4096 (two levels bracket a time)");
+    if (!c->G.single_slab || c->ring || !(c->G.j_begin == 0 && c->G.ny_loc == c->G.Ny))
+        return fail(c, -5, "picles_wind_stream_init: slabs, slab mode and the native ring do not carry a wind stream: a whole-grid context is needed");
+    if (c->nest || !c->nest_children.empty())
+        return fail(c, -5, "picles_wind_stream_init: the context is part of a nest: streamed nests are not carried (picles_nest_free first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flush(c); if (rc) return rc; }
+    HIPCHK(c, hipDeviceSynchronize());
+    WindWindow &W = c->wind;
+    if (!W.ring_in) {
+        HIPCHK(c, hipEventCreateWithFlags(&W.ring_in, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&W.ring_out, hipEventDisableTiming));
+    }
+    if (W.d_wgu) { hipFree(W.d_wgu); hipFree(W.d_wgv); W.d_wgu = W.d_wgv = nullptr; }
+    W.lattice = false;                   /* (until the ring is up, as picles_set_wind_grid) */
+    W.ring_off();
+    const size_t nb = (size_t)nx * ny * n_slots * 8;
+    { int rc = W.make_pair(c, W.d_wgu, nb, W.d_wgv, nb); if (rc) return rc; }
+    HIPCHK(c, hipMemsetAsync(W.d_wgu, 0, nb, c->stream));
+    HIPCHK(c, hipMemsetAsync(W.d_wgv, 0, nb, c->stream));
+    c->fp_lattice = 0;
+    WindGrid &w = W.wg;
+    w.nx = nx; w.ny = ny; w.nt = n_slots;
+    w.x0 = x0; w.inv_dx = 1.0 / dx; w.y0 = y0; w.inv_dy = 1.0 / dy; w.t0 = t0; w.inv_dt = 1.0 / dt;
+    w.mesh_x0 = mesh_x0; w.mesh_y0 = mesh_y0; w.mesh_dx = c->g.dx; w.mesh_dy = c->g.dy;
+    w.u = W.d_wgu; w.v = W.d_wgv;
+    W.lat_t0 = t0; W.lat_dt = dt;
+    (void)W.drop_middle(c);
+    W.lattice = true;
+    W.ring = true;
+    W.ring_slots = n_slots;
+    W.ring_pushes = 0;
+    W.mode = PICLES_LATTICE_LINEAR;
+    W.invalidate();
+    return 0;
+}
+
+PX_EXPORT int32_t picles_wind_stream_push(picles_ctx *c, int64_t k, const void *u, const void *v, int32_t dtype, int32_t where, void *caller_stream)
+{
+    if (!c) return -1;
+    WindWindow &W = c->wind;
+    if (!W.streamed()) return fail(c, -2, "picles_wind_stream_push: picles_wind_stream_init first");
+    if (!u || !v) return fail(c, -2, "picles_wind_stream_push: both planes are needed");
+    if ((dtype != PICLES_WIND_F64 && dtype != PICLES_WIND_F32) || (where != PICLES_WIND_HOST && where != PICLES_WIND_DEVICE))
+        return fail(c, -2, "picles_wind_stream_push: dtype must be PICLES_WIND_F64 or _F32, where PICLES_WIND_HOST or _DEVICE");
+    char b[384];
+    if (k < 0 || (W.ring_newest >= 0 && k != W.ring_newest + 1)) {
+        snprintf(b, sizeof b, "picles_wind_stream_push: level k = %lld is out of order: the levels arrive one at a time, the next one is k = %lld "
+                              "(a level already held is not pushed again; picles_wind_stream_reset starts over)",
+                 (long long)k, W.ring_newest >= 0 ? W.ring_newest + 1 : 0LL);
+        return fail(c, -2, b);
+    }
+    int64_t kc = 0;
+    double fc = 0.0;
+    if (picles_wind_stream_coord(W.lat_t0, W.lat_dt, c->clock, &kc, &fc) == 0 && W.ring_holds(k - W.ring_slots) && k - W.ring_slots >= kc) {
+        snprintf(b, sizeof b, "picles_wind_stream_push: level k = %lld goes to the slot of level %lld, which the interval of the clock (t = %.17g, "
+                              "levels %lld and up) still needs: step the model first, or picles_wind_stream_init with more than %d slots",
+                 (long long)k, (long long)(k - W.ring_slots), c->clock, (long long)kc, W.ring_slots);
+        return fail(c, -2, b);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)W.wg.nx * W.wg.ny;
+    double *du = W.d_wgu + (size_t)(k % W.ring_slots) * n, *dv = W.d_wgv + (size_t)(k % W.ring_slots) * n;
+    hipStream_t cs = (hipStream_t)caller_stream;
+    if (where == PICLES_WIND_DEVICE) {
+        if (cs) {      /* what the caller enqueued so far produces the planes */
+            HIPCHK(c, hipEventRecord(W.ring_in, cs));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, W.ring_in, 0));
+        }
+        if (dtype == PICLES_WIND_F64) {
+            HIPCHK(c, hipMemcpyAsync(du, u, n * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(dv, v, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            hipLaunchKernelGGL(k_wind_ingest, dim3(nblocks((long long)n, 256)), dim3(256), 0, c->stream, (const float *)u, (const float *)v, du, dv, (long long)n);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (cs) {      /* the caller may overwrite its planes in stream order */
+            HIPCHK(c, hipEventRecord(W.ring_out, c->stream));
+            HIPCHK(c, hipStreamWaitEvent(cs, W.ring_out, 0));
+        }
+    } else {
+        std::vector<double> wide;
+        const double *hu = (const double *)u, *hv = (const double *)v;
+        if (dtype == PICLES_WIND_F32) {
+            wide.resize(2 * n);
+            for (size_t q = 0; q < n; q++) { wide[q] = (double)((const float *)u)[q]; wide[n + q] = (double)((const float *)v)[q]; }
+            hu = wide.data(); hv = wide.data() + n;
+        }
+        HIPCHK(c, hipMemcpyAsync(du, hu, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dv, hv, n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));      /* complete on return: the caller may reuse its host buffers */
+    }
+    if (W.ring_newest < 0) W.ring_first = k;
+    W.ring_newest = k;
+    W.ring_pushes++;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_wind_stream_info(const picles_ctx *c, int32_t *n_slots, int64_t *oldest, int64_t *newest, int64_t *pushes)
+{
+    if (!c || !c->wind.streamed()) return -1;
+    const WindWindow &W = c->wind;
+    if (n_slots) *n_slots = W.ring_slots;
+    if (oldest) *oldest = W.ring_oldest();
+    if (newest) *newest = W.ring_newest;
+    if (pushes) *pushes = W.ring_pushes;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_wind_stream_reset(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->wind.streamed()) return fail(c, -2, "picles_wind_stream_reset: picles_wind_stream_init first");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flush(c); if (rc) return rc; }      /* (a pending fused step is completed under its own window, as picles_set_wind_grid_mode does) */
+    c->wind.ring_first = c->wind.ring_newest = -1;
+    c->wind.invalidate();
+    return 0;
 }
 
 PX_EXPORT int32_t picles_get_winds(picles_ctx *c, double *u0, double *v0, double *u1, double *v1)
@@ -1436,8 +1732,30 @@ static int seed_at(picles_ctx *c, double t0, double wind_t, double wind_dt)
 {
     HIPCHK(c, hipSetDevice(c->device));
     if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* earlier steps may still run on caller / ring streams */
+    { int rc = c->wind.ring_seed_levels(c, wind_t); if (rc) return rc; }      /* (a wind stream: refused before anything has changed) */
     c->clock = t0;
-    if (c->wind.from_lattice()) {   /* winds at t = 0.0 seed the particles (run.jl:213-215) */
+    if (c->wind.streamed()) {
+        /* a wind stream may not hold the window's end yet, and only level 0 is read: the level at wind_t in both planes of the seed's
+         * two-level window (the same level 0, to the bit), which the first step replaces by its own */
+        WindWindow &W = c->wind;
+        int64_t k = 0;
+        double f = 0.0;
+        (void)picles_wind_stream_coord(W.lat_t0, W.lat_dt, wind_t, &k, &f);
+        WindRingOut O{};
+        for (int q = 0; q < 2; q++) {
+            O.s0[q] = (int)(k % W.ring_slots);
+            O.s1[q] = f != 0.0 ? (int)((k + 1) % W.ring_slots) : O.s0[q];
+            O.f[q] = f;
+        }
+        O.u[0] = c->A.u0; O.v[0] = c->A.v0; O.u[1] = c->A.u1; O.v[1] = c->A.v1;
+        hipLaunchKernelGGL(k_wind_sample_ring<2>, dim3(nblocks(c->A.n, 256)), dim3(256), 0, c->stream, c->G, W.wg, O, c->A.n);
+        HIPCHK(c, hipGetLastError());
+        WindWindow::Shape two;
+        two.form = WindWindow::TWO;
+        int rc = W.set(c, two, wind_t, wind_t + wind_dt, c->stream);
+        if (rc) return rc;
+        W.invalidate();
+    } else if (c->wind.from_lattice()) {   /* winds at t = 0.0 seed the particles (run.jl:213-215) */
         /* only level 0 is read (k_seed evaluates the window at its start); the window's end is sampled at the seed time scale, whatever
          * lies between: a plain two-level window, replaced by the first step's own */
         c->wind.invalidate();
@@ -1509,6 +1827,7 @@ static void step_begun(picles_ctx *c, double dt, int flags)
 static int begin_step(picles_ctx *c, double dt, int32_t flags)
 {
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
+    { int rc = c->wind.ring_levels(c, c->clock, dt, 1, "picles_begin_step"); if (rc) return rc; }      /* (before the flush: a refused call has changed nothing) */
     { int rc = flush(c); if (rc) return rc; }
     if (c->wind.from_lattice()) {  /* (first: a window the lattice cannot carry is refused before the step has changed anything) */
         HIPCHK(c, hipSetDevice(c->device));
@@ -1743,6 +2062,7 @@ PX_EXPORT int32_t picles_begin_fused_step(picles_ctx *c, double dt)
     if (!c) return -1;
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     { int rc = bforce_window(c, dt, 1, "picles_begin_fused_step"); if (rc) return rc; }
+    { int rc = c->wind.ring_levels(c, c->clock, dt, 1, "picles_begin_fused_step"); if (rc) return rc; }
     if (!step_fusable(c, PICLES_STEP_ZERO_FIRST, dt)) return 1;
     /* PICLES_WAVEROW=require: every launch of the step — the whole grid, or a slab's edge and interior rows — must take k_step_waverow;
      * refused here, before the step has changed anything */
@@ -1864,6 +2184,7 @@ PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
     if (!(dt > 0.0)) return fail(c, -2, "dt must be positive");
     { int rc = probe_room(c, 1, "picles_time_step"); if (rc) return rc; }      /* refused before anything has changed */
     { int rc = bforce_window(c, dt, 1, "picles_time_step"); if (rc) return rc; }
+    { int rc = c->wind.ring_levels(c, c->clock, dt, 1, "picles_time_step"); if (rc) return rc; }
     { int rc = track_step_ok(c, dt, "picles_time_step"); if (rc) return rc; }
     int rc = time_step_phases(c, dt, flags);
     if (rc) return rc;
@@ -1883,6 +2204,7 @@ PX_EXPORT int32_t picles_run_steps(picles_ctx *c, double dt, int32_t n_steps)
     if (c->G.single_slab && dt > 0.0) { int rc = probe_room(c, n_steps, "picles_run_steps"); if (rc) return rc; }   /* up front, not half-way */
     if (c->G.single_slab && dt > 0.0) { int rc = bforce_window(c, dt, n_steps, "picles_run_steps"); if (rc) return rc; }   /* every start time, before anything is enqueued */
     if (n_steps > 0) { int rc = track_step_ok(c, dt, "picles_run_steps"); if (rc) return rc; }
+    { int rc = c->wind.ring_levels(c, c->clock, dt, n_steps, "picles_run_steps"); if (rc) return rc; }      /* a wind stream: every level, before anything is enqueued */
     const bool region = c->timing && c->timing_mode == 2 && n_steps > 0;
     if (region) {      /* one event pair around the whole call, on the stream the launches go to */
         HIPCHK(c, hipSetDevice(c->device));
@@ -2224,10 +2546,30 @@ PX_EXPORT int32_t picles_diag_shape(const picles_ctx *c, int32_t *nxc, int32_t *
 PX_EXPORT int32_t picles_diag_pending(const picles_ctx *c) { return c ? c->diag_ring.count : -1; }
 
 template <int CX, bool VEC>
-static void diag_launch(picles_ctx *c, unsigned char *slot)
+static void diag_launch(picles_ctx *c, float *fields, double *partials)
 {
     hipLaunchKernelGGL((k_diag<CX, VEC>), dim3((unsigned)c->diag_npart), dim3(DIAG_TILE), 0, c->stream, c->diag, (const double *)c->A.state,
-                       (float *)slot, (double *)(slot + c->diag_part_off));
+                       fields, partials);
+}
+
+/* State at the step boundary, then the kernel on the context stream into (fields, partials): a ring slot (push) or the caller's
+ * device buffers (export) */
+static int diag_run(picles_ctx *c, float *fields, double *partials)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flush(c); if (rc) return rc; }
+    if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* an un-fused slab step leaves its scatter on the ring's stream M */
+    const bool vec = (c->diag.Nx & 1) == 0;                  /* every cell's row segment then starts on a 16-byte boundary */
+    timing_begin(c, c->stream, 4);
+    switch (c->diag.cx) {
+    case 1: diag_launch<1, false>(c, fields, partials); break;
+    case 2: if (vec) diag_launch<2, true>(c, fields, partials); else diag_launch<2, false>(c, fields, partials); break;
+    case 4: if (vec) diag_launch<4, true>(c, fields, partials); else diag_launch<4, false>(c, fields, partials); break;
+    default: diag_launch<0, false>(c, fields, partials);
+    }
+    timing_end(c, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return 0;
 }
 
 PX_EXPORT int32_t picles_diag_push(picles_ctx *c)
@@ -2236,21 +2578,32 @@ PX_EXPORT int32_t picles_diag_push(picles_ctx *c)
     if (!c->diag_ring.cap) return fail(c, -2, "picles_diag_init first");
     unsigned char *d = c->diag_ring.next_slot();
     if (!d) return fail(c, -3, "diagnostics ring full: pop first");
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc = flush(c); if (rc) return rc; }
-    if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* an un-fused slab step leaves its scatter on the ring's stream M */
-    const bool vec = (c->diag.Nx & 1) == 0;                  /* every cell's row segment then starts on a 16-byte boundary */
-    timing_begin(c, c->stream, 4);
-    switch (c->diag.cx) {
-    case 1: diag_launch<1, false>(c, d); break;
-    case 2: if (vec) diag_launch<2, true>(c, d); else diag_launch<2, false>(c, d); break;
-    case 4: if (vec) diag_launch<4, true>(c, d); else diag_launch<4, false>(c, d); break;
-    default: diag_launch<0, false>(c, d);
-    }
-    timing_end(c, c->stream);
-    HIPCHK(c, hipGetLastError());
+    { int rc = diag_run(c, (float *)d, (double *)(d + c->diag_part_off)); if (rc) return rc; }
     /* stream-ordered behind the step that produced State; the D2H leg runs beside the next steps */
     return c->diag_ring.ship(c, d, c->stream, c->diag_slot_bytes, 0);
+}
+
+/* the same kernel into the caller's device buffers: no slot, no copy to the host; the caller's stream waits for the kernel */
+PX_EXPORT int32_t picles_diag_export(picles_ctx *c, void *fields_dev, double *partials_dev, void *caller_stream)
+{
+    if (!c) return -1;
+    if (!c->diag_ring.cap) return fail(c, -2, "picles_diag_init first");
+    if (!fields_dev) return fail(c, -2, "picles_diag_export: no device buffer for the fields");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!partials_dev) {      /* the kernel writes its partials somewhere: a block of the context's own, made on first use */
+        if (!c->diag_scratch) HIPCHK(c, hipMalloc(&c->diag_scratch, (size_t)c->diag_npart * 7 * 8));
+        partials_dev = c->diag_scratch;
+    }
+    if (caller_stream) {      /* whatever the caller still has reading or writing its buffers comes first */
+        HIPCHK(c, hipEventRecord(c->ev_ctx, (hipStream_t)caller_stream));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ctx, 0));
+    }
+    { int rc = diag_run(c, (float *)fields_dev, partials_dev); if (rc) return rc; }
+    if (caller_stream) {
+        HIPCHK(c, hipEventRecord(c->ev_ctx, c->stream));
+        HIPCHK(c, hipStreamWaitEvent((hipStream_t)caller_stream, c->ev_ctx, 0));
+    }
+    return 0;
 }
 
 PX_EXPORT int32_t picles_diag_pop(picles_ctx *c, void *fields, double *partials, double *time)
@@ -3221,6 +3574,8 @@ PX_EXPORT int32_t picles_nest_init(picles_ctx *c, picles_ctx *p, int32_t n_corne
                            ": create both contexts on one device");
     if (!c->G.single_slab || c->ring || !p->G.single_slab || p->ring)
         return fail(c, -5, "picles_nest_init: slabs, slab mode and the native ring do not nest: both contexts must be whole-grid contexts");
+    if (c->wind.streamed() || p->wind.streamed())
+        return fail(c, -5, "picles_nest_init: the child or the parent holds a wind stream (picles_wind_stream_*): streamed nests are not carried");
     if (!c->bf_n) return fail(c, -2, "picles_nest_init: the child has no boundary forcing set: picles_bforce_init with the nodes to force first");
     if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string("picles_nest_init") + NEST_NO_EXT_STREAMS);
     if (n_corner < 1 || !corner_ij || !index || !weight)
@@ -3554,6 +3909,7 @@ PX_EXPORT int32_t picles_set_slab_mode(picles_ctx *c, int32_t on)
     if (on && c->bf_n) return fail(c, -5, std::string("picles_set_slab_mode") + BFORCE_NO_SLABS);
     if (on && c->trk) return fail(c, -5, "picles_set_slab_mode: the context holds a track set (picles_track_free first): the corners of an event may lie on two slabs");
     if (on && !c->nest_children.empty()) return fail(c, -5, "picles_set_slab_mode: the context is the parent of a nest (picles_nest_free on its children first)");
+    if (on && c->wind.streamed()) return fail(c, -5, "picles_set_slab_mode: the context holds a wind stream (picles_wind_stream_*), which slabs do not carry: picles_set_winds or picles_set_wind_grid first");
     if (on) {
         if ((G.periodic_y && G.Ny <= 2 * G.R) || G.ny_loc < G.R)
             return fail(c, -2, "slab: periodic y axis not longer than 2*halo_rows, or fewer own rows than halo_rows");
@@ -4102,6 +4458,13 @@ static uint64_t ckpt_fingerprint(const picles_ctx *c)
     h = fp_bytes(h, c->h_mask.data(), c->h_mask.size());
     h = fp_val(h, c->G.single_slab); h = fp_val(h, c->halo0);
     h = fp_val(h, (int32_t)(c->A.m11 != nullptr)); h = fp_val(h, c->fp_metric);
+    if (c->wind.streamed()) {      /* a wind stream: its geometry, time axis, mode and ring size — not its contents */
+        const WindGrid &w = c->wind.wg;
+        h = fp_bytes(h, "stream", 6);
+        h = fp_val(h, c->wind.mode); h = fp_val(h, w.nx); h = fp_val(h, w.ny); h = fp_val(h, c->wind.ring_slots);
+        for (double v : {w.x0, w.inv_dx, w.y0, w.inv_dy, c->wind.lat_t0, c->wind.lat_dt, w.mesh_x0, w.mesh_y0}) h = fp_val(h, v);
+        return h;
+    }
     h = fp_val(h, (int32_t)c->wind.from_lattice());
     if (c->wind.from_lattice()) {
         const WindGrid &w = c->wind.wg;
@@ -4234,7 +4597,7 @@ PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t 
     bool same = h.fingerprint == ckpt_fingerprint(c) && h.payload_bytes == payload && h.n == c->A.n && h.nseg == CKPT_NSEG;
     for (int k = 0; same && k < CKPT_NSEG; k++) same = h.seg_off[k] == S.off[k] && h.seg_len[k] == S.len[k];
     if (!same) return fail(c, PICLES_CKPT_E_CONFIG, "picles_checkpoint_load: the blob was written by a model of another configuration "
-                                                    "(grid, mask, physics, ODE settings, metric, wind lattice, slab rows or slab mode differ)");
+                                                    "(grid, mask, physics, ODE settings, metric, wind lattice or wind stream, slab rows or slab mode differ)");
     const GridP &G = c->G;
     const int R = h.halo_rows;
     if (R < 1 || R > 1024 || (!G.single_slab && ((G.periodic_y && G.Ny <= 2 * R) || G.ny_loc < R)) || h.mr_w < 0 || h.mr_w > 4 || (h.cur & ~1))

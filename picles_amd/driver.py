@@ -261,6 +261,69 @@ class HipModel:
         if mode != K.LATTICE_LINEAR:
             self._ck(self.lib.picles_set_wind_grid_mode(self.h, mode), "picles_set_wind_grid_mode")
 
+    # ---- streamed winds (picles_wind_stream_*: a lattice whose time levels arrive one at a time, from device memory) ----
+    def wind_stream_init(self, nx, ny, x0, dx, y0, dy, t0, dt, mesh_x0, mesh_y0, n_slots=3, time_mode="linear"):
+        """a ring of n_slots >= 2 (u, v) levels on an (nx, ny) lattice, level k at t0 + k dt; replaces whatever winds the model had"""
+        mode = {"linear": K.LATTICE_LINEAR, "smooth3": K.LATTICE_SMOOTH3}[time_mode]
+        self._ck(self.lib.picles_wind_stream_init(self.h, int(nx), int(ny), float(x0), float(dx), float(y0), float(dy), float(t0), float(dt),
+                                                  float(mesh_x0), float(mesh_y0), int(n_slots)), "picles_wind_stream_init")
+        self._stream_shape = (int(nx), int(ny))
+        if mode != K.LATTICE_LINEAR:
+            self._ck(self.lib.picles_set_wind_grid_mode(self.h, mode), "picles_set_wind_grid_mode")
+
+    def wind_stream_push(self, k, u, v):
+        """level k: NumPy arrays (host; float32 or float64, anything else is converted to float64) or torch CUDA tensors (float32 /
+        float64, contiguous), shape (ny, nx) or flat — nx * ny values, x fastest.  A tensor is handed over by pointer on torch's
+        current stream: the library orders its copy behind what that stream holds, and the stream behind the copy"""
+        nx, ny = getattr(self, "_stream_shape", (0, 0))
+        n = nx * ny
+        if hasattr(u, "data_ptr"):
+            import torch
+            for a in (u, v):
+                if not a.is_cuda or a.dtype not in (torch.float32, torch.float64) or not a.is_contiguous():
+                    raise ValueError("wind_stream_push: tensors must live on the device, be float32 or float64 and contiguous")
+                if a.numel() != n or (a.dim() != 1 and tuple(a.shape) != (ny, nx)):
+                    raise ValueError(f"wind_stream_push: a level is {ny} x {nx} values (shape (ny, nx) or flat), got {tuple(a.shape)}")
+            if u.dtype != v.dtype:
+                raise ValueError("wind_stream_push: u and v must have one dtype")
+            dtype = K.WIND_F32 if u.dtype == torch.float32 else K.WIND_F64
+            cur = torch.cuda.current_stream(u.device)
+            if cur.cuda_stream:
+                self._ck(self.lib.picles_wind_stream_push(self.h, int(k), u.data_ptr(), v.data_ptr(), dtype, K.WIND_DEVICE, cur.cuda_stream),
+                         "picles_wind_stream_push")
+                return
+            # torch's default stream is the null stream, which the C ABI reads as "already synchronised": the hand-over goes through
+            # a side stream ordered behind and in front of it, so the host still does not wait
+            side = getattr(self, "_stream_side", None)
+            if side is None:
+                side = self._stream_side = torch.cuda.Stream(u.device)
+            side.wait_stream(cur)
+            try:
+                self._ck(self.lib.picles_wind_stream_push(self.h, int(k), u.data_ptr(), v.data_ptr(), dtype, K.WIND_DEVICE, side.cuda_stream),
+                         "picles_wind_stream_push")
+            finally:
+                cur.wait_stream(side)
+            return
+        f32 = all(getattr(a, "dtype", None) == np.float32 for a in (u, v))
+        dt = np.float32 if f32 else np.float64
+        u, v = (np.ascontiguousarray(np.asarray(a, dtype=dt)) for a in (u, v))
+        for a in (u, v):
+            if a.size != n or (a.ndim != 1 and a.shape != (ny, nx)):
+                raise ValueError(f"wind_stream_push: a level is {ny} x {nx} values (shape (ny, nx) or flat), got {a.shape}")
+        self._ck(self.lib.picles_wind_stream_push(self.h, int(k), u.ctypes.data, v.ctypes.data, K.WIND_F32 if f32 else K.WIND_F64,
+                                                  K.WIND_HOST, None), "picles_wind_stream_push")
+
+    def wind_stream_info(self):
+        """(n_slots, oldest level held, newest level held, pushes so far); oldest = newest = -1: the ring is empty.  No device work"""
+        s = C.c_int32()
+        a = [C.c_int64() for _ in range(3)]
+        if self.lib.picles_wind_stream_info(self.h, C.byref(s), *[C.byref(x) for x in a]) != 0:
+            raise K.PiclesError("picles_wind_stream_info failed: wind_stream_init first")
+        return (s.value,) + tuple(x.value for x in a)
+
+    def wind_stream_reset(self):
+        self._ck(self.lib.picles_wind_stream_reset(self.h), "picles_wind_stream_reset")
+
     def get_winds(self):
         out = [np.empty(self.N) for _ in range(4)]
         self._ck(self.lib.picles_get_winds(self.h, *[K.dptr(a) for a in out]), "picles_get_winds")
@@ -474,6 +537,31 @@ class HipModel:
         t = C.c_double()
         self._ck(self.lib.picles_diag_pop(self.h, f.ctypes.data, K.dptr(p), C.byref(t)), "picles_diag_pop")
         return f.reshape((nf, nyc, nxc)).transpose(0, 2, 1), p, t.value
+
+    def diag_export(self, fields, partials=None):
+        """the snapshot of diag_push, written into torch CUDA tensors instead of a ring slot (picles_diag_export): `fields` float32,
+        contiguous, n_fields * Nxc * nyc_loc values (the memory layout of diag_pop: [n_fields, nyc_loc, Nxc]); `partials` float64
+        [n_partials, 7] or None.  Nothing is copied to the host; torch's current stream is ordered behind the kernel"""
+        import torch
+        nxc, nyc, nf, npart, _ = self.diag_shape()
+        if not (fields.is_cuda and fields.dtype == torch.float32 and fields.is_contiguous() and fields.numel() == nf * nxc * nyc):
+            raise ValueError(f"diag_export: fields must be a contiguous float32 device tensor of {nf} x {nyc} x {nxc} values")
+        if partials is not None and not (partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()
+                                         and partials.numel() == npart * 7):
+            raise ValueError(f"diag_export: partials must be a contiguous float64 device tensor of {npart} x 7 values")
+        cur = torch.cuda.current_stream(fields.device)
+        s = cur
+        if not cur.cuda_stream:          # torch's default stream is the null stream: ordered through a side stream (wind_stream_push)
+            s = getattr(self, "_stream_side", None)
+            if s is None:
+                s = self._stream_side = torch.cuda.Stream(fields.device)
+            s.wait_stream(cur)
+        try:
+            self._ck(self.lib.picles_diag_export(self.h, fields.data_ptr(), None if partials is None else C.cast(partials.data_ptr(), K.c_double_p),
+                                                 s.cuda_stream), "picles_diag_export")
+        finally:
+            if s is not cur:
+                cur.wait_stream(s)
 
     @property
     def diag_pending(self):

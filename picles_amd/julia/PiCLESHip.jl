@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(16)
+const PICLES_ABI_VERSION = Int32(17)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -456,6 +456,49 @@ function run_fields!(model::WaveGrowth2DHIP, Δt::Float64, n_steps::Integer, sin
     end
     after_step!(model.State)
     check_dropped(model)
+    nothing
+end
+
+"""
+    wind_stream_init!(model, x, y, t0, dt; slots=3)
+    wind_stream_push!(model, k, u, v; stream=C_NULL)
+    diag_export!(model, fields, partials=C_NULL; stream=C_NULL)
+
+Coupling (`picles_wind_stream_*`, `picles_diag_export`; the contract is in include/picles_hip.h, "streamed winds"): the winds as a
+lattice over the regular axes `x`, `y` whose time levels `t0 + k dt` arrive one at a time in a ring of `slots` levels on the device,
+and the coarse diagnostics written into the caller's device buffers.  `wind_stream_push!` takes host `Matrix{Float64}` /
+`Matrix{Float32}` levels `[nx, ny]`, or device pointers (`Ptr{Float64}` / `Ptr{Float32}`, e.g. of a ROCArray) with the HIP stream
+that produces them: the library orders its copy behind that stream and the stream behind the copy.  A step whose levels are not
+held is refused by `picles_run_steps` / `picles_time_step` with a text that names the missing level.  `diag_export!` needs
+`picles_diag_init` first (`run_fields!` makes it); `fields` and `partials` are device pointers.
+"""
+function wind_stream_init!(model::WaveGrowth2DHIP, x::AbstractVector{<:Real}, y::AbstractVector{<:Real}, t0::Real, dt::Real; slots::Integer=3)
+    grid = model.grid
+    check(model.ctx, ccall((:picles_wind_stream_init, libpicles), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Int32),
+        model.ctx, length(x), length(y), x[1], x[2] - x[1], y[1], y[2] - y[1], t0, dt, grid.data.x[1, 1], grid.data.y[1, 1], slots), "picles_wind_stream_init")
+    model.winds_uploaded = true      # the device produces every window by itself: upload_winds! has nothing to do, the chunked paths apply
+    model.winds_static = true
+    nothing
+end
+
+function wind_stream_push!(model::WaveGrowth2DHIP, k::Integer, u::Matrix{T}, v::Matrix{T}) where {T<:Union{Float32,Float64}}
+    size(u) == size(v) || error("wind_stream_push!: u and v differ in shape")
+    check(model.ctx, ccall((:picles_wind_stream_push, libpicles), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}),
+        model.ctx, k, u, v, T === Float32 ? 1 : 0, 0, C_NULL), "picles_wind_stream_push")
+    nothing
+end
+
+function wind_stream_push!(model::WaveGrowth2DHIP, k::Integer, u::Ptr{T}, v::Ptr{T}; stream::Ptr{Cvoid}=C_NULL) where {T<:Union{Float32,Float64}}
+    check(model.ctx, ccall((:picles_wind_stream_push, libpicles), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}),
+        model.ctx, k, u, v, T === Float32 ? 1 : 0, 1, stream), "picles_wind_stream_push")
+    nothing
+end
+
+function diag_export!(model::WaveGrowth2DHIP, fields::Ptr{Float32}, partials::Ptr{Float64}=Ptr{Float64}(C_NULL); stream::Ptr{Cvoid}=C_NULL)
+    check(model.ctx, ccall((:picles_diag_export, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}),
+        model.ctx, fields, partials, stream), "picles_diag_export")
+    after_step!(model.State)
     nothing
 end
 

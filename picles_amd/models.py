@@ -326,11 +326,25 @@ class WaveGrowth2D:
         self.backend = factory(g, p, o, m, grid.data.mask, **(backend_kwargs or {}))
         if hasattr(grid, "metric"):     # spherical mesh: per-node projection + great-circle term
             self.backend.set_metric(*grid.metric())
+        if self._streamed() and not hasattr(self.backend, "wind_stream_init"):
+            from .coupling import REFUSAL
+            raise NotImplementedError(REFUSAL)
         self._wind_window = None
         self._state = LazyState(self.backend, (g.Nx, g.Ny, 3))
 
     # ---- winds ----
+    def _streamed(self):
+        from .coupling import StreamedWinds
+        return isinstance(self.winds, StreamedWinds)
+
+    def wind_steps_allowed(self, dt, k):
+        """run()'s hook: how many of the next k steps the winds on the device cover — all of them, except under StreamedWinds, where
+        the levels held in the ring decide (a source is asked for more first)"""
+        return self.winds.steps_allowed(dt, k) if self._streamed() else k
+
     def _is_static(self, dt):
+        if self._streamed():
+            return False
         if self._winds_static is None:
             a = sample_winds(self.winds, self.grid, 0.0)
             b = sample_winds(self.winds, self.grid, 0.37 * dt + 1.0)
@@ -346,12 +360,20 @@ class WaveGrowth2D:
         from .wind_emulator import GriddedWinds
         if isinstance(self.winds, GriddedWinds) and hasattr(self.backend, "set_wind_grid"):
             return True
+        if self._streamed():          # levels pushed into a ring on the device (picles_amd/coupling.py), sampled there like a lattice
+            return True
         return bool(self._is_static(dt) if detect else self._winds_static)
 
     def upload_winds(self, t, dt, seeding=False):
         """node-sample the wind closures for the step [t, t+dt]: three levels (t, t+dt/2, t+dt), interpolated in t by the kernel.
         `seeding`: the window is init_particles!'s, which reads its level 0 only (winds at t = 0.0, run.jl:213-215)"""
         from .wind_emulator import GriddedWinds
+        if self._streamed():
+            # the ring is made once per backend; a source is asked for the levels the window reads (seeding: those bracketing t)
+            self.winds.attach(self)
+            self.winds.ensure(t, t if seeding else t + dt)
+            self._wind_window = "device-stream"
+            return
         if isinstance(self.winds, GriddedWinds) and hasattr(self.backend, "set_wind_grid"):
             if self._wind_window != "device-lattice":      # once: the device samples every step itself
                 g = self.grid

@@ -343,6 +343,10 @@ class NestForcing(BoundaryForcing):
     # ---- before anything is seeded ----
     def check_run(self, sim, writers, store=False, cash_store=False, pickup=False):
         super().check_run(sim, writers, store=store, cash_store=cash_store, pickup=pickup)
+        from .coupling import StreamedWinds
+        if any(isinstance(getattr(mm, "winds", None), StreamedWinds) for mm in (sim.model, self.parent.model)):
+            raise NotImplementedError("NestForcing: the child or the parent runs under StreamedWinds: streamed nests are not carried "
+                                      "(a GriddedWinds lattice or static winds on both models)")
         pw = writers_of(self.parent)
         if any(w.kind == "checkpointer" for w in pw):
             raise NotImplementedError("NestForcing: a Checkpointer in the parent's output_writers: a nested pair is checkpointed through the "

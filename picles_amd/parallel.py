@@ -174,6 +174,9 @@ class SlabModel:
         from . import fetch_relations as FetchRelations
         grid, ODEsys, ODEsets = cfg_model["grid"], cfg_model["ODEsys"], cfg_model["ODEsets"]
         self.grid, self.winds = grid, cfg_model["winds"]
+        from .coupling import StreamedWinds, REFUSAL
+        if isinstance(self.winds, StreamedWinds):
+            raise NotImplementedError("SlabModel: " + REFUSAL)
         self.rank, self.world = rank, world
         self.periodic_boundary = bool(cfg_model.get("periodic_boundary", True))
         ms = cfg_model.get("minimal_state")

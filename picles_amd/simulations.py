@@ -132,7 +132,8 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
     # steps to take (run.jl:113 loops while `stop_time >= clock.time`: one step past stop_time); None without a finite stop_time
     n = 0 if not sim.running else None if sim.stop_time == float("inf") else int(math.floor((sim.stop_time - m.clock.time) / sim.Δt)) + 1
     # nothing observes State between the steps: enqueue the whole loop from C, in one call or in chunks between the writers' iterations
-    # (static winds, or a lattice the device samples: WaveGrowth2D.runs_chunked; closures that vary in time take the per-step loop)
+    # (static winds, a lattice the device samples or levels streamed into its ring: WaveGrowth2D.runs_chunked; closures that vary in
+    # time take the per-step loop)
     chunk_winds = m.runs_chunked(sim.Δt) if hasattr(m, "runs_chunked") else getattr(m, "_winds_static", False)
     chunked = not store and not cash_store and hasattr(m.backend, "run_steps") and chunk_winds and n is not None
     if chunked and n > 0:
@@ -148,6 +149,8 @@ def run(sim: Simulation, store=False, pickup=False, cash_store=False, debug=Fals
         time0, it0, done = m.clock.time, m.clock.iteration, 0
         while done < n:
             k = min([n - done] + [w.steps_allowed(m.backend, it0 + done) for w in writers])
+            if hasattr(m, "wind_steps_allowed"):
+                k = m.wind_steps_allowed(sim.Δt, k)      # streamed winds: the steps the levels held on the device cover
             m.backend.run_steps(sim.Δt, k)
             for w in phase["after_chunk"]:
                 w.after_chunk(m.backend)
