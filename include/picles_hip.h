@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 17
+#define PICLES_ABI_VERSION 18
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -619,6 +619,38 @@ int32_t picles_nest_set_levels(picles_ctx *child, double t0, const double *v0, d
  *   return; the child keeps a device copy until the next call or picles_destroy.  A forcing set or a nest of the child is not touched. */
 int32_t picles_nest_prolong(picles_ctx *child, picles_ctx *parent, const int32_t *ix0, const int32_t *ix1, const double *wx,
                             const int32_t *iy0, const int32_t *iy1, const double *wy, double dt);
+
+/* ---- a child moved across its parent (ABI 18): between two legs of a nested run the child's box is translated by
+ * (si, sj) of its own nodes — a vortex-following nest —, so that new node (i, j) lies where old node (i + si, j + sj) lay.  The child
+ * keeps the sea it has resolved where the old and the new box overlap and takes the parent's where the new box is freshly exposed. ----
+ * THE STATE, per new node (i, j), with Ncx x Ncy the child's grid and m = keep_margin (the nodes dropped along the old box's rim and
+ * band, whose State is prescribed rather than resolved):
+ *     KEPT when m <= i + si < Ncx - m and m <= j + sj < Ncy - m: the bits of the child's State at old node (i + si, j + sj), as they
+ *     stand — calm (0, 0, 0) nodes and NaN payloads included;
+ *     any other node: picles_nest_prolong's value at (i, j) for the tables given, which are those of the NEW box in the parent
+ *     (the same corners, weights, wet test, serial sums and divisions; (0, 0, 0) where no corner is wet).
+ * kx ky nodes are kept, kx = max(0, Ncx - max(m, si) - max(m, -si)) and ky likewise; |si| >= Ncx - 2m keeps none, and the call is
+ * picles_nest_prolong at the new place.  k_nest_relocate (picles_amd/csrc/k_nest.h) writes the result into MovieState, which
+ * afterwards HOLDS THE RELOCATED STATE (picles_get_movie_state reads it; the next step with PICLES_STEP_MOVIE overwrites it).
+ * THE CALL, in this order: completes the parent's pending step and the child's own, each on its own stream; orders the child's
+ * stream behind the parent's with an event; launches the kernel; orders the parent's stream behind it; moves the mesh origin of a wind
+ * lattice the child holds to (mesh_x0, mesh_y0) — the lattice is not uploaded again; without a lattice the two arguments are ignored —;
+ * resets the child as picles_seed(child, t) resets it at its clock t (a lattice child samples the two-level window [t, t + dt] at the
+ * new nodes; a child under host-set winds keeps the window it holds: upload the winds at the new nodes just before); copies the
+ * relocated State into State and remeshes it (picles_remesh(child, dt)).  It returns after enqueueing.  What the child holds afterwards
+ * is, bit for bit, what picles_seed(child, t), picles_set_state(child, <the relocated State>), picles_remesh(child, dt) leave on a
+ * child created at the new position.  Neither clock moves.
+ *   refuses (-2 / -5, both contexts as they were, picles_last_error(child) has the text): everything picles_nest_prolong refuses; a
+ *   child that was never seeded; clocks of child and parent that differ; keep_margin < 0; a child that still holds a nest, a forcing
+ *   set, a feedback or a statistics set (their nodes are index space and would go stale silently: end the leg first); a child with a
+ *   periodic axis, with a metric set (picles_set_metric), with land nodes in its mask (class 0 or 2: the mask would travel with the
+ *   box) or under a wind stream.  Probe, track and diagnostics sets sample index space and are left alone: they move with the box.
+ *   Not carried across a move: statistics accumulators, a track table's geometry, the checkpoint fingerprint of the old origin (a
+ *   blob written after a move is loaded by a context created at that leg's origin). */
+int32_t picles_nest_relocate(picles_ctx *child, picles_ctx *parent, int32_t si, int32_t sj, int32_t keep_margin,
+                             const int32_t *ix0, const int32_t *ix1, const double *wx,
+                             const int32_t *iy0, const int32_t *iy1, const double *wy,
+                             double dt, double mesh_x0, double mesh_y0);
 
 /* ---- two-way nesting: the child's sea state fed back into its parent.  A nested child (picles_nest_init) may feed back: the library
  * makes a forcing set on the PARENT — its ocean nodes under the child — whose one level is the child's State restricted onto them,

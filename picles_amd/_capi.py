@@ -103,7 +103,7 @@ WIND_HOST, WIND_DEVICE = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 17
+ABI_VERSION = 18
 SLAB_ID_BYTES = 128
 PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
 
@@ -199,6 +199,8 @@ SYMBOLS = {
     "picles_nest_set_levels": (C.c_int32, [_VP, C.c_double, c_double_p, C.c_double, c_double_p]),
     "picles_nest_free": (C.c_int32, [_VP]),
     "picles_nest_prolong": (C.c_int32, [_VP, _VP, c_int32_p, c_int32_p, c_double_p, c_int32_p, c_int32_p, c_double_p, C.c_double]),
+    "picles_nest_relocate": (C.c_int32, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_double_p, c_int32_p, c_int32_p, c_double_p,
+                                         C.c_double, C.c_double, C.c_double]),
     "picles_nest_feedback_init": (C.c_int32, [_VP, C.c_int32, c_int32_p, C.c_int32, c_int32_p, C.c_int32, c_int32_p, c_double_p]),
     "picles_nest_feedback": (C.c_int32, [_VP]),
     "picles_nest_feedback_info": (C.c_int32, [_VP, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_int64)]),

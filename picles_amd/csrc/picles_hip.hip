@@ -644,6 +644,7 @@ struct picles_ctx {
     double pend_t = 0.0, pend_dt = 0.0;
     signed char *d_mask = nullptr;
     std::vector<signed char> h_mask;
+    long long first_land = -1;          /* the first node of class 0 or 2 in h_mask (-1: an all-ocean box; picles_nest_relocate moves no other) */
     double clock = 0.0;
     /* pending step (begin_step .. scatter_remesh) */
     double step_dt = 0.0;
@@ -1022,6 +1023,7 @@ PX_EXPORT int32_t picles_create(const picles_grid *g, const picles_phys *p, cons
                 mk = ring ? 3 : 1;
             }
             c->h_mask[(long long)jl * G.Nx + i] = mk;
+            if ((mk == 0 || mk == 2) && c->first_land < 0) c->first_land = (long long)jl * G.Nx + i;
         }
     /* ocean_points (WaveGrowthModels2D.jl:256-270) and check_boundary_point (core_2D.jl:360-366) */
     bool any3 = false;
@@ -3704,9 +3706,10 @@ PX_EXPORT int32_t picles_nest_free(picles_ctx *c)
 }
 
 /* one axis of picles_nest_prolong's tables, held as stencil_check holds a stencil: indices inside [0, n_par), weights finite and in [0, 1] */
-static int prolong_axis_check(picles_ctx *c, const char *axis, int n_child, int n_par, const int32_t *i0, const int32_t *i1, const double *w)
+static int prolong_axis_check(picles_ctx *c, const char *axis, int n_child, int n_par, const int32_t *i0, const int32_t *i1, const double *w,
+                              const char *call = "picles_nest_prolong")
 {
-    const std::string who = "picles_nest_prolong: ";
+    const std::string who = std::string(call) + ": ";
     for (int k = 0; k < n_child; k++) {
         for (int v : {i0[k], i1[k]})
             if (v < 0 || v >= n_par)
@@ -3718,26 +3721,12 @@ static int prolong_axis_check(picles_ctx *c, const char *axis, int n_child, int 
     return 0;
 }
 
-PX_EXPORT int32_t picles_nest_prolong(picles_ctx *c, picles_ctx *p, const int32_t *ix0, const int32_t *ix1, const double *wx,
-                                      const int32_t *iy0, const int32_t *iy1, const double *wy, double dt)
+/* the six tables of picles_nest_prolong / picles_nest_relocate on the device, one block the child keeps: wx, wy, then ix0, ix1, iy0, iy1 */
+static int prolong_tab_upload(picles_ctx *c, const int32_t *ix0, const int32_t *ix1, const double *wx, const int32_t *iy0, const int32_t *iy1,
+                              const double *wy)
 {
-    if (!c) return -1;
-    if (!p) return fail(c, -2, "picles_nest_prolong: no parent context given");
-    if (c == p) return fail(c, -2, "picles_nest_prolong: child and parent are the same context: a child is started from another model");
-    if (c->device != p->device)
-        return fail(c, -5, "picles_nest_prolong: child on device " + std::to_string(c->device) + ", parent on device " + std::to_string(p->device) +
-                           ": create both contexts on one device");
-    if (!c->G.single_slab || c->ring || !p->G.single_slab || p->ring)
-        return fail(c, -5, "picles_nest_prolong: slabs, slab mode and the native ring do not nest: both contexts must be whole-grid contexts");
-    if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string("picles_nest_prolong") + NEST_NO_EXT_STREAMS);
-    if (!p->seeded) return fail(c, -2, "picles_nest_prolong: the parent was never seeded: it holds no sea state to start a child from");
-    if (!(dt > 0.0)) return fail(c, -2, "picles_nest_prolong: dt must be positive (the child's step: the remesh and a lattice's first window use it)");
-    if (!ix0 || !ix1 || !wx || !iy0 || !iy1 || !wy) return fail(c, -2, "picles_nest_prolong: the six tables ix0, ix1, wx, iy0, iy1, wy must be given");
     const int ncx = c->G.Nx, ncy = c->G.Ny;
-    { int rc = prolong_axis_check(c, "column", ncx, p->G.Nx, ix0, ix1, wx); if (rc) return rc; }
-    { int rc = prolong_axis_check(c, "row", ncy, p->G.Ny, iy0, iy1, wy); if (rc) return rc; }
     HIPCHK(c, hipSetDevice(c->device));
-    /* the tables, one block: wx, wy, then ix0, ix1, iy0, iy1 */
     const size_t nd = (size_t)ncx + ncy, bytes = nd * sizeof(double) + 2 * nd * sizeof(int);
     if (c->prolong_tab) HIPCHK(c, hipStreamSynchronize(c->stream));      /* the launch of an earlier call may still read them */
     if (c->prolong_cap < bytes) {
@@ -3759,6 +3748,29 @@ PX_EXPORT int32_t picles_nest_prolong(picles_ctx *c, picles_ctx *p, const int32_
         std::copy(iy1, iy1 + ncy, hi + 2 * ncx + ncy);
     }
     HIPCHK(c, hipMemcpy(c->prolong_tab, h.data(), bytes, hipMemcpyHostToDevice));       /* blocking: the caller's tables are free on return */
+    return 0;
+}
+
+PX_EXPORT int32_t picles_nest_prolong(picles_ctx *c, picles_ctx *p, const int32_t *ix0, const int32_t *ix1, const double *wx,
+                                      const int32_t *iy0, const int32_t *iy1, const double *wy, double dt)
+{
+    if (!c) return -1;
+    if (!p) return fail(c, -2, "picles_nest_prolong: no parent context given");
+    if (c == p) return fail(c, -2, "picles_nest_prolong: child and parent are the same context: a child is started from another model");
+    if (c->device != p->device)
+        return fail(c, -5, "picles_nest_prolong: child on device " + std::to_string(c->device) + ", parent on device " + std::to_string(p->device) +
+                           ": create both contexts on one device");
+    if (!c->G.single_slab || c->ring || !p->G.single_slab || p->ring)
+        return fail(c, -5, "picles_nest_prolong: slabs, slab mode and the native ring do not nest: both contexts must be whole-grid contexts");
+    if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string("picles_nest_prolong") + NEST_NO_EXT_STREAMS);
+    if (!p->seeded) return fail(c, -2, "picles_nest_prolong: the parent was never seeded: it holds no sea state to start a child from");
+    if (!(dt > 0.0)) return fail(c, -2, "picles_nest_prolong: dt must be positive (the child's step: the remesh and a lattice's first window use it)");
+    if (!ix0 || !ix1 || !wx || !iy0 || !iy1 || !wy) return fail(c, -2, "picles_nest_prolong: the six tables ix0, ix1, wx, iy0, iy1, wy must be given");
+    const int ncx = c->G.Nx, ncy = c->G.Ny;
+    { int rc = prolong_axis_check(c, "column", ncx, p->G.Nx, ix0, ix1, wx); if (rc) return rc; }
+    { int rc = prolong_axis_check(c, "row", ncy, p->G.Ny, iy0, iy1, wy); if (rc) return rc; }
+    { int rc = prolong_tab_upload(c, ix0, ix1, wx, iy0, iy1, wy); if (rc) return rc; }
+    const size_t nd = (size_t)ncx + ncy;
     {   /* the parent's State at its clock, whole: its pending step completed on its own stream */
         const std::string keep = p->err;
         int rc = flush(p);
@@ -3776,6 +3788,81 @@ PX_EXPORT int32_t picles_nest_prolong(picles_ctx *c, picles_ctx *p, const int32_
     /* the parent's next step overwrites the State this kernel reads: its stream goes on behind it */
     HIPCHK(c, hipEventRecord(c->ev_ctx, c->stream));
     HIPCHK(c, hipStreamWaitEvent(p->stream, c->ev_ctx, 0));
+    c->state_zero = false;
+    return picles_remesh(c, dt);
+}
+
+/* a child moved across its parent (include/picles_hip.h) */
+PX_EXPORT int32_t picles_nest_relocate(picles_ctx *c, picles_ctx *p, int32_t si, int32_t sj, int32_t keep_margin, const int32_t *ix0,
+                                       const int32_t *ix1, const double *wx, const int32_t *iy0, const int32_t *iy1, const double *wy, double dt,
+                                       double mesh_x0, double mesh_y0)
+{
+    if (!c) return -1;
+    const char *const who = "picles_nest_relocate";
+    const std::string W = std::string(who) + ": ";
+    if (!p) return fail(c, -2, W + "no parent context given");
+    if (c == p) return fail(c, -2, W + "child and parent are the same context: a child is moved across another model");
+    if (c->device != p->device)
+        return fail(c, -5, W + "child on device " + std::to_string(c->device) + ", parent on device " + std::to_string(p->device) +
+                           ": create both contexts on one device");
+    if (!c->G.single_slab || c->ring || !p->G.single_slab || p->ring)
+        return fail(c, -5, W + "slabs, slab mode and the native ring do not nest: both contexts must be whole-grid contexts");
+    if (c->ext_streams || p->ext_streams) return fail(c, -5, std::string(who) + NEST_NO_EXT_STREAMS);
+    if (!p->seeded) return fail(c, -2, W + "the parent was never seeded: it holds no sea state to expose a child to");
+    if (!c->seeded) return fail(c, -2, W + "the child was never seeded: it holds no sea state to keep (picles_nest_prolong starts a child)");
+    if (!(dt > 0.0)) return fail(c, -2, W + "dt must be positive (the child's step: the remesh and a lattice's first window use it)");
+    if (keep_margin < 0) return fail(c, -2, W + "keep_margin must be >= 0 (the nodes dropped along the old box's rim)");
+    if (c->clock != p->clock) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "picles_nest_relocate: the child's clock (%.17g) and the parent's (%.17g) differ: a box moves between two legs, on a common clock",
+                 c->clock, p->clock);
+        return fail(c, -2, buf);
+    }
+    if (c->nest || c->bf_n || c->fb || c->stat_on)
+        return fail(c, -5, W + "the child still holds a " + (c->fb ? "feedback" : c->nest ? "nest" : c->bf_n ? "forcing set" : "statistics set") +
+                           ": its nodes would keep their indices and lose their places (end the leg first: picles_nest_free, picles_bforce_free, "
+                           "picles_stat_free)");
+    if (c->G.periodic_x || c->G.periodic_y || c->G.tripolar) return fail(c, -5, W + "the child has a periodic axis: only an open box moves");
+    if (c->A.m11) return fail(c, -5, W + "the child has a metric set (picles_set_metric): its planes belong to the old position");
+    if (c->wind.streamed()) return fail(c, -5, W + "the child runs under a wind stream: its ring holds levels sampled for the old position's lattice window");
+    if (c->first_land >= 0)
+        return fail(c, -5, W + "the child's mask has land nodes (node " + std::to_string(c->first_land) + " is of class " +
+                           std::to_string((int)c->h_mask[(size_t)c->first_land]) + "): the mask is index space and would travel with the box");
+    if (!ix0 || !ix1 || !wx || !iy0 || !iy1 || !wy) return fail(c, -2, W + "the six tables ix0, ix1, wx, iy0, iy1, wy must be given");
+    const int ncx = c->G.Nx, ncy = c->G.Ny;
+    { int rc = prolong_axis_check(c, "column", ncx, p->G.Nx, ix0, ix1, wx, who); if (rc) return rc; }
+    { int rc = prolong_axis_check(c, "row", ncy, p->G.Ny, iy0, iy1, wy, who); if (rc) return rc; }
+    { int rc = prolong_tab_upload(c, ix0, ix1, wx, iy0, iy1, wy); if (rc) return rc; }
+    const size_t nd = (size_t)ncx + ncy;
+    {   /* both States at the common clock, whole: the pending steps completed, each on its own stream */
+        const std::string keep = p->err;
+        int rc = flush(p);
+        if (rc) { const std::string why = p->err; p->err = keep; return fail(c, rc, W + "the parent's pending step: " + why); }
+        if ((rc = flush(c))) return rc;
+    }
+    HIPCHK(c, hipEventRecord(p->ev_ctx, p->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, p->ev_ctx, 0));
+    const double *dwx = c->prolong_tab, *dwy = dwx + ncx;
+    const int *dix0 = (const int *)(c->prolong_tab + nd), *dix1 = dix0 + ncx, *diy0 = dix1 + ncx, *diy1 = diy0 + ncy;
+    /* into MovieState: an in-place shift races with itself, and the seed below writes State */
+    hipLaunchKernelGGL(k_nest_relocate, dim3(nblocks(c->A.n, NEST_BLOCK)), dim3(NEST_BLOCK), 0, c->stream, ncx, ncy, (int)si, (int)sj, (int)keep_margin,
+                       p->G.Nx, p->A.n, dix0, dix1, dwx, diy0, diy1, dwy, (const double *)p->A.state, (const double *)c->A.state, c->A.movie);
+    HIPCHK(c, hipGetLastError());
+    /* the parent's next step overwrites the State this kernel reads: its stream goes on behind it */
+    HIPCHK(c, hipEventRecord(c->ev_ctx, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(p->stream, c->ev_ctx, 0));
+    if (c->wind.from_lattice()) {      /* the lattice stays where it is in the common frame: the mesh moves under it */
+        c->wind.wg.mesh_x0 = mesh_x0;
+        c->wind.wg.mesh_y0 = mesh_y0;
+        c->wind.invalidate();
+    }
+    /* what picles_seed resets, at the common clock and under the wind at the new nodes; then the relocated State and its particles */
+    { int rc = seed_at(c, c->clock, c->clock, dt); if (rc) return rc; }
+    /* no step of the box at its new place has been taken: a restart blob reads as that of a context seeded there (nothing reads
+     * either before the next step sets them) */
+    c->step_dt = 0.0;
+    c->step_flags = 0;
+    HIPCHK(c, hipMemcpyAsync(c->A.state, c->A.movie, 3 * (size_t)c->A.n * 8, hipMemcpyDeviceToDevice, c->stream));
     c->state_zero = false;
     return picles_remesh(c, dt);
 }

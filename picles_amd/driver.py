@@ -809,23 +809,43 @@ class HipModel:
         self._feedback_goes()
         self._ck(self.lib.picles_nest_free(self.h), "picles_nest_free")
 
+    def _prolong_tables(self, who, ix0, ix1, wx, iy0, iy1, wy):
+        """the six per-axis tables of nest_prolong / nest_relocate, shapes checked, as the library takes them: (a0, a1, wx, b0, b1, wy)"""
+        ints = [np.ascontiguousarray(a, dtype=np.int64) for a in (ix0, ix1, iy0, iy1)]
+        w = [np.ascontiguousarray(a, dtype=np.float64) for a in (wx, wy)]
+        for a, b, n, axis in ((ints[0], ints[1], self.Nx, "x"), (ints[2], ints[3], self.ny_loc, "y")):
+            if not (a.shape == b.shape == (n,)):
+                raise ValueError(f"{who}: the {axis} index tables must hold {n} entries each, got {a.shape} and {b.shape}")
+        if w[0].shape != (self.Nx,) or w[1].shape != (self.ny_loc,):
+            raise ValueError(f"{who}: the weight tables must hold {self.Nx} and {self.ny_loc} entries, got {w[0].shape} and {w[1].shape}")
+        a0, a1, b0, b1 = (_int32_planes(a.reshape(-1, 1), who).reshape(-1) for a in ints)
+        return a0, a1, w[0], b0, b1, w[1]
+
     def nest_prolong(self, parent, ix0, ix1, wx, iy0, iy1, wy, dt):
         """this model started from `parent` (a HipModel) at the parent's clock: the parent's State prolonged onto every node of this
         model, and the particles the remesh makes of it with step `dt` (picles_nest_prolong; nesting.prolong_tables gives the six
         per-axis tables: 0-based parent columns / rows and weights in [0, 1] per child column / row)"""
         ph = getattr(parent, "h", parent)
-        ints = [np.ascontiguousarray(a, dtype=np.int64) for a in (ix0, ix1, iy0, iy1)]
-        w = [np.ascontiguousarray(a, dtype=np.float64) for a in (wx, wy)]
-        for a, b, n, axis in ((ints[0], ints[1], self.Nx, "x"), (ints[2], ints[3], self.ny_loc, "y")):
-            if not (a.shape == b.shape == (n,)):
-                raise ValueError(f"nest_prolong: the {axis} index tables must hold {n} entries each, got {a.shape} and {b.shape}")
-        if w[0].shape != (self.Nx,) or w[1].shape != (self.ny_loc,):
-            raise ValueError(f"nest_prolong: the weight tables must hold {self.Nx} and {self.ny_loc} entries, got {w[0].shape} and {w[1].shape}")
-        a0, a1, b0, b1 = (_int32_planes(a.reshape(-1, 1), "nest_prolong").reshape(-1) for a in ints)
+        a0, a1, fx, b0, b1, fy = self._prolong_tables("nest_prolong", ix0, ix1, wx, iy0, iy1, wy)
         # (State is replaced too: the model layer resets its lazy view after the start — nesting.start_from_parent — as after a step)
         self.gen += 1
-        self._ck(self.lib.picles_nest_prolong(self.h, ph, _p32(a0), _p32(a1), K.dptr(w[0]), _p32(b0), _p32(b1), K.dptr(w[1]), float(dt)),
+        self._ck(self.lib.picles_nest_prolong(self.h, ph, _p32(a0), _p32(a1), K.dptr(fx), _p32(b0), _p32(b1), K.dptr(fy), float(dt)),
                  "picles_nest_prolong")
+
+    def nest_relocate(self, parent, si, sj, keep_margin, ix0, ix1, wx, iy0, iy1, wy, dt, mesh_x0=0.0, mesh_y0=0.0):
+        """this model's box moved by (si, sj) of its own nodes across `parent` (a HipModel), between two legs of a nested run: new
+        node (i, j) keeps the State of old node (i + si, j + sj) where that lies `keep_margin` nodes inside the old box and takes the
+        parent's prolonged State elsewhere; the particles are remade with step `dt` (picles_nest_relocate; nesting.relocate_state is
+        the definition).  The tables are nesting.prolong_tables(parent_grid, NEW child grid); (mesh_x0, mesh_y0): the new
+        coordinates of node (0, 0), for a wind lattice this model holds.  Static winds are uploaded at the new nodes before the call"""
+        ph = getattr(parent, "h", parent)
+        for v, name in ((si, "si"), (sj, "sj"), (keep_margin, "keep_margin")):
+            if not (isinstance(v, (int, np.integer)) and -2 ** 31 <= int(v) < 2 ** 31):
+                raise ValueError(f"nest_relocate: {name} must be an integer of 32 bits, not {v!r}")
+        a0, a1, fx, b0, b1, fy = self._prolong_tables("nest_relocate", ix0, ix1, wx, iy0, iy1, wy)
+        self.gen += 1
+        self._ck(self.lib.picles_nest_relocate(self.h, ph, int(si), int(sj), int(keep_margin), _p32(a0), _p32(a1), K.dptr(fx), _p32(b0), _p32(b1),
+                                               K.dptr(fy), float(dt), float(mesh_x0), float(mesh_y0)), "picles_nest_relocate")
 
     # ---- two-way nesting (picles_nest_feedback_*: this nested model's State restricted onto ocean nodes of its parent, on the device) ----
     def nest_feedback_init(self, fb_nodes, src_nodes, index, weights):

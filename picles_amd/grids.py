@@ -130,6 +130,25 @@ class TwoDCartesianGridMesh:
         return np.array([[1 / self.stats.dx, 0.0], [0.0, 1 / self.stats.dy]])
 
 
+def translated(grid: TwoDCartesianGridMesh, si: int, sj: int) -> TwoDCartesianGridMesh:
+    """the open, all-ocean Cartesian mesh `grid` moved by (si, sj) of its own nodes: a mesh constructed at the shifted extents
+    (xmin + si dx, xmin + si dx + dx (Nx - 1), Nx, ...), so that its coordinates are those of a grid built there directly
+    (nesting.move_child: a child box that follows a storm).  A mask with land is index space and would travel with the box: refused"""
+    if not isinstance(grid, TwoDCartesianGridMesh):
+        raise NotImplementedError("translated: only a TwoDCartesianGridMesh moves")
+    for v in (si, sj):
+        if not isinstance(v, (int, np.integer)):
+            raise ValueError(f"translated: the shift is whole nodes, not {v!r}")
+    st = grid.stats
+    Nx, Ny = int(st.Nx), int(st.Ny)
+    if not (isinstance(st.Nx, N_NonPeriodic) and isinstance(st.Ny, N_NonPeriodic)):
+        raise NotImplementedError("translated: a mesh with a periodic axis does not move")
+    if np.isin(np.asarray(grid.data.mask), (LAND, LAND_BOUNDARY)).any():
+        raise NotImplementedError("translated: the mesh has land nodes; the mask is index space and would travel with the box")
+    xmin, ymin = st.xmin + int(si) * st.dx, st.ymin + int(sj) * st.dy
+    return TwoDCartesianGridMesh(xmin, xmin + st.dx * (Nx - 1), Nx, ymin, ymin + st.dy * (Ny - 1), Ny, periodic_boundary=(False, False))
+
+
 # ---------------------------------------------------------------------------------------------
 # Spherical (lon/lat) mesh — reference: src/Grids/SphericalGrid.jl, spherical_grid_corrections.jl
 # ---------------------------------------------------------------------------------------------

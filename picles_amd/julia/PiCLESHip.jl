@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(17)
+const PICLES_ABI_VERSION = Int32(18)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -713,6 +713,25 @@ function nest_prolong!(child::WaveGrowth2DHIP, parent::WaveGrowth2DHIP, ix0, ix1
     a0, a1, b0, b1 = (Vector{Int32}(v .- 1) for v in (ix0, ix1, iy0, iy1))
     fx, fy = Vector{Float64}(wx), Vector{Float64}(wy)
     check(child.ctx, ccall((:picles_nest_prolong, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Float64), child.ctx, parent.ctx, a0, a1, fx, b0, b1, fy, Float64(dt)), "picles_nest_prolong")
+    nothing
+end
+
+"""
+    nest_relocate!(child, parent, si, sj, keep_margin, ix0, ix1, wx, iy0, iy1, wy, dt; mesh_x0 = 0.0, mesh_y0 = 0.0)
+
+A child moved across its parent between two legs of a nested run (`picles_nest_relocate`, ABI 18; the contract is in
+include/picles_hip.h): the box is translated by `(si, sj)` child nodes; new node `(i, j)` keeps the State of old node `(i + si, j + sj)`
+where that lies at least `keep_margin` nodes inside the old box, and takes the parent's prolonged State elsewhere.  The tables are
+`nest_prolong!`'s, for the NEW box (1-based).  `mesh_x0`, `mesh_y0`: the new coordinates of node (1, 1), for a wind lattice the child
+holds (ignored without one).  The child is reset as `picles_seed(child, t)` resets it and remeshed with step `dt`; MovieState then holds
+the relocated State.  Refused for a child that still holds a nest, a forcing set, a feedback or a statistics set, that has land, a
+periodic axis, a metric or a wind stream, and for unequal clocks.  Returns after enqueueing.
+"""
+function nest_relocate!(child::WaveGrowth2DHIP, parent::WaveGrowth2DHIP, si::Integer, sj::Integer, keep_margin::Integer, ix0, ix1, wx, iy0, iy1, wy, dt::Real;
+                        mesh_x0::Real = 0.0, mesh_y0::Real = 0.0)
+    a0, a1, b0, b1 = (Vector{Int32}(v .- 1) for v in (ix0, ix1, iy0, iy1))
+    fx, fy = Vector{Float64}(wx), Vector{Float64}(wy)
+    check(child.ctx, ccall((:picles_nest_relocate, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Float64, Float64, Float64), child.ctx, parent.ctx, Int32(si), Int32(sj), Int32(keep_margin), a0, a1, fx, b0, b1, fy, Float64(dt), Float64(mesh_x0), Float64(mesh_y0)), "picles_nest_relocate")
     nothing
 end
 

@@ -47,6 +47,13 @@ switches the child on when the storm nears: the parent's State at its clock t is
 device (`prolong_state` is the definition, picles_nest_prolong the call, k_nest_prolong in picles_amd/csrc/k_nest.h the kernel),
 the child's particles are remeshed from it under the child's wind at t, and both clocks read t: `run(child_sim)` with a
 NestForcing then proceeds as from a common cold start.
+
+A CHILD THAT FOLLOWS THE STORM (`move_child`, `run_following`).  Between two legs of `run(child_sim)` the child's box is
+translated by whole child nodes (`grids.translated`): where the old and the new box overlap the child keeps the sea it resolved, the
+freshly exposed nodes take the parent's State prolonged (`relocate_state` is the definition, picles_nest_relocate the call,
+k_nest_relocate the kernel), and the particles are remade under the wind at the new nodes.  `run_following` runs legs under a fresh
+NestForcing each and moves the box behind every leg so that its centre follows a track.  An open Cartesian box without land, under
+static winds or a device-sampled lattice; restart of `run_following` itself is not carried.
 """
 from __future__ import annotations
 
@@ -247,6 +254,172 @@ def start_from_parent(child_sim, parent_sim):
     cm.clock.time, cm.clock.iteration = t, 0
     child_sim.initialized = True
     child_sim.running = False
+
+
+def _whole_shift(shift, keep_margin, who):
+    si, sj = shift
+    for v in (si, sj):
+        if not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{who}: the shift is whole child nodes (si, sj), not {shift!r}")
+    if not (isinstance(keep_margin, (int, np.integer)) and keep_margin >= 0):
+        raise ValueError(f"{who}: keep_margin must be an integer >= 0, not {keep_margin!r}")
+    return int(si), int(sj), int(keep_margin)
+
+
+def kept_box(shape, shift, keep_margin):
+    """the new nodes that keep the child's own State under a move by `shift` = (si, sj): (i0, i1, j0, j1), the half-open ranges of
+    new i and j with keep_margin <= i + si < Ncx - keep_margin and likewise in j (empty ranges have i1 == i0): kx ky nodes,
+    kx = max(0, Ncx - max(m, si) - max(m, -si))"""
+    (ncx, ncy), (si, sj), m = shape, shift, keep_margin
+    i0, j0 = max(0, m - si), max(0, m - sj)
+    return i0, max(i0, min(ncx, ncx - m - si)), j0, max(j0, min(ncy, ncy - m - sj))
+
+
+def relocate_state(S_child, S_parent, parent_grid, new_child_grid, shift, keep_margin):
+    """k_nest_relocate in NumPy, bit for bit: the State of a child whose box has been translated by `shift` = (si, sj) of its own
+    nodes, so that new node (i, j) lies where old node (i + si, j + sj) lay.  S_child float64 [Ncx, Ncy, 3] is the child's State
+    before the move, `new_child_grid` the translated grid (`grids.translated`).  Where keep_margin <= i + si < Ncx - keep_margin and
+    keep_margin <= j + sj < Ncy - keep_margin the new node takes the bits of S_child[i + si, j + sj] as they stand, calm (0, 0, 0)
+    nodes and NaN payloads included; any other node takes `prolong_state(S_parent, parent_grid, new_child_grid)[i, j]`.
+    keep_margin drops the old box's rim and band, whose State is prescribed rather than resolved"""
+    si, sj, m = _whole_shift(shift, keep_margin, "relocate_state")
+    Sc = np.ascontiguousarray(S_child, dtype=np.float64)
+    out = prolong_state(S_parent, parent_grid, new_child_grid)
+    if Sc.shape != out.shape:
+        raise ValueError(f"relocate_state: the child's State is {Sc.shape}, the new grid's {out.shape}: a move keeps the box's shape")
+    i0, i1, j0, j1 = kept_box(Sc.shape[:2], (si, sj), m)
+    if i1 > i0 and j1 > j0:
+        out.view(np.uint64)[i0:i1, j0:j1] = Sc.view(np.uint64)[i0 + si:i1 + si, j0 + sj:j1 + sj]
+    return out
+
+
+def move_child(child_sim, parent_sim, shift, keep_margin=None):
+    """A child box moved across its parent, between two legs of `run(child_sim)` (a vortex-following nest): the box
+    is translated by `shift` = (si, sj) whole child nodes.  Where the old and the new box overlap, `keep_margin` nodes inside the old
+    one, the child keeps the sea it resolved; the freshly exposed nodes take the parent's State prolonged (`relocate_state` is the
+    definition, picles_nest_relocate the call, k_nest_relocate in picles_amd/csrc/k_nest.h the kernel: nothing crosses PCIe).  The
+    particles are remade from that State under the child's wind at the new nodes with fresh controller memory.  Afterwards
+    `child.grid` is the translated grid (`grids.translated`); clock time and iteration are kept.
+    keep_margin: default the `width` of the NestForcing still in child_sim.output_writers, at least 1.
+    The leg before must have ended (NestForcing.finish frees the link), both clocks must agree, and the child is an open Cartesian
+    box without land under static winds or a lattice the device samples.  A new box that leaves the parent is prolong_tables'
+    ValueError; like every refusal here it comes before anything is touched.
+    A NestForcing holds geometry from its constructor: THE NEXT LEG TAKES A NEW ONE, built after the move.  Writers that carry node
+    coordinates (FieldWriter and its kin) keep those of their construction: point them at a per-leg path.  Not carried across a
+    move: statistics accumulators, a track table, StreamedWinds, a checkpoint's origin."""
+    from .grids import TwoDCartesianGridMesh, translated
+    cm, pm = child_sim.model, parent_sim.model
+    if type(cm).__name__ == "SlabModel" or type(pm).__name__ == "SlabModel":
+        raise NotImplementedError("move_child: slabs do not nest: use whole-grid models")
+    if cm is pm:
+        raise ValueError("move_child: the parent must be another model")
+    if not parent_sim.initialized or not child_sim.initialized:
+        raise ValueError("move_child: both models must have been run: a box moves between two legs of a nested run")
+    if keep_margin is None:
+        f = getattr(child_sim, "output_writers", {}).get("boundary_forcing")
+        keep_margin = max(1, int(getattr(f, "width", 1)))
+    si, sj, m = _whole_shift(shift, keep_margin, "move_child")
+    from .coupling import StreamedWinds
+    if isinstance(getattr(cm, "winds", None), StreamedWinds):
+        raise NotImplementedError("move_child: the child runs under StreamedWinds: a streamed child does not move")
+    if not cm.runs_chunked(child_sim.Δt, detect=True):
+        raise NotImplementedError(f"move_child: the child's wind closures vary in time: {WINDS_REFUSAL}")
+    if not isinstance(cm.grid, TwoDCartesianGridMesh):
+        raise NotImplementedError("move_child: only a child on a Cartesian grid moves (no spherical child)")
+    if float(cm.clock.time) != float(pm.clock.time):
+        raise ValueError(f"move_child: the child's clock ({cm.clock.time!r}) and the parent's ({pm.clock.time!r}) differ: a box moves "
+                         "between two legs, on a common clock")
+    new_grid = translated(cm.grid, si, sj)                 # land or a periodic axis: NotImplementedError, nothing touched
+    tables = prolong_tables(pm.grid, new_grid)             # a node of the new box outside the parent: ValueError, nothing touched
+    if not hasattr(cm.backend, "nest_relocate"):
+        raise NotImplementedError("move_child needs a backend with nest_relocate (the HIP library, ABI 18)")
+    t, dt = float(cm.clock.time), float(child_sim.Δt)
+    old_grid = cm.grid
+    lattice = cm._wind_window == "device-lattice"
+    cm.grid = new_grid
+    try:
+        if not lattice:
+            cm._wind_window = None
+            cm.upload_winds(t, dt, seeding=True)           # static: the level at the new nodes; a lattice stays on the device
+        cm.backend.nest_relocate(pm.backend, si, sj, m, *tables, dt, float(new_grid.data.x[0, 0]), float(new_grid.data.y[0, 0]))
+    except BaseException:
+        cm.grid = old_grid
+        if not lattice:
+            cm._wind_window = None
+            cm.upload_winds(t, dt, seeding=True)           # the winds of the old nodes again
+        raise
+    st = getattr(cm, "_state", None)
+    if st is not None:
+        st.after_step()                  # the device field was replaced: no host mirror, no recorded write survives the move
+    child_sim.running = False
+
+
+def _box_shift(child_grid, parent_grid, target, snap):
+    """the whole-node shift (si, sj) that brings the centre of the child's box closest to `target` = (x, y): rounded to whole child
+    nodes, or (snap="parent") to whole parent cells; clamped on every non-periodic parent axis so that all child nodes stay inside"""
+    out = []
+    cs, ps = child_grid.stats, parent_grid.stats
+    for c, lo, hi, d, D, N, plo, phi, what in ((target[0], cs.xmin, cs.xmax, cs.dx, ps.dx, ps.Nx, ps.xmin, ps.xmax, "x"),
+                                               (target[1], cs.ymin, cs.ymax, cs.dy, ps.dy, ps.Ny, ps.ymin, ps.ymax, "y")):
+        unit = 1
+        if snap == "parent":
+            unit = int(round(D / d))
+            if unit < 1 or abs(unit * d - D) > 1e-9 * D:
+                raise ValueError(f"run_following: snap='parent' needs a parent spacing that is a whole multiple of the child's; in {what} "
+                                 f"they are {D!r} and {d!r}")
+        s = int(round((float(c) - 0.5 * (lo + hi)) / (unit * d))) * unit
+        if _kind(N) == "open":
+            smin = -int(math.floor((lo - plo) / d + 1e-9))           # the shifts that keep [lo, hi] inside [plo, phi]
+            smax = int(math.floor((phi - hi) / d + 1e-9))
+            smin, smax = -((-smin) // unit) * unit, (smax // unit) * unit
+            s = min(max(s, smin), smax)
+        out.append(s)
+    return tuple(out)
+
+
+def run_following(child_sim, parent_sim, centre, *, stop_time, nest, every=1, snap="child", keep_margin=None, on_leg=None):
+    """A nested run whose child box follows `centre(t) -> (x, y)` — a storm's wind maximum, a best-track position — across the
+    parent.  The run is a sequence of LEGS of `every` parent steps: each leg is `run(child_sim)` under a fresh
+    `NestForcing(child_model, parent=parent_sim, **nest)` (`nest` names at least `ratio` and `side` or `nodes`; `feedback=True` with
+    snap="parent" keeps an aligned two-way child aligned), with `child_sim.stop_time` set so that run() takes `every * ratio` child
+    steps; legs are run until the child's clock has reached `stop_time` (whole legs: the last one may end behind it).  After a leg,
+    at the common clock t, the box centre goes to `centre(t)` rounded to whole child nodes (snap="child") or whole parent cells
+    (snap="parent"), clamped on a non-periodic parent axis so that every child node stays inside the parent (a periodic axis does
+    not wrap a box: leaving the period is move_child's ValueError); a zero shift calls nothing, any other `move_child`.
+    keep_margin: move_child's, default max(1, nest["width"]).
+    on_leg(k, child_sim) runs in front of leg k = 0, 1, ...: point FieldWriter and similar writers of either model at a per-leg path
+    there — their files carry the coordinates of their construction, and every leg begins them anew.
+    Returns [(t, x0, y0), ...]: the box origin (node (0, 0)) at the start and behind every leg.
+    The child must be started (`start_from_parent`, or a common cold start: both clocks equal).  RESTART inside run_following is
+    not carried: a Checkpointer in a leg writes pair checkpoints as in any nested run, and a checkpoint is picked up by a program
+    that builds the child at THAT LEG's origin and runs on from there — the link side-car's geometry hash refuses any other origin."""
+    from .simulations import run
+    if snap not in ("child", "parent"):
+        raise ValueError(f"run_following: snap must be 'child' or 'parent', not {snap!r}")
+    if not (isinstance(every, (int, np.integer)) and every >= 1):
+        raise ValueError(f"run_following: every must be an integer >= 1, not {every!r}")
+    if "ratio" not in nest:
+        raise ValueError("run_following: nest=dict(ratio=r, side=... | nodes=..., ...) must name the ratio")
+    cm, pm = child_sim.model, parent_sim.model
+    ratio = _whole(nest["ratio"])
+    m = max(1, int(nest.get("width", 1))) if keep_margin is None else keep_margin
+    dt = float(child_sim.Δt)
+    n = int(every) * ratio
+    origin = lambda: (float(cm.clock.time), float(cm.grid.data.x[0, 0]), float(cm.grid.data.y[0, 0]))
+    boxes = [origin()]
+    k = 0
+    while cm.clock.time < stop_time - 1e-9 * dt:
+        if on_leg is not None:
+            on_leg(k, child_sim)
+        child_sim.output_writers["boundary_forcing"] = NestForcing(cm, parent=parent_sim, **nest)
+        child_sim.stop_time = float(cm.clock.time) + (n - 0.5) * dt          # run() steps while stop_time >= clock.time: n steps
+        run(child_sim)
+        shift = _box_shift(cm.grid, pm.grid, centre(float(cm.clock.time)), snap)
+        if shift != (0, 0):
+            move_child(child_sim, parent_sim, shift, keep_margin=m)
+        boxes.append(origin())
+        k += 1
+    return boxes
 
 
 def default_feedback_margin(width, dx_child, dx_parent):
