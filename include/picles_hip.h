@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 18
+#define PICLES_ABI_VERSION 19
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -351,6 +351,82 @@ int32_t picles_diag_pending(const picles_ctx *ctx);
  * layout of pop.  No ring slot, no copy to the host; an event recorded behind the kernel is waited for by caller_stream (NULL: the
  * caller orders itself, e.g. picles_sync).  The same bits as push + pop.  Refuses: not initialised, fields_dev NULL */
 int32_t picles_diag_export(picles_ctx *ctx, void *fields_dev, double *partials_dev, void *caller_stream);
+
+/* ---- coupling fluxes: wind input, dissipation, wave-supported stress and Stokes drift planes (ABI 19) ------------------------
+ * What the partner models of a coupled system consume.  The atmosphere: the momentum the waves take out of the wind (the
+ * wave-supported stress, WAVEWATCH III's taw).  The ocean: the momentum and energy the breaking waves hand down (two, phioc) and the
+ * surface Stokes drift (uss).  The model evaluates the terms behind them at every Runge-Kutta stage — Ĩ = C_e α² H_β, the wind
+ * input, and D̃ = eⁿ (k_p/e_T)²ⁿ, the dissipation (particle_waves_v5.jl:317-335) — and fuses them into d ln e/dt; here they are
+ * formed apart, once, from State and the wind at the clock, coarsened and reduced on the device like the diagnostics above.
+ * The set is NOT part of the PICLES_DIAG_* mask, and no part of the checkpoint blob.  It only reads: a push or export leaves State,
+ * particles, counters and the restart blob as a flush alone would.  Works on slabs, spheres and nests.
+ *
+ * THE NODE (picles_amd/csrc/k_flux.h states the arithmetic operation by operation; the tests build that header for the host).
+ * A node is ACTIVE when e, m_x, m_y are finite, e >= minimal_state[0] and m_x m_x + m_y m_y >= minimal_state[1] (NodeToParticle!'s
+ * branch A).  It becomes a particle (ln e, c̄ = m e / (2 |m|²)), and under the wind (u, v) the general form of the right-hand side
+ * gives ω_p, k_p (with their speed floors), Ĩ (α <= 500; 0 for a vanishing wind), D̃ (n = 2 and general n) and ω_p r_g S_cg, with the
+ * physics switches honoured: a switched-off term is an exact +0.0.  With d = c̄ / |c̄|, nine values per node:
+ *     phi_in    = e ω_p Ĩ               energy (variance) input from the wind [m² s⁻¹]
+ *     phi_dis   = e ω_p D̃               dissipation
+ *     phi_shift = e ω_p r_g S_cg        the peak-downshift term of the energy equation
+ *     tq_in     = ω_p phi_in d          momentum from air to waves (x, y)      (deep water: c_p = g/ω_p, τ = ρ_w g φ / c_p = ρ_w ω_p φ)
+ *     tq_dis    = ω_p phi_dis d         momentum from waves to ocean (x, y)
+ *     us        = 2 e ω_p k_p d         surface Stokes drift of the peak wave [m s⁻¹] (x, y)
+ * phi_in - phi_dis + phi_shift = e d(ln e)/dt of the right-hand side, to rounding.  An active node one of whose nine values is not
+ * finite is BAD.  A node that is not active, or bad, contributes zero to everything; bad nodes are counted apart.
+ *
+ * PLANES.  Coarse cells, tiles and layout are those of picles_diag_* (cx, cy in 1 ... 16, global cells, j_begin % cy == 0, planes of
+ * Nxc x nyc_loc float32, column-major [I + Nxc J], selected planes in ascending bit order).  A cell's value is the AREA mean: the sum
+ * over its active nodes in the order j outer, i inner from +0.0, divided by the number of nodes the cell covers (cx cy, fewer in a
+ * ragged last cell) — land and calm nodes count as zero; the partner model applies its own sea fraction — then multiplied by the
+ * set's scale as the last fp64 operation (scale_phi for the three phi planes, scale_tau for the four tq planes, 1 for us) and
+ * rounded to float32, nearest even.  A cell without an active node holds +0.0, never a NaN (a node's non-finite values do not reach
+ * a sum: the node is BAD; a finite mean beyond the float32 range rounds to ±inf).  scale_phi = ρ_w g gives W m⁻², scale_tau = ρ_w N m⁻².
+ * PARTIALS.  Eleven doubles per tile: the nine UNSCALED sums of the tile's cells (before the division), n_active, n_bad, each reduced
+ * by the tree of the diagnostics' sums; the host combines them in ascending (J, T) order from +0.0, over slabs in rank order.
+ *
+ * THE WIND AT THE CLOCK.  The kernel reads a level plane the wind window holds at the clock; nothing is interpolated.  A static
+ * window: its level.  A clock equal to the window's start: level 0.  A clock equal to the window's end — the time the (u1, v1)
+ * planes hold, which is where every model step leaves the clock; for a knot or polyline window its end level — those planes as they
+ * stand.  Under host-set levels (picles_set_winds*) any other clock is refused (-2) with a text that names the remedy — step to a
+ * level, or set the window — before anything is launched: a pending fused step stays pending.  A lattice or streamed context
+ * (picles_set_wind_grid, picles_wind_stream_*) reads the planes its last step or seed sampled where they hold the clock's level, and
+ * otherwise — a clock between levels; after picles_set_wind_grid*, picles_nest_relocate, picles_checkpoint_load — samples the level at
+ * the clock with the sampler of its windows (a function of the time alone) into a spare pair of planes, made on first use; a wind
+ * stream that does not hold the level(s) bracketing the clock refuses (-2, naming the level to push).
+ *
+ *   init:    refuses (-2, context unchanged) factors outside 1..16, an empty or unknown mask, scales that are not finite and positive,
+ *            n_slots < 1, a second init, a slab with j_begin % cy != 0
+ *   shape:   coarse shape, number of selected planes and partials, bytes of the field block (4 Nxc nyc_loc n_fields); no device work
+ *   push:    completes a pending fused step as picles_diag_push does, launches the kernel on the context stream into the slot's device
+ *            buffer and starts the asynchronous copy into pinned host memory on the store stream (the ring of §15 that snapshots,
+ *            diagnostics and probes share).  Refuses: not initialised, ring full (-3), the wind rule
+ *   pop:     waits for the OLDEST snapshot: fields (bytes of picles_flux_shape), partials (n_partials * 11 doubles, may be NULL), its
+ *            model time (may be NULL).  Refuses: none pending (-3)
+ *   pending: snapshots pushed and not yet popped
+ *   export:  what push does up to the kernel launch, with the kernel writing into the CALLER's device buffers (fields_dev; partials_dev
+ *            may be NULL), the layout of pop; an event recorded behind the kernel is waited for by caller_stream (NULL: the caller
+ *            orders itself).  The same bits as push + pop.  Refuses: not initialised, fields_dev NULL, the wind rule
+ *   free:    drops the set with whatever is pending; init may follow.  picles_destroy frees it too; picles_checkpoint_load treats a
+ *            flux snapshot in flight like a store snapshot */
+#define PICLES_FLUX_PHI_IN     1
+#define PICLES_FLUX_PHI_DIS    2
+#define PICLES_FLUX_PHI_SHIFT  4
+#define PICLES_FLUX_TQ_IN_X    8
+#define PICLES_FLUX_TQ_IN_Y   16
+#define PICLES_FLUX_TQ_DIS_X  32
+#define PICLES_FLUX_TQ_DIS_Y  64
+#define PICLES_FLUX_US_X     128
+#define PICLES_FLUX_US_Y     256
+#define PICLES_FLUX_ALL      511
+#define PICLES_FLUX_NPARTIAL  11
+int32_t picles_flux_init(picles_ctx *ctx, int32_t cx, int32_t cy, int32_t field_mask, double scale_phi, double scale_tau, int32_t n_slots);
+int32_t picles_flux_shape(const picles_ctx *ctx, int32_t *nxc, int32_t *nyc_loc, int32_t *n_fields, int32_t *n_partials, size_t *bytes);
+int32_t picles_flux_push(picles_ctx *ctx);
+int32_t picles_flux_pop(picles_ctx *ctx, void *fields, double *partials, double *time);
+int32_t picles_flux_pending(const picles_ctx *ctx);
+int32_t picles_flux_export(picles_ctx *ctx, void *fields_dev, double *partials_dev, void *caller_stream);
+int32_t picles_flux_free(picles_ctx *ctx);
 
 /* ---- station probes: the State value of chosen nodes after every step, with the fused path kept --------------------------------
  * Point output — the series of the sea state at buoys, platforms, validation points — is what the reference's scripts cut out of

@@ -103,7 +103,7 @@ WIND_HOST, WIND_DEVICE = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 18
+ABI_VERSION = 19
 SLAB_ID_BYTES = 128
 PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
 
@@ -122,6 +122,13 @@ DIAG_FIELDS = ("hs", "tp", "cg_x", "cg_y", "e", "m_x", "m_y")
 DIAG_BITS = {name: 1 << k for k, name in enumerate(DIAG_FIELDS)}
 DIAG_TILE = 256
 DIAG_PARTIAL = ("sum_e", "sum_mx", "sum_my", "n_wet", "max_e", "max_mx", "max_my")
+
+# coupling fluxes (picles_flux_*): plane bits in plane order, and the eleven doubles of a tile partial
+FLUX_FIELDS = ("phi_in", "phi_dis", "phi_shift", "tq_in_x", "tq_in_y", "tq_dis_x", "tq_dis_y", "us_x", "us_y")
+FLUX_BITS = {name: 1 << k for k, name in enumerate(FLUX_FIELDS)}
+FLUX_ALL = 511
+FLUX_PARTIAL = tuple("sum_" + f for f in FLUX_FIELDS) + ("n_active", "n_bad")
+FLUX_NPARTIAL = 11
 
 ST_STEPPED, ST_MAXITERS, ST_RESEED_NAN, ST_RESEED_INF = 1, 2, 4, 8
 ST_CLAMPED, ST_SWITCHED_ON, ST_DTMIN, ST_NONFINITE = 16, 32, 64, 128
@@ -174,6 +181,13 @@ SYMBOLS = {
     "picles_diag_pop": (C.c_int32, [_VP, _VP, c_double_p, c_double_p]),
     "picles_diag_pending": (C.c_int32, [_VP]),
     "picles_diag_export": (C.c_int32, [_VP, _VP, c_double_p, _VP]),
+    "picles_flux_init": (C.c_int32, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32]),
+    "picles_flux_shape": (C.c_int32, [_VP, c_int32_p, c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_size_t)]),
+    "picles_flux_push": (C.c_int32, [_VP]),
+    "picles_flux_pop": (C.c_int32, [_VP, _VP, c_double_p, c_double_p]),
+    "picles_flux_pending": (C.c_int32, [_VP]),
+    "picles_flux_export": (C.c_int32, [_VP, _VP, c_double_p, _VP]),
+    "picles_flux_free": (C.c_int32, [_VP]),
     "picles_probe_init": (C.c_int32, [_VP, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32]),
     "picles_probe_sample": (C.c_int32, [_VP, _VP]),
     "picles_probe_pop": (C.c_int32, [_VP, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int64), c_int32_p]),

@@ -3,13 +3,17 @@
 PiCLES as the wave component of a coupled system: an atmosphere hands over the 10 m winds of one coupling interval, knows nothing of
 the next, and wants the sea state back.  `StreamedWinds` is the wind source for that — a lattice with regular (x, y) axes like
 `wind_emulator.GriddedWinds`, whose time levels t_k = t0 + k dt are pushed into a ring on the device (`picles_wind_stream_*`) — and
-`HipModel.diag_export` the way back: Hs / Tp / cg planes written into the caller's device tensors.  Both directions are ordered
-against torch's current stream with events; neither copies to the host.
+`HipModel.diag_export` the way back: Hs / Tp / cg planes written into the caller's device tensors.  Beside it, `FluxExport` hands back
+what the partner models consume rather than a description of the sea (`picles_flux_*`): the momentum and energy the
+waves take out of the wind (the wave-supported stress), what the breaking waves hand down to the ocean, and the surface Stokes drift.
+All directions are ordered against torch's current stream with events; none copies to the host.
 
     winds = StreamedWinds(x, y, t0=0.0, dt=3600.0, slots=3)
     model = WaveGrowth2D(winds=winds, winds_static=False, ...)
     initialize... ; winds.push(0, u0, v0); winds.push(1, u1, v1)      # NumPy arrays or torch CUDA tensors, (ny, nx) or flat
     model.backend.run_steps(dt, n)                                   # refused with a text if a level the steps read is missing
+    fluxes = FluxExport(model, coarsen=(4, 4), rho_water=1025.0)     # once
+    planes = fluxes()                                                # dict of [nyc, nxc] float32 CUDA tensors: tq_in_x, phi_dis, us_x, ...
 
 With `source=callable(k) -> (u, v)` run(sim) pulls the levels itself, a chunk at a time, as far as the ring admits.
 """
@@ -143,3 +147,32 @@ class StreamedWinds:
             n += 1
             t += dt
         return max(n, 1)
+
+
+class FluxExport:
+    """FluxExport(model, coarsen=(4, 4), fields=_capi.FLUX_FIELDS, rho_water=1025.0): the coupling fluxes of the model's current
+    step boundary in device tensors of its own (`picles_flux_export`).  Calling it runs the kernel behind the model's steps and orders
+    torch's current stream behind the kernel; it returns {plane name: float32 CUDA tensor [nyc, nxc]} — views of one block that the
+    next call overwrites — the phi planes in W m-2 (rho_water * g), the tq planes in N m-2 (rho_water), the Stokes drift in m s-1, as
+    area means over the coarse cells (land and calm nodes count as zero).  `partials` holds the tile partials ([n_partials, 11]
+    float64, on the device; driver.combine_flux_partials of its host copy gives the area totals).  The wind is the level the wind
+    window holds at the clock — after a step, the step's end level; a lattice or streamed model samples it where its planes hold
+    none (include/picles_hip.h, "coupling fluxes")."""
+
+    def __init__(self, model, coarsen=(4, 4), fields=K.FLUX_FIELDS, rho_water=1025.0, device=None):
+        import torch
+        b = self.backend = model.backend
+        if not hasattr(b, "flux_export"):
+            raise NotImplementedError("FluxExport needs the HIP library's flux set (picles_flux_*): this backend has none")
+        if not (np.isfinite(rho_water) and rho_water > 0.0):
+            raise ValueError("FluxExport: rho_water must be finite and positive")
+        b.flux_init(coarsen, fields, scale_phi=float(rho_water) * 9.81, scale_tau=float(rho_water), n_slots=1)
+        self.fields = b.flux_fields
+        nxc, nyc, nf, npart, _ = b.flux_shape()
+        dev = torch.device("cuda", getattr(b, "device", 0)) if device is None else device
+        self.planes = torch.zeros((nf, nyc, nxc), dtype=torch.float32, device=dev)
+        self.partials = torch.zeros((npart, K.FLUX_NPARTIAL), dtype=torch.float64, device=dev)
+
+    def __call__(self):
+        self.backend.flux_export(self.planes, self.partials)
+        return {f: self.planes[k] for k, f in enumerate(self.fields)}

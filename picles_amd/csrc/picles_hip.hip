@@ -35,6 +35,7 @@
  *   k_bforce         (k_bforce.hip) open-boundary forcing: behind the launch that writes a step's records, one lane per forced rim
  *                    node bears a particle from the prescribed sea state, advances it and leaves its record.  Latency bound.
  *   k_ckpt           checkpoint payload: packs / verifies / unpacks the planes of a restart blob in one pass. HBM bound.
+ *   k_flux           (k_flux.h) coupling fluxes: wind input, dissipation, stress and Stokes drift planes + one partial per tile
  *   k_diag           (k_diag.h) coarse wave diagnostics: float32 Hs / Tp / cg planes + one partial of sums and maxima per tile of
  *                    256 coarse cells, one pass over State. HBM bound.
  */
@@ -58,6 +59,7 @@
 
 #include "kernels.h"
 #include "k_diag.h"
+#include "k_flux.h"
 #include "k_probe.h"
 #include "k_stat.h"
 #include "k_nest.h"
@@ -574,6 +576,7 @@ struct WindWindow {
     double *um_buf = nullptr, *vm_buf = nullptr;
     double *lv_buf = nullptr, *xb_buf = nullptr;
     int poly_cap = 0;
+    double *sp_u = nullptr, *sp_v = nullptr;       /* a spare pair: the lattice's level at a time that is none of the window's (sample_spare) */
 
     bool static_() const { return shape.form == STATIC; }
     bool polyline() const { return shape.form == POLYLINE; }
@@ -588,6 +591,16 @@ struct WindWindow {
     /* does the window start where the pending step started, with (u1, v1) holding the lattice at the clock: can prepare() follow it? */
     bool contiguous_with(double pend_t, double clock) const { return held && held_t == clock && t0 == pend_t && !static_(); }
     bool middle(const Arrays &A, const double *&u, const double *&v) const { u = A.um; v = A.vm; return u != nullptr; }
+    /* the level planes the window holds at time t, as they stand — nothing is interpolated (picles_flux_*): a static
+     * window's only level; level 0 at the window's start; (u1, v1) at its end (whatever lies between: a knot or polyline window keeps
+     * its end level there too) — for a lattice at the time they hold it, and only while they are known to (invalidate()) */
+    bool level_at(const Arrays &A, double t, const double *&u, const double *&v) const
+    {
+        const bool ok = !lattice || held;
+        if (ok && (static_() || t == t0)) { u = A.u0; v = A.v0; return true; }
+        if (ok && t == (lattice ? held_t : t1)) { u = A.u1; v = A.v1; return true; }
+        return false;
+    }
 
     int make_pair(picles_ctx *c, double *&a, size_t a_bytes, double *&b, size_t b_bytes);
     int need(picles_ctx *c, const Shape &sh, bool prev = false);      /* the pairs a window of this shape reads (prev: and the fused remesh) */
@@ -602,6 +615,9 @@ struct WindWindow {
     int plan(picles_ctx *c, double t, double dt, Shape &sh) const;
     int sample(picles_ctx *c, const Shape &sh, double t, double dt, bool with0, hipStream_t s);
     int prepare(picles_ctx *c, double t, double dt, bool follow, hipStream_t s);
+    /* the lattice's level at time t, sampled on stream s into the spare pair (made on first use): for a reader whose clock is at
+     * none of the window's levels (level_at).  A wind stream that does not hold the level(s) bracketing t refuses, before anything is launched */
+    int sample_spare(picles_ctx *c, double t, const char *who, hipStream_t s, const double *&u, const double *&v);
     void release(Arrays &A);                       /* idempotent; the caller has drained the streams that read the planes */
 };
 
@@ -671,6 +687,12 @@ struct picles_ctx {
     int diag_nfields = 0, diag_npart = 0;
     size_t diag_field_bytes = 0, diag_part_off = 0, diag_slot_bytes = 0;
     double *diag_scratch = nullptr;                /* picles_diag_export without a partials buffer: where the kernel's partials go */
+    /* coupling fluxes (picles_flux_*; k_flux.h): a ring like the diagnostics' — a slot is the float32 planes followed by the tile partials */
+    OutRing flux_ring;
+    FluxP flux{};
+    int flux_nfields = 0, flux_npart = 0;
+    size_t flux_field_bytes = 0, flux_part_off = 0, flux_slot_bytes = 0;
+    double *flux_scratch = nullptr;                /* picles_flux_export without a partials buffer */
     int probe_n = 0;
     int *probe_nodes = nullptr;                    /* device: i plane, then the LOCAL row plane */
     Cadence probe_cad;                             /* steps: model steps completed since picles_probe_init */
@@ -1104,6 +1126,8 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     c->store.release();
     c->diag_ring.release();
     if (c->diag_scratch) hipFree(c->diag_scratch);
+    c->flux_ring.release();
+    if (c->flux_scratch) hipFree(c->flux_scratch);
     probe_release(c);
     if (c->trk) hipDeviceSynchronize();         /* samples issued on caller streams write the table about to go */
     track_release(c);
@@ -1222,7 +1246,7 @@ int WindWindow::drop_middle(picles_ctx *c)
 }
 void WindWindow::release(Arrays &A)
 {
-    for (double **p : {&A.uP, &A.vP, &um_buf, &vm_buf, &lv_buf, &xb_buf, &d_wgu, &d_wgv}) { hipFree(*p); *p = nullptr; }
+    for (double **p : {&A.uP, &A.vP, &um_buf, &vm_buf, &lv_buf, &xb_buf, &d_wgu, &d_wgv, &sp_u, &sp_v}) { hipFree(*p); *p = nullptr; }
     poly_cap = 0;
     for (hipEvent_t *e : {&ring_in, &ring_out}) { if (*e) hipEventDestroy(*e); *e = nullptr; }
     ring_off();
@@ -1506,6 +1530,42 @@ int WindWindow::prepare(picles_ctx *c, double t, double dt, bool follow, hipStre
     if (follow) rotate(c->A);
     else if (reuse) reuse_swap(c->A);
     return sample(c, sh, t, dt, !follow && !reuse, s);
+}
+
+int WindWindow::sample_spare(picles_ctx *c, double t, const char *who, hipStream_t s, const double *&u, const double *&v)
+{
+    const size_t plane = (size_t)c->A.n * 8;
+    dim3 grid(nblocks(c->A.n, 256)), block(256);
+    if (ring) {
+        int64_t k = 0;
+        double f = 0.0;
+        char b[400];
+        if (picles_wind_stream_coord(lat_t0, lat_dt, t, &k, &f)) {
+            snprintf(b, sizeof b, "%s: the clock %.17g lies before the first time level of the wind stream (t0 = %.17g)", who, t, lat_t0);
+            return fail(c, -2, b);
+        }
+        for (long long q = k; q <= k + (f != 0.0 ? 1 : 0); q++)
+            if (!ring_holds(q)) {
+                snprintf(b, sizeof b, "%s: the wind at the clock %.17g needs level k = %lld (t = %.17g) of the wind stream, which is not held "
+                                      "(levels held: %lld .. %lld): picles_wind_stream_push it first, or step to a level the window holds",
+                         who, t, q, lat_t0 + (double)q * lat_dt, ring_oldest(), ring_newest);
+                return fail(c, -2, b);
+            }
+        if (!sp_u) { int rc = make_pair(c, sp_u, plane, sp_v, plane); if (rc) return rc; }
+        WindRingOut O{};
+        O.s0[0] = (int)(k % ring_slots);
+        O.s1[0] = f != 0.0 ? (int)((k + 1) % ring_slots) : O.s0[0];
+        O.f[0] = f;
+        O.u[0] = sp_u; O.v[0] = sp_v;
+        hipLaunchKernelGGL(k_wind_sample_ring<1>, grid, block, 0, s, c->G, wg, O, c->A.n);
+    } else {
+        if (!sp_u) { int rc = make_pair(c, sp_u, plane, sp_v, plane); if (rc) return rc; }
+        WindSampleOut O = {{t, 0.0}, {sp_u, nullptr}, {sp_v, nullptr}};
+        hipLaunchKernelGGL(k_wind_sample<1>, grid, block, 0, s, c->G, wg, O, c->A.n);
+    }
+    HIPCHK(c, hipGetLastError());
+    u = sp_u; v = sp_v;
+    return 0;
 }
 
 /* ---- the wind stream (the contract: include/picles_hip.h, "streamed winds") ---- */
@@ -2619,6 +2679,158 @@ PX_EXPORT int32_t picles_diag_pop(picles_ctx *c, void *fields, double *partials,
     if (partials) memcpy(partials, s.host + c->diag_part_off, (size_t)c->diag_npart * 7 * 8);
     if (time) *time = s.time;
     c->diag_ring.drop();
+    return 0;
+}
+
+/* ---- coupling fluxes (the definition: include/picles_hip.h, "coupling fluxes"; the node and the kernel: k_flux.h) ---- */
+PX_EXPORT int32_t picles_flux_init(picles_ctx *c, int32_t cx, int32_t cy, int32_t field_mask, double scale_phi, double scale_tau, int32_t n_slots)
+{
+    if (!c) return -1;
+    if (cx < 1 || cx > 16 || cy < 1 || cy > 16) return fail(c, -2, "picles_flux_init: coarsening factors must be 1 ... 16");
+    if (field_mask <= 0 || (field_mask & ~PICLES_FLUX_ALL)) return fail(c, -2, "picles_flux_init: empty or unknown field mask");
+    if (!(std::isfinite(scale_phi) && scale_phi > 0.0 && std::isfinite(scale_tau) && scale_tau > 0.0))
+        return fail(c, -2, "picles_flux_init: scale_phi and scale_tau must be finite and positive");
+    if (n_slots < 1) return fail(c, -2, "picles_flux_init: n_slots must be >= 1");
+    if (c->flux_ring.cap) return fail(c, -2, "picles_flux_init: the flux set is already initialised (picles_flux_free first)");
+    if (c->G.j_begin % cy != 0) return fail(c, -2, "picles_flux_init: the slab's j_begin must be a multiple of cy (coarse cells are global)");
+    HIPCHK(c, hipSetDevice(c->device));
+    FluxP F{};
+    F.Nx = c->G.Nx; F.ny_loc = c->G.ny_loc; F.cx = cx; F.cy = cy;
+    F.Nxc = (c->G.Nx + cx - 1) / cx; F.nyc_loc = (c->G.ny_loc + cy - 1) / cy;
+    F.tiles_per_row = (F.Nxc + DIAG_TILE - 1) / DIAG_TILE;
+    F.mask = (unsigned)field_mask; F.scale_phi = scale_phi; F.scale_tau = scale_tau; F.plane = c->A.n;
+    const int nf = __builtin_popcount((unsigned)field_mask), np = F.nyc_loc * F.tiles_per_row;
+    const size_t fb = (size_t)4 * F.Nxc * F.nyc_loc * nf, po = (fb + 15) & ~(size_t)15, sb = po + (size_t)np * FLUX_NP * 8;
+    { int rc = c->flux_ring.init(c, n_slots, sb); if (rc) return rc; }
+    c->flux = F; c->flux_nfields = nf; c->flux_npart = np;
+    c->flux_field_bytes = fb; c->flux_part_off = po; c->flux_slot_bytes = sb;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_flux_shape(const picles_ctx *c, int32_t *nxc, int32_t *nyc_loc, int32_t *n_fields, int32_t *n_partials, size_t *bytes)
+{
+    if (!c || !c->flux_ring.cap) return -1;
+    if (nxc) *nxc = c->flux.Nxc;
+    if (nyc_loc) *nyc_loc = c->flux.nyc_loc;
+    if (n_fields) *n_fields = c->flux_nfields;
+    if (n_partials) *n_partials = c->flux_npart;
+    if (bytes) *bytes = c->flux_field_bytes;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_flux_pending(const picles_ctx *c) { return c ? c->flux_ring.count : -1; }
+
+/* the wind rule: the level planes the window holds at the clock; a lattice or streamed context whose window holds none samples the
+ * level at the clock (k_wind_sample<1>, the sampler of its windows: a function of the time alone); a host-set window refuses with a
+ * text that names the remedy — before anything is launched (the flush of a pending step included: it changes neither the window nor
+ * the clock) */
+static int flux_wind(picles_ctx *c, const char *who, const double *&u, const double *&v)
+{
+    if (c->wind.level_at(c->A, c->clock, u, v)) return 0;
+    if (c->wind.from_lattice()) {      /* the device has the source: the level at the clock itself, into the spare pair */
+        HIPCHK(c, hipSetDevice(c->device));
+        return c->wind.sample_spare(c, c->clock, who, c->stream, u, v);
+    }
+    char buf[400];
+    snprintf(buf, sizeof buf, "%s: the wind window [%.17g, %.17g] holds no level at the clock %.17g, and nothing is interpolated: step to a "
+             "level (the end of a model step is one), or set the window (picles_set_winds*) so that it starts or ends at the clock",
+             who, c->wind.t0, c->wind.t1, c->clock);
+    return fail(c, -2, buf);
+}
+
+template <int CX, bool VEC>
+static void flux_launch(picles_ctx *c, const double *u, const double *v, float *fields, double *partials)
+{
+    hipLaunchKernelGGL((k_flux<CX, VEC>), dim3((unsigned)c->flux_npart), dim3(DIAG_TILE), 0, c->stream, c->P, c->flux, (const double *)c->A.state,
+                       u, v, fields, partials);
+}
+
+/* State at the step boundary, then the kernel on the context stream into (fields, partials): a ring slot (push) or the caller's
+ * device buffers (export).  (u, v): the planes flux_wind found */
+static int flux_run(picles_ctx *c, const double *u, const double *v, float *fields, double *partials)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flush(c); if (rc) return rc; }
+    if (c->ext_streams) HIPCHK(c, hipDeviceSynchronize());   /* an un-fused slab step leaves its scatter on the ring's stream M */
+    /* 16-byte loads: every cell's row segment starts on a 16-byte boundary of each of the five planes */
+    const bool vec = (c->flux.Nx & 1) == 0 && (c->A.n & 1) == 0 && (((uintptr_t)c->A.state | (uintptr_t)u | (uintptr_t)v) & 15u) == 0;
+    timing_begin(c, c->stream, 4);      /* other_ms of picles_get_timing: the slot k_diag and the checkpoint kernel share (a kernel trace tells them apart) */
+    switch (c->flux.cx) {
+    case 1: flux_launch<1, false>(c, u, v, fields, partials); break;
+    case 2: if (vec) flux_launch<2, true>(c, u, v, fields, partials); else flux_launch<2, false>(c, u, v, fields, partials); break;
+    case 4: if (vec) flux_launch<4, true>(c, u, v, fields, partials); else flux_launch<4, false>(c, u, v, fields, partials); break;
+    default: flux_launch<0, false>(c, u, v, fields, partials);
+    }
+    timing_end(c, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+PX_EXPORT int32_t picles_flux_push(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->flux_ring.cap) return fail(c, -2, "picles_flux_init first");
+    unsigned char *d = c->flux_ring.next_slot();
+    if (!d) return fail(c, -3, "flux ring full: pop first");
+    const double *u, *v;
+    { int rc = flux_wind(c, "picles_flux_push", u, v); if (rc) return rc; }
+    { int rc = flux_run(c, u, v, (float *)d, (double *)(d + c->flux_part_off)); if (rc) return rc; }
+    /* stream-ordered behind the step that produced State; the D2H leg runs beside the next steps */
+    return c->flux_ring.ship(c, d, c->stream, c->flux_slot_bytes, 0);
+}
+
+/* the same kernel into the caller's device buffers: no slot, no copy to the host; the caller's stream waits for the kernel */
+PX_EXPORT int32_t picles_flux_export(picles_ctx *c, void *fields_dev, double *partials_dev, void *caller_stream)
+{
+    if (!c) return -1;
+    if (!c->flux_ring.cap) return fail(c, -2, "picles_flux_init first");
+    if (!fields_dev) return fail(c, -2, "picles_flux_export: no device buffer for the fields");
+    const double *u, *v;
+    { int rc = flux_wind(c, "picles_flux_export", u, v); if (rc) return rc; }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!partials_dev) {      /* the kernel writes its partials somewhere: a block of the context's own, made on first use */
+        if (!c->flux_scratch) HIPCHK(c, hipMalloc(&c->flux_scratch, (size_t)c->flux_npart * FLUX_NP * 8));
+        partials_dev = c->flux_scratch;
+    }
+    if (caller_stream) {      /* whatever the caller still has reading or writing its buffers comes first */
+        HIPCHK(c, hipEventRecord(c->ev_ctx, (hipStream_t)caller_stream));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ctx, 0));
+    }
+    { int rc = flux_run(c, u, v, (float *)fields_dev, partials_dev); if (rc) return rc; }
+    if (caller_stream) {
+        HIPCHK(c, hipEventRecord(c->ev_ctx, c->stream));
+        HIPCHK(c, hipStreamWaitEvent((hipStream_t)caller_stream, c->ev_ctx, 0));
+    }
+    return 0;
+}
+
+PX_EXPORT int32_t picles_flux_pop(picles_ctx *c, void *fields, double *partials, double *time)
+{
+    if (!c || !fields) return -1;
+    if (!c->flux_ring.count) return fail(c, -3, "no flux snapshot pending");
+    HIPCHK(c, hipSetDevice(c->device));
+    OutRing::Slot s;
+    { int rc = c->flux_ring.front(c, s); if (rc) return rc; }
+    memcpy(fields, s.host, c->flux_field_bytes);
+    if (partials) memcpy(partials, s.host + c->flux_part_off, (size_t)c->flux_npart * FLUX_NP * 8);
+    if (time) *time = s.time;
+    c->flux_ring.drop();
+    return 0;
+}
+
+/* the set goes, with whatever is still pending: the kernel and the copies that use the slots are waited for first */
+PX_EXPORT int32_t picles_flux_free(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->flux_ring.cap) return fail(c, -2, "picles_flux_init first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->store_stream) HIPCHK(c, hipStreamSynchronize(c->store_stream));
+    c->flux_ring.release();
+    if (c->flux_scratch) { hipFree(c->flux_scratch); c->flux_scratch = nullptr; }
+    c->flux = FluxP{};
+    c->flux_nfields = c->flux_npart = 0;
+    c->flux_field_bytes = c->flux_part_off = c->flux_slot_bytes = 0;
     return 0;
 }
 
@@ -4662,7 +4874,7 @@ PX_EXPORT int32_t picles_checkpoint_load(picles_ctx *c, const void *buf, size_t 
     if (!c || !buf) return -1;
     if (c->probe.count > 0)
         return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_load: probe samples of this context are pending (picles_probe_pop first)");
-    if (c->ck_inflight || c->store.count > 0 || c->diag_ring.count > 0)
+    if (c->ck_inflight || c->store.count > 0 || c->diag_ring.count > 0 || c->flux_ring.count > 0)
         return fail(c, PICLES_CKPT_E_BUSY, "picles_checkpoint_load: a checkpoint or store snapshot of this context is in flight (end / pop it first)");
     CkptHeader h;
     if (bytes < sizeof h) return fail(c, PICLES_CKPT_E_SHORT, "picles_checkpoint_load: buffer shorter than a checkpoint header");

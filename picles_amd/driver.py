@@ -82,6 +82,36 @@ def combine_partials(list_of_partials, Nx, Ny) -> dict:
 
 SCALAR_NAMES = K.DIAG_PARTIAL + ("mean_of_state",)
 
+
+def flux_field_mask(fields) -> int:
+    """plane names (or a ready bit mask) -> PICLES_FLUX_* bit mask"""
+    if isinstance(fields, (int, np.integer)):
+        return int(fields)
+    if isinstance(fields, str):
+        fields = (fields,)
+    unknown = [f for f in fields if f not in K.FLUX_BITS]
+    if unknown:
+        raise ValueError(f"unknown flux planes {unknown}: choose from {K.FLUX_FIELDS}")
+    mask = 0
+    for f in fields:
+        mask |= K.FLUX_BITS[f]
+    return mask
+
+
+def combine_flux_partials(list_of_partials) -> dict:
+    """the eleven area totals from the tile partials of picles_flux_pop — one [n_partials, 11] array, or a list of them in rank
+    order for a slab run — combined sequentially in ascending (J, tile) order from +0.0: the same bits whatever the decomposition.
+    The nine sums are UNSCALED node sums (multiply by the cell area and the set's scale for an integrated flux)."""
+    if isinstance(list_of_partials, np.ndarray) and list_of_partials.ndim == 2:
+        list_of_partials = [list_of_partials]
+    acc = [0.0] * K.FLUX_NPARTIAL
+    for part in list_of_partials:
+        for row in np.asarray(part, dtype=np.float64).reshape(-1, K.FLUX_NPARTIAL).tolist():
+            for k in range(K.FLUX_NPARTIAL):
+                acc[k] = acc[k] + row[k]
+    return dict(zip(K.FLUX_PARTIAL, acc))
+
+
 # ---- run statistics: the plane block of picles_stat_get / picles_stat_set (include/picles_hip.h "run statistics") ----
 STAT_GROUPS = {"peak": K.STAT_PEAK, "mean": K.STAT_MEAN, "exceed": K.STAT_EXCEED}
 STAT_PEAK_PLANES = ("e_peak", "mx_peak", "my_peak", "t_peak")
@@ -566,6 +596,72 @@ class HipModel:
     @property
     def diag_pending(self):
         return self.lib.picles_diag_pending(self.h)
+
+    # ---- coupling fluxes (picles_flux_*: wind input, dissipation, stress and Stokes drift planes + area totals, on the device) ----
+    def flux_init(self, coarsen=(4, 4), fields=K.FLUX_FIELDS, scale_phi=1.0, scale_tau=1.0, n_slots=3):
+        """coarsen = (cx, cy), each 1 ... 16; fields: names out of _capi.FLUX_FIELDS (the planes come in that order, whatever the
+        order given here) or the bit mask itself; scale_phi multiplies the three phi planes (rho_water * g: W m^-2), scale_tau the
+        four tq planes (rho_water: N m^-2)"""
+        cx, cy = (coarsen, coarsen) if np.isscalar(coarsen) else coarsen
+        mask = flux_field_mask(fields)
+        self._ck(self.lib.picles_flux_init(self.h, int(cx), int(cy), mask, float(scale_phi), float(scale_tau), int(n_slots)), "picles_flux_init")
+        self.flux_fields = tuple(f for f in K.FLUX_FIELDS if mask & K.FLUX_BITS[f])
+        self.flux_coarsen = (int(cx), int(cy))
+
+    def flux_shape(self):
+        """(Nxc, nyc_loc, n_fields, n_partials, bytes of the float32 field block); no device work"""
+        a = [C.c_int32() for _ in range(4)]
+        b = C.c_size_t()
+        rc = self.lib.picles_flux_shape(self.h, *[C.byref(x) for x in a], C.byref(b))
+        if rc != 0:
+            raise K.PiclesError("picles_flux_shape failed: flux_init first")
+        return tuple(x.value for x in a) + (b.value,)
+
+    def flux_push(self):
+        self._ck(self.lib.picles_flux_push(self.h), "picles_flux_push")
+
+    def flux_pop(self):
+        """the oldest snapshot: (planes float32 [n_fields, Nxc, nyc_loc] — each plane Fortran-ordered, i.e. [I + Nxc J] in memory —,
+        partials float64 [n_partials, 11], model time)"""
+        nxc, nyc, nf, npart, _ = self.flux_shape()
+        f = np.empty(nf * nxc * nyc, dtype=np.float32)
+        p = np.empty((npart, K.FLUX_NPARTIAL))
+        t = C.c_double()
+        self._ck(self.lib.picles_flux_pop(self.h, f.ctypes.data, K.dptr(p), C.byref(t)), "picles_flux_pop")
+        return f.reshape((nf, nyc, nxc)).transpose(0, 2, 1), p, t.value
+
+    def flux_export(self, fields, partials=None):
+        """the snapshot of flux_push, written into torch CUDA tensors instead of a ring slot (picles_flux_export): `fields` float32,
+        contiguous, n_fields * Nxc * nyc_loc values (the memory layout of flux_pop: [n_fields, nyc_loc, Nxc]); `partials` float64
+        [n_partials, 11] or None.  Nothing is copied to the host; torch's current stream is ordered behind the kernel"""
+        import torch
+        nxc, nyc, nf, npart, _ = self.flux_shape()
+        if not (fields.is_cuda and fields.dtype == torch.float32 and fields.is_contiguous() and fields.numel() == nf * nxc * nyc):
+            raise ValueError(f"flux_export: fields must be a contiguous float32 device tensor of {nf} x {nyc} x {nxc} values")
+        if partials is not None and not (partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()
+                                         and partials.numel() == npart * K.FLUX_NPARTIAL):
+            raise ValueError(f"flux_export: partials must be a contiguous float64 device tensor of {npart} x {K.FLUX_NPARTIAL} values")
+        cur = torch.cuda.current_stream(fields.device)
+        s = cur
+        if not cur.cuda_stream:          # torch's default stream is the null stream: ordered through a side stream (diag_export)
+            s = getattr(self, "_stream_side", None)
+            if s is None:
+                s = self._stream_side = torch.cuda.Stream(fields.device)
+            s.wait_stream(cur)
+        try:
+            self._ck(self.lib.picles_flux_export(self.h, fields.data_ptr(), None if partials is None else C.cast(partials.data_ptr(), K.c_double_p),
+                                                 s.cuda_stream), "picles_flux_export")
+        finally:
+            if s is not cur:
+                cur.wait_stream(s)
+
+    def flux_free(self):
+        self._ck(self.lib.picles_flux_free(self.h), "picles_flux_free")
+        self.flux_fields = ()
+
+    @property
+    def flux_pending(self):
+        return self.lib.picles_flux_pending(self.h)
 
     # ---- station probes (picles_probe_*: the State value of chosen nodes behind every step, the fused path kept) ----
     def probe_init(self, nodes, every=1, first=1, capacity=64):

@@ -41,22 +41,27 @@ def coarse_coordinate(x, c: int):
 
 
 class NpyFieldStore:
-    format = "npy"
+    """group, scalar_names: what a sibling product (picles_amd/flux_output.py) changes; `extra`: further entries of the side-car"""
 
-    def __init__(self, path, name, time, x, y, var_names):
+    format = "npy"
+    group = "waves"
+    scalar_names = SCALAR_NAMES
+
+    def __init__(self, path, name, time, x, y, var_names, extra=None):
         self.dir = Path(path)
         self.dir.mkdir(parents=True, exist_ok=True)
         self.shape = (len(time), len(x), len(y), len(var_names))
-        self.path = self.dir / f"{name}.waves.data.npy"
+        self.path = self.dir / f"{name}.{self.group}.data.npy"
         self.data = np.lib.format.open_memmap(self.path, mode="w+", dtype=np.float32, shape=self.shape)
-        self.scalars = np.lib.format.open_memmap(self.dir / f"{name}.waves.scalars.npy", mode="w+", dtype=np.float64,
-                                                 shape=(len(time), len(SCALAR_NAMES)))
+        self.scalars = np.lib.format.open_memmap(self.dir / f"{name}.{self.group}.scalars.npy", mode="w+", dtype=np.float64,
+                                                 shape=(len(time), len(self.scalar_names)))
         self.data[:] = np.nan
         self.scalars[:] = np.nan
         self.json = self.dir / f"{name}.json"
-        self.meta = {"group": "waves", "dims": ["time", "x", "y", "field"], "var_names": list(var_names),
-                     "scalar_names": list(SCALAR_NAMES), "time": [float("nan")] * len(time), "x": list(map(float, x)),
+        self.meta = {"group": self.group, "dims": ["time", "x", "y", "field"], "var_names": list(var_names),
+                     "scalar_names": list(self.scalar_names), "time": [float("nan")] * len(time), "x": list(map(float, x)),
                      "y": list(map(float, y))}
+        self.meta.update(extra or {})
 
     def write(self, i, fields, scalars, time):
         self.data[i] = np.moveaxis(fields, 0, -1)
@@ -73,9 +78,11 @@ class H5FieldStore:
     """the HDF5 form, through the file layer of picles_amd/storing.py"""
 
     format = "hdf5"
+    group = "waves"
+    scalar_names = SCALAR_NAMES
 
-    def __init__(self, path, name, time, x, y, var_names):
-        h = self.h5 = H5File(path, name, "waves")
+    def __init__(self, path, name, time, x, y, var_names, extra=None):
+        h = self.h5 = H5File(path, name, self.group)
         self.dir, self.path = h.dir, h.path
         nt, nx, ny, nf = self.shape = (len(time), len(x), len(y), len(var_names))
         self.data = h.sliced("data", (nf, ny, nx, nt), np.float32)
@@ -84,9 +91,14 @@ class H5FieldStore:
         h.f64("x", x)
         h.f64("y", y)
         h.strings("var_names", list(var_names))
-        h.strings("scalar_names", list(SCALAR_NAMES))
+        h.strings("scalar_names", list(self.scalar_names))
+        for k, v in (extra or {}).items():          # lists of strings become string datasets, numbers float64 datasets
+            if isinstance(v, (list, tuple)) and v and isinstance(v[0], str):
+                h.strings(k, list(v))
+            else:
+                h.f64(k, np.atleast_1d(np.asarray(v, dtype=np.float64)))
         self.times = np.full(nt, np.nan)
-        self.scalars = np.full((nt, len(SCALAR_NAMES)), np.nan)
+        self.scalars = np.full((nt, len(self.scalar_names)), np.nan)
 
     def write(self, i, fields, scalars, time):
         # (field, y, x): a no-op for the planes as popped

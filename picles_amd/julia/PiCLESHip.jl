@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(18)
+const PICLES_ABI_VERSION = Int32(19)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -499,6 +499,97 @@ function diag_export!(model::WaveGrowth2DHIP, fields::Ptr{Float32}, partials::Pt
     check(model.ctx, ccall((:picles_diag_export, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}),
         model.ctx, fields, partials, stream), "picles_diag_export")
     after_step!(model.State)
+    nothing
+end
+
+const FLUX_FIELDS = (:phi_in, :phi_dis, :phi_shift, :tq_in_x, :tq_in_y, :tq_dis_x, :tq_dis_y, :us_x, :us_y)      # PICLES_FLUX_* bits in plane order
+
+"""
+    flux_init!(model; coarsen=(4, 4), fields=FLUX_FIELDS, rho_water=1025.0, slots=3)
+    flux_shape(model) -> (nxc, nyc, n_fields, n_partials, bytes)
+    flux_push!(model); flux_pop!(model, planes, partials) -> t; flux_pending(model)
+    flux_export!(model, fields, partials=C_NULL; stream=C_NULL)
+    flux_free!(model)
+    run_fluxes!(model, Δt, n_steps, sink!; every=10, coarsen=(4, 4), fields=FLUX_FIELDS, rho_water=1025.0, slots=3)
+
+Coupling fluxes (`picles_flux_*`; the contract is in include/picles_hip.h, "coupling fluxes"): what the partner models consume —
+the energy and momentum the waves take out of the wind (`phi_in`, `tq_in`: the wave-supported stress), what the breaking waves
+hand down to the ocean (`phi_dis`, `tq_dis`) and the surface Stokes drift (`us`) — formed on the device from State and the wind at
+the clock, as area means over coarse cells.  `rho_water` sets the scales: the `phi` planes come in W m⁻² (`rho_water * g`), the `tq`
+planes in N m⁻².  `run_fluxes!` is `run_fields!` with these planes: `sink!(i, planes::Array{Float32,3}, partials::Matrix{Float64}, t)`,
+`partials[:, k]` the eleven doubles (nine unscaled sums, n_active, n_bad) of tile k.  A push or export at a clock where the wind
+window holds no level is refused: the end of every model step is a level.
+"""
+function flux_init!(model::WaveGrowth2DHIP; coarsen=(4, 4), fields=FLUX_FIELDS, rho_water::Real=1025.0, slots::Integer=3)
+    mask = Int32(0)
+    for f in fields
+        k = findfirst(==(Symbol(f)), FLUX_FIELDS)
+        k === nothing && error("unknown flux plane $f")
+        mask |= Int32(1) << (k - 1)
+    end
+    check(model.ctx, ccall((:picles_flux_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Float64, Float64, Int32),
+        model.ctx, coarsen[1], coarsen[2], mask, Float64(rho_water) * 9.81, Float64(rho_water), slots), "picles_flux_init")
+    nothing
+end
+
+function flux_shape(model::WaveGrowth2DHIP)
+    nxc, nyc, nf, np = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0)
+    nbytes = Ref{Csize_t}(0)
+    ccall((:picles_flux_shape, libpicles), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Csize_t}), model.ctx, nxc, nyc, nf, np, nbytes) == 0 ||
+        error("picles_flux_shape failed: flux_init! first")
+    (nxc[], nyc[], nf[], np[], nbytes[])
+end
+
+flux_push!(model::WaveGrowth2DHIP) = (check(model.ctx, ccall((:picles_flux_push, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_flux_push"); after_step!(model.State); nothing)
+
+function flux_pop!(model::WaveGrowth2DHIP, planes::Array{Float32,3}, partials::Matrix{Float64})
+    t = Ref(0.0)
+    check(model.ctx, ccall((:picles_flux_pop, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}), model.ctx, planes, partials, t), "picles_flux_pop")
+    t[]
+end
+
+flux_pending(model::WaveGrowth2DHIP) = ccall((:picles_flux_pending, libpicles), Int32, (Ptr{Cvoid},), model.ctx)
+
+function flux_export!(model::WaveGrowth2DHIP, fields::Ptr{Float32}, partials::Ptr{Float64}=Ptr{Float64}(C_NULL); stream::Ptr{Cvoid}=C_NULL)
+    check(model.ctx, ccall((:picles_flux_export, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}),
+        model.ctx, fields, partials, stream), "picles_flux_export")
+    after_step!(model.State)
+    nothing
+end
+
+flux_free!(model::WaveGrowth2DHIP) = (check(model.ctx, ccall((:picles_flux_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_flux_free"); nothing)
+
+function run_fluxes!(model::WaveGrowth2DHIP, Δt::Float64, n_steps::Integer, sink!; every::Integer=10, coarsen=(4, 4),
+                     fields=FLUX_FIELDS, rho_water::Real=1025.0, slots::Integer=3)
+    upload_winds!(model, model.clock.time, Δt)
+    model.winds_static || error("run_fluxes! needs winds the device can produce by itself (static winds or wind_lattice)")
+    flux_init!(model; coarsen=coarsen, fields=fields, rho_water=rho_water, slots=slots)
+    nxc, nyc, nf, np, _ = flux_shape(model)
+    planes = Array{Float32,3}(undef, nxc, nyc, nf)
+    partials = Matrix{Float64}(undef, 11, np)
+    i = 1
+    drain_one() = begin
+        t = flux_pop!(model, planes, partials)
+        sink!(i, planes, partials, t); i += 1
+    end
+    flux_push!(model)
+    done = 0
+    while done < n_steps
+        k = min(every, n_steps - done)
+        check(model.ctx, ccall((:picles_run_steps, libpicles), Int32, (Ptr{Cvoid}, Float64, Int32), model.ctx, Δt, k), "picles_run_steps")
+        for _ in 1:k
+            PiCLES.Operators.TimeSteppers.tick!(model.clock, Δt)
+        end
+        done += k
+        k == every || break                       # a remainder shorter than `every` ends the run without an output
+        flux_pending(model) == slots && drain_one()
+        flux_push!(model)
+    end
+    while flux_pending(model) > 0
+        drain_one()
+    end
+    flux_free!(model)
+    check_dropped(model)
     nothing
 end
 

@@ -551,6 +551,38 @@ class SlabModel:
         dist.all_gather_object(parts, (f, p))
         return (np.concatenate([a for a, _ in parts], axis=2), combine_partials([b for _, b in parts], Nx, Ny), t)
 
+    # ---- coupling fluxes of this rank's rows (picles_flux_*; needs j_begin % cy == 0 on every rank) ----
+    def flux_init(self, coarsen=(4, 4), fields=K.FLUX_FIELDS, scale_phi=1.0, scale_tau=1.0, n_slots=3):
+        self.backend.flux_init(coarsen, fields, scale_phi, scale_tau, n_slots)
+
+    def flux_shape(self):
+        return self.backend.flux_shape()
+
+    def flux_push(self):
+        """snapshot the fluxes of the current step boundary (collective in effect: every rank pushes at the same step)"""
+        self.sync()
+        self.backend.flux_push()
+
+    def flux_pop(self):
+        return self.backend.flux_pop()
+
+    @property
+    def flux_pending(self):
+        return self.backend.flux_pending
+
+    def gather_fluxes(self):
+        """pop this rank's oldest flux snapshot and gather all ranks': (planes [n_fields, Nxc, Nyc] concatenated along y in rank
+        order, the eleven area totals formed from the partials in rank order, J ascending, model time).  Coarse cells are global, so
+        both equal a single context's bit for bit."""
+        from .driver import combine_flux_partials
+        f, p, t = self.backend.flux_pop()
+        if self.world == 1:
+            return f, combine_flux_partials([p]), t
+        import torch.distributed as dist
+        parts = [None] * self.world
+        dist.all_gather_object(parts, (f, p))
+        return (np.concatenate([a for a, _ in parts], axis=2), combine_flux_partials([b for _, b in parts]), t)
+
     # ---- station probes: every rank samples the nodes of its own rows (picles_probe_*) ----
     def probe_init(self, nodes, every=1, first=1, capacity=64):
         """nodes: (n, 2) global 0-based (i, j) anywhere on the grid, the same list on every rank; each rank probes those inside its
