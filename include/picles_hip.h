@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PICLES_ABI_VERSION 19
+#define PICLES_ABI_VERSION 20
 
 /* ---- grid: TwoDCartesianGridStatistics + mesh mask (Grids/CartesianGrid.jl:26-101,
  *      Grids/mask_utils.jl:38-55) ------------------------------------------------ */
@@ -427,6 +427,72 @@ int32_t picles_flux_pop(picles_ctx *ctx, void *fields, double *partials, double 
 int32_t picles_flux_pending(const picles_ctx *ctx);
 int32_t picles_flux_export(picles_ctx *ctx, void *fields_dev, double *partials_dev, void *caller_stream);
 int32_t picles_flux_free(picles_ctx *ctx);
+
+/* ---- flux means: the coupling fluxes accumulated behind every step and exported as interval means (ABI 20) ---------------------
+ * A coupler does not exchange snapshots: the wave model takes several steps per coupling interval, and what the partners must
+ * receive is the momentum and energy that crossed the surface over the interval — the time mean of the fluxes over the wave steps
+ * in it (WAVEWATCH III and the couplers built on OASIS or ESMF exchange interval means for this reason).  A context that holds a flux
+ * set (picles_flux_init) may also hold ONE mean set; it takes its coarse cells, its mask and its scales from the flux set.
+ *
+ * STORAGE.  Eleven fp64 accumulator planes of Nxc x nyc_loc, column-major [I + Nxc J] like the flux planes, all zero at init: the
+ * nine sums in PICLES_FLUX_* bit order — always all nine: the mask selects only at export — then n_active and n_bad, which are
+ * counts.  88 B per coarse cell.  The host side keeps n_samples, t_first and t_last, as the statistics set does.
+ *
+ * ONE UPDATE, at a moment when the clock is t:
+ *   1. every node gets the State value picles_get_state would return for it at that moment, bit for bit: with a fused step pending
+ *      from its scatter records, by the pull the scatter would run (as the statistics set and the station probes do); otherwise
+ *      from State in memory;
+ *   2. the wind is THE WIND AT THE CLOCK of the flux set (above), with its refusals, which come before anything is launched;
+ *   3. per coarse cell the eleven cell sums S_q are those of the flux kernel: the node arithmetic of k_flux.h per node, the nodes
+ *      visited j outer, i inner, from +0.0; active nodes add their nine values and count into n_active, bad nodes into n_bad;
+ *   4. acc_q = acc_q + S_q, one fp64 addition per plane and cell; n_samples goes up by one, t_last = t (and t_first = t at the
+ *      first sample).
+ * An update does not complete a pending fused step and does not synchronise the host; it leaves State, particles, counters, reach
+ * counters, dispatch order, clock and the restart blob untouched.  Samples carry EQUAL weight: a caller who changes Δt inside an
+ * interval should export before the change.
+ *
+ * AUTOMATIC UPDATES.  picles_time_step, picles_run_steps and picles_slab_run_steps update behind every model step they complete for
+ * which s >= first and (s - first) % every == 0, s counting the steps completed since picles_flux_mean_init: the schedule, the
+ * places and the stream ordering of the statistics set (in the native ring: the probe stream).  The split-phase calls count steps
+ * and do not update: their caller calls picles_flux_mean_update(ctx, stream) behind the scatter of the step.  Operations on the
+ * accumulators are ordered behind each other whatever streams they use.  An automatic update runs BEHIND its step: where the wind rule
+ * refuses it — only a host-set window that does not end where the step ends can: a static window, a window over [t, t + dt], a
+ * lattice and a stream always hold or sample the level — the call returns -2 with the step taken, the clock advanced and no
+ * sample counted (in picles_run_steps and picles_slab_run_steps: at that step, the steps before it taken and sampled); the text
+ * names the remedy, and the caller may set the window and call picles_flux_mean_update for the sample that is missing.
+ *
+ * THE MEAN needs n = n_samples >= 1.  For a selected plane q a cell holds
+ *     plane_q = (float)((acc_q / (n_cover * n)) * scale_q)
+ * n_cover the nodes the cell covers; the product n_cover * n formed in fp64 (exact), then one division; the scale the last fp64
+ * operation; rounded to float32, nearest even.  scale_q and the selection of planes are the flux set's.  The tile partials of a mean
+ * are eleven doubles per tile of 256 coarse columns: each accumulator plane reduced by the tree of the flux partials, unscaled and
+ * undivided; the host divides by n.
+ *
+ *   init:    refuses (-2, context unchanged): no flux set, every < 1, first < 1, a second init
+ *   shape:   every, the number of accumulator planes (11), their bytes; -1 without a set; no device work
+ *   update:  one update now, on `stream` (NULL: the context stream).  Refuses: no set; the wind rule
+ *   push:    the finalising kernel writes fields and partials into the next slot of the FLUX SET's ring, in the slot layout of
+ *            picles_flux_push; picles_flux_pop / picles_flux_pending serve it; the slot's time is the clock.  With reset != 0 the
+ *            accumulators and the three scalars go to zero in stream order behind it.  A pending step stays pending.  Refuses: no
+ *            set, ring full (-3), n_samples == 0 (-2)
+ *   export:  the same into the CALLER's device buffers (partials_dev may be NULL), ordered like picles_flux_export
+ *   get:     the raw accumulators (11 planes of Nxc nyc_loc doubles) and the three scalars; waits for the latest operation on the
+ *            accumulators only, through an event: a pending step stays pending.  planes may be NULL: the scalars alone, which the
+ *            host keeps — no device work
+ *   set:     the raw accumulators in, behind the updates already issued: how a picked-up run continues an open interval
+ *            (picles_checkpoint_load leaves the accumulators as they are: they are no part of the blob)
+ *   reset:   accumulators and scalars to zero, in stream order; s goes on
+ *   free:    drops the mean set.  picles_flux_free and picles_destroy drop it with the flux set.  picles_nest_relocate on a context
+ *            whose mean set holds samples refuses (-2): push or reset first — the cells would mean another place after the move */
+int32_t picles_flux_mean_init(picles_ctx *ctx, int32_t every, int32_t first);
+int32_t picles_flux_mean_shape(const picles_ctx *ctx, int32_t *every, int32_t *n_planes, size_t *bytes);
+int32_t picles_flux_mean_update(picles_ctx *ctx, void *stream);
+int32_t picles_flux_mean_push(picles_ctx *ctx, int32_t reset);
+int32_t picles_flux_mean_export(picles_ctx *ctx, void *fields_dev, double *partials_dev, void *caller_stream, int32_t reset);
+int32_t picles_flux_mean_get(picles_ctx *ctx, double *planes, int64_t *n_samples, double *t_first, double *t_last);
+int32_t picles_flux_mean_set(picles_ctx *ctx, const double *planes, int64_t n_samples, double t_first, double t_last);
+int32_t picles_flux_mean_reset(picles_ctx *ctx);
+int32_t picles_flux_mean_free(picles_ctx *ctx);
 
 /* ---- station probes: the State value of chosen nodes after every step, with the fused path kept --------------------------------
  * Point output — the series of the sea state at buoys, platforms, validation points — is what the reference's scripts cut out of

@@ -103,7 +103,7 @@ WIND_HOST, WIND_DEVICE = 0, 1
 STEP_ZERO_FIRST = 1
 STEP_MOVIE = 2
 STEP_ATOMIC = 4
-ABI_VERSION = 19
+ABI_VERSION = 20
 SLAB_ID_BYTES = 128
 PROBE_E_FULL = -30          # a step entry point or picles_probe_sample found the probe ring full (include/picles_hip.h)
 
@@ -188,6 +188,15 @@ SYMBOLS = {
     "picles_flux_pending": (C.c_int32, [_VP]),
     "picles_flux_export": (C.c_int32, [_VP, _VP, c_double_p, _VP]),
     "picles_flux_free": (C.c_int32, [_VP]),
+    "picles_flux_mean_init": (C.c_int32, [_VP, C.c_int32, C.c_int32]),
+    "picles_flux_mean_shape": (C.c_int32, [_VP, c_int32_p, c_int32_p, C.POINTER(C.c_size_t)]),
+    "picles_flux_mean_update": (C.c_int32, [_VP, _VP]),
+    "picles_flux_mean_push": (C.c_int32, [_VP, C.c_int32]),
+    "picles_flux_mean_export": (C.c_int32, [_VP, _VP, c_double_p, _VP, C.c_int32]),
+    "picles_flux_mean_get": (C.c_int32, [_VP, c_double_p, C.POINTER(C.c_int64), c_double_p, c_double_p]),
+    "picles_flux_mean_set": (C.c_int32, [_VP, c_double_p, C.c_int64, C.c_double, C.c_double]),
+    "picles_flux_mean_reset": (C.c_int32, [_VP]),
+    "picles_flux_mean_free": (C.c_int32, [_VP]),
     "picles_probe_init": (C.c_int32, [_VP, C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32]),
     "picles_probe_sample": (C.c_int32, [_VP, _VP]),
     "picles_probe_pop": (C.c_int32, [_VP, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int64), c_int32_p]),

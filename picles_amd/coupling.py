@@ -176,3 +176,33 @@ class FluxExport:
     def __call__(self):
         self.backend.flux_export(self.planes, self.partials)
         return {f: self.planes[k] for k, f in enumerate(self.fields)}
+
+
+class FluxMeanExport(FluxExport):
+    """FluxMeanExport(model, coarsen=(4, 4), fields=_capi.FLUX_FIELDS, rho_water=1025.0, every=1): the coupling fluxes as the MEAN over
+    the model steps since the last call, which is what a coupler exchanges (`picles_flux_mean_*`; include/picles_hip.h, "flux means").
+    The device accumulates the cell sums behind every `every`-th model step — the steps stay fused — and calling the object finalises
+    them into the device tensors of FluxExport (`picles_flux_mean_export` with reset = 1: the next interval starts empty) and returns
+    {plane name: float32 CUDA tensor [nyc, nxc]}.  `n_samples`, `t_first`, `t_last` describe the samples held now (after a call: the
+    interval that call exported is in `exported`).  `partials` holds the unscaled, undivided tile partials of the interval: the
+    host divides their combination by the number of samples.  A call with no sample held is refused by the library."""
+
+    def __init__(self, model, coarsen=(4, 4), fields=K.FLUX_FIELDS, rho_water=1025.0, every=1, device=None):
+        super().__init__(model, coarsen, fields, rho_water, device)
+        if not hasattr(self.backend, "flux_mean_export"):
+            raise NotImplementedError("FluxMeanExport needs the HIP library's mean set (picles_flux_mean_*): this backend has none")
+        self.backend.flux_mean_init(every=every, first=every)
+        self.exported = dict(n_samples=0, t_first=0.0, t_last=0.0)
+
+    def _scalars(self):
+        return self.backend.flux_mean_scalars()           # host-side values: no device work
+
+    n_samples = property(lambda self: self._scalars()[0])
+    t_first = property(lambda self: self._scalars()[1])
+    t_last = property(lambda self: self._scalars()[2])
+
+    def __call__(self):
+        n, t0, t1 = self._scalars()
+        self.backend.flux_mean_export(self.planes, self.partials, reset=True)
+        self.exported = dict(n_samples=n, t_first=t0, t_last=t1)
+        return {f: self.planes[k] for k, f in enumerate(self.fields)}

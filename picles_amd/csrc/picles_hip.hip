@@ -36,6 +36,8 @@
  *                    node bears a particle from the prescribed sea state, advances it and leaves its record.  Latency bound.
  *   k_ckpt           checkpoint payload: packs / verifies / unpacks the planes of a restart blob in one pass. HBM bound.
  *   k_flux           (k_flux.h) coupling fluxes: wind input, dissipation, stress and Stokes drift planes + one partial per tile
+ *   k_flux_mean_update, k_flux_mean_final   (k_flux_mean.h) flux means: the cell sums of k_flux added to fp64 accumulators behind every
+ *                    step, from the scatter records where a fused step is pending; the interval mean in k_flux's planes and partials
  *   k_diag           (k_diag.h) coarse wave diagnostics: float32 Hs / Tp / cg planes + one partial of sums and maxima per tile of
  *                    256 coarse cells, one pass over State. HBM bound.
  */
@@ -62,6 +64,7 @@
 #include "k_flux.h"
 #include "k_probe.h"
 #include "k_stat.h"
+#include "k_flux_mean.h"
 #include "k_nest.h"
 #include "k_track.h"
 
@@ -693,6 +696,17 @@ struct picles_ctx {
     int flux_nfields = 0, flux_npart = 0;
     size_t flux_field_bytes = 0, flux_part_off = 0, flux_slot_bytes = 0;
     double *flux_scratch = nullptr;                /* picles_flux_export without a partials buffer */
+    /* flux means (picles_flux_mean_*; k_flux_mean.h): eleven fp64 accumulator planes of the flux set's coarse cells in one device
+     * block, the host-side scalars, and the event behind the latest operation on the planes, as the statistics set keeps them */
+    bool fm_on = false;
+    Cadence fm_cad;                                /* steps: model steps completed since picles_flux_mean_init */
+    long long fm_samples = 0;
+    double fm_t_first = 0.0, fm_t_last = 0.0;
+    double *fm_acc = nullptr;
+    size_t fm_bytes = 0;
+    hipEvent_t fm_ev = nullptr;
+    hipStream_t fm_stream = nullptr;               /* the stream fm_ev was recorded on */
+    bool fm_ev_live = false;
     int probe_n = 0;
     int *probe_nodes = nullptr;                    /* device: i plane, then the LOCAL row plane */
     Cadence probe_cad;                             /* steps: model steps completed since picles_probe_init */
@@ -869,6 +883,9 @@ static void track_release(picles_ctx *c);
 /* run statistics (defined behind the station probes) */
 static int stat_update(picles_ctx *c, hipStream_t s);
 static void stat_release(picles_ctx *c);
+/* flux means (defined behind the run statistics) */
+static int flux_mean_update(picles_ctx *c, hipStream_t s, const char *who);
+static void flux_mean_release(picles_ctx *c);
 /* open-boundary forcing (defined behind the run statistics) */
 static void bforce_release(picles_ctx *c);
 
@@ -911,6 +928,7 @@ static void step_completed(picles_ctx *c)
     c->clock += c->step_dt;
     c->probe_cad.steps++;
     c->stat_cad.steps++;
+    c->fm_cad.steps++;
 }
 
 /* scatter + remesh of the last fused step, if still outstanding */
@@ -1126,6 +1144,8 @@ PX_EXPORT int32_t picles_destroy(picles_ctx *c)
     c->store.release();
     c->diag_ring.release();
     if (c->diag_scratch) hipFree(c->diag_scratch);
+    if (c->fm_on) hipDeviceSynchronize();       /* updates issued on caller streams read and write the planes about to go */
+    flux_mean_release(c);
     c->flux_ring.release();
     if (c->flux_scratch) hipFree(c->flux_scratch);
     probe_release(c);
@@ -2256,7 +2276,9 @@ PX_EXPORT int32_t picles_time_step(picles_ctx *c, double dt, int32_t flags)
     /* the track sample of this step, at the clock after the tick: the same place, the same ordering */
     if (c->trk && (rc = track_take(c, c->stream))) return rc;
     /* the statistics update of this step: the same place, the same ordering */
-    if (c->stat_on && c->stat_cad.due(c->stat_cad.steps)) return stat_update(c, c->stream);
+    if (c->stat_on && c->stat_cad.due(c->stat_cad.steps)) { if ((rc = stat_update(c, c->stream))) return rc; }
+    /* the flux-mean update of this step: the same place, the same ordering */
+    if (c->fm_on && c->fm_cad.due(c->fm_cad.steps)) return flux_mean_update(c, c->stream, "picles_time_step");
     return 0;
 }
 
@@ -2724,12 +2746,13 @@ PX_EXPORT int32_t picles_flux_pending(const picles_ctx *c) { return c ? c->flux_
  * level at the clock (k_wind_sample<1>, the sampler of its windows: a function of the time alone); a host-set window refuses with a
  * text that names the remedy — before anything is launched (the flush of a pending step included: it changes neither the window nor
  * the clock) */
-static int flux_wind(picles_ctx *c, const char *who, const double *&u, const double *&v)
+static int flux_wind(picles_ctx *c, const char *who, const double *&u, const double *&v, hipStream_t s = nullptr)
 {
+    if (!s) s = c->stream;
     if (c->wind.level_at(c->A, c->clock, u, v)) return 0;
     if (c->wind.from_lattice()) {      /* the device has the source: the level at the clock itself, into the spare pair */
         HIPCHK(c, hipSetDevice(c->device));
-        return c->wind.sample_spare(c, c->clock, who, c->stream, u, v);
+        return c->wind.sample_spare(c, c->clock, who, s, u, v);
     }
     char buf[400];
     snprintf(buf, sizeof buf, "%s: the wind window [%.17g, %.17g] holds no level at the clock %.17g, and nothing is interpolated: step to a "
@@ -2826,6 +2849,10 @@ PX_EXPORT int32_t picles_flux_free(picles_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->store_stream) HIPCHK(c, hipStreamSynchronize(c->store_stream));
+    if (c->fm_on) {      /* the mean set takes its cells from this one: it goes with it */
+        HIPCHK(c, hipDeviceSynchronize());
+        flux_mean_release(c);
+    }
     c->flux_ring.release();
     if (c->flux_scratch) { hipFree(c->flux_scratch); c->flux_scratch = nullptr; }
     c->flux = FluxP{};
@@ -3335,6 +3362,211 @@ PX_EXPORT int32_t picles_stat_free(picles_ctx *c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());       /* updates in flight read and write the planes about to go */
     stat_release(c);
+    return 0;
+}
+
+/* ---- flux means (the contract: include/picles_hip.h, "flux means"; the kernels: k_flux_mean.h) ---- */
+/* an operation on the accumulators, on stream s: behind the latest one wherever that ran */
+static int flux_mean_order(picles_ctx *c, hipStream_t s)
+{
+    if (c->fm_ev_live && c->fm_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->fm_ev, 0));
+    return 0;
+}
+static int flux_mean_mark(picles_ctx *c, hipStream_t s)
+{
+    HIPCHK(c, hipEventRecord(c->fm_ev, s));
+    c->fm_stream = s;
+    c->fm_ev_live = true;
+    return 0;
+}
+
+template <bool FROM_REC>
+static void flux_mean_launch(picles_ctx *c, hipStream_t s, const Arrays &A, const double *u, const double *v)
+{
+    const FluxP &F = c->flux;
+    const dim3 block(PICLES_BLOCK);
+    const dim3 grid((unsigned)(nblocks(F.Nx, PICLES_BLOCK) * (long long)F.nyc_loc));
+#define FM_CASE(CX) case CX: hipLaunchKernelGGL((k_flux_mean_update<FROM_REC, CX>), grid, block, 0, s, c->P, c->G, A, F, u, v, c->fm_acc); break
+    switch (F.cx) {
+    FM_CASE(1); FM_CASE(2); FM_CASE(4); FM_CASE(8); FM_CASE(16);
+    default:
+        hipLaunchKernelGGL((k_flux_mean_update<FROM_REC, 0>), dim3((unsigned)c->flux_npart), dim3(DIAG_TILE), 0, s, c->P, c->G, A, F, u, v, c->fm_acc);
+    }
+#undef FM_CASE
+}
+
+/* one update, on stream s — the stream behind which everything the sample depends on has been ordered (stat_update's rule).  The wind
+ * rule first: it refuses before anything is launched; a lattice's level at the clock is sampled on s, behind the set's latest operation */
+static int flux_mean_update(picles_ctx *c, hipStream_t s, const char *who)
+{
+    { int rc = flux_mean_order(c, s); if (rc) return rc; }
+    const double *u, *v;
+    { int rc = flux_wind(c, who, u, v, s); if (rc) return rc; }
+    if (c->pending) flux_mean_launch<true>(c, s, arrays_for(c, c->cur, c->cur), u, v);
+    else flux_mean_launch<false>(c, s, c->A, u, v);
+    HIPCHK(c, hipGetLastError());
+    { int rc = flux_mean_mark(c, s); if (rc) return rc; }
+    /* a wind lattice samples the next windows on the context stream into planes this update may still be reading on another one */
+    if (s != c->stream && c->wind.from_lattice()) HIPCHK(c, hipStreamWaitEvent(c->stream, c->fm_ev, 0));
+    if (c->fm_samples == 0) c->fm_t_first = c->clock;
+    c->fm_t_last = c->clock;
+    c->fm_samples++;
+    return 0;
+}
+
+static void flux_mean_release(picles_ctx *c)
+{
+    if (c->fm_acc) hipFree(c->fm_acc);
+    if (c->fm_ev) hipEventDestroy(c->fm_ev);
+    c->fm_acc = nullptr; c->fm_ev = nullptr; c->fm_stream = nullptr; c->fm_ev_live = false;
+    c->fm_on = false; c->fm_bytes = 0;
+    c->fm_cad = Cadence{};
+    c->fm_samples = 0; c->fm_t_first = 0.0; c->fm_t_last = 0.0;
+}
+
+PX_EXPORT int32_t picles_flux_mean_init(picles_ctx *c, int32_t every, int32_t first)
+{
+    if (!c) return -1;
+    if (!c->flux_ring.cap) return fail(c, -2, "picles_flux_mean_init: the mean set takes its cells, mask and scales from a flux set (picles_flux_init first)");
+    if (c->fm_on) return fail(c, -2, "picles_flux_mean_init: a mean set exists (picles_flux_mean_free first)");
+    if (every < 1 || first < 1) return fail(c, -2, "picles_flux_mean_init: every and first must be >= 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->flux.Nxc * c->flux.nyc_loc * FLUX_NP * 8;
+    Undo undo{[c] { flux_mean_release(c); }};
+    { int rc = store_stream_get(c); if (rc) return rc; }
+    HIPCHK(c, hipMalloc(&c->fm_acc, bytes));
+    HIPCHK(c, hipEventCreateWithFlags(&c->fm_ev, hipEventDisableTiming));
+    HIPCHK(c, hipMemsetAsync(c->fm_acc, 0, bytes, c->stream));
+    c->fm_bytes = bytes;
+    { int rc = flux_mean_mark(c, c->stream); if (rc) return rc; }
+    c->fm_cad = Cadence{every, first, 0};
+    c->fm_samples = 0; c->fm_t_first = 0.0; c->fm_t_last = 0.0;
+    c->fm_on = true;
+    undo.armed = false;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_flux_mean_shape(const picles_ctx *c, int32_t *every, int32_t *n_planes, size_t *bytes)
+{
+    if (!c || !c->fm_on) return -1;
+    if (every) *every = c->fm_cad.every;
+    if (n_planes) *n_planes = FLUX_NP;
+    if (bytes) *bytes = c->fm_bytes;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_flux_mean_update(picles_ctx *c, void *stream)
+{
+    if (!c) return -1;
+    if (!c->fm_on) return fail(c, -2, "picles_flux_mean_init first");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (stream) c->ext_streams = true;
+    return flux_mean_update(c, stream ? (hipStream_t)stream : c->stream, "picles_flux_mean_update");
+}
+
+/* the accumulators and the three scalars to zero, on stream s behind the latest operation */
+static int flux_mean_zero(picles_ctx *c, hipStream_t s)
+{
+    { int rc = flux_mean_order(c, s); if (rc) return rc; }
+    HIPCHK(c, hipMemsetAsync(c->fm_acc, 0, c->fm_bytes, s));
+    { int rc = flux_mean_mark(c, s); if (rc) return rc; }
+    c->fm_samples = 0; c->fm_t_first = 0.0; c->fm_t_last = 0.0;
+    return 0;
+}
+
+/* the finalising kernel on the context stream into (fields, partials), behind the updates wherever they ran.  Nothing is flushed */
+static int flux_mean_final(picles_ctx *c, float *fields, double *partials)
+{
+    { int rc = flux_mean_order(c, c->stream); if (rc) return rc; }
+    hipLaunchKernelGGL(k_flux_mean_final, dim3((unsigned)c->flux_npart), dim3(DIAG_TILE), 0, c->stream, c->flux, (double)c->fm_samples,
+                       (const double *)c->fm_acc, fields, partials);
+    HIPCHK(c, hipGetLastError());
+    return flux_mean_mark(c, c->stream);
+}
+
+PX_EXPORT int32_t picles_flux_mean_push(picles_ctx *c, int32_t reset)
+{
+    if (!c) return -1;
+    if (!c->fm_on) return fail(c, -2, "picles_flux_mean_init first");
+    if (c->fm_samples == 0) return fail(c, -2, "picles_flux_mean_push: the mean set holds no sample: there is no mean to form");
+    unsigned char *d = c->flux_ring.next_slot();
+    if (!d) return fail(c, -3, "flux ring full: pop first");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flux_mean_final(c, (float *)d, (double *)(d + c->flux_part_off)); if (rc) return rc; }
+    { int rc = c->flux_ring.ship(c, d, c->stream, c->flux_slot_bytes, 0); if (rc) return rc; }
+    return reset ? flux_mean_zero(c, c->stream) : 0;
+}
+
+PX_EXPORT int32_t picles_flux_mean_export(picles_ctx *c, void *fields_dev, double *partials_dev, void *caller_stream, int32_t reset)
+{
+    if (!c) return -1;
+    if (!c->fm_on) return fail(c, -2, "picles_flux_mean_init first");
+    if (!fields_dev) return fail(c, -2, "picles_flux_mean_export: no device buffer for the fields");
+    if (c->fm_samples == 0) return fail(c, -2, "picles_flux_mean_export: the mean set holds no sample: there is no mean to form");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!partials_dev) {
+        if (!c->flux_scratch) HIPCHK(c, hipMalloc(&c->flux_scratch, (size_t)c->flux_npart * FLUX_NP * 8));
+        partials_dev = c->flux_scratch;
+    }
+    if (caller_stream) {      /* whatever the caller still has reading or writing its buffers comes first */
+        HIPCHK(c, hipEventRecord(c->ev_ctx, (hipStream_t)caller_stream));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_ctx, 0));
+    }
+    { int rc = flux_mean_final(c, (float *)fields_dev, partials_dev); if (rc) return rc; }
+    if (caller_stream) {
+        HIPCHK(c, hipEventRecord(c->ev_ctx, c->stream));
+        HIPCHK(c, hipStreamWaitEvent((hipStream_t)caller_stream, c->ev_ctx, 0));
+    }
+    return reset ? flux_mean_zero(c, c->stream) : 0;
+}
+
+PX_EXPORT int32_t picles_flux_mean_get(picles_ctx *c, double *planes, int64_t *n_samples, double *t_first, double *t_last)
+{
+    if (!c) return -1;
+    if (!c->fm_on) return fail(c, -2, "picles_flux_mean_init first");
+    if (planes) {
+        HIPCHK(c, hipSetDevice(c->device));
+        /* the latest operation on the planes alone: the copy rides the store stream behind its event; a pending step stays pending */
+        HIPCHK(c, hipStreamWaitEvent(c->store_stream, c->fm_ev, 0));
+        HIPCHK(c, hipMemcpyAsync(planes, c->fm_acc, c->fm_bytes, hipMemcpyDeviceToHost, c->store_stream));
+        HIPCHK(c, hipStreamSynchronize(c->store_stream));      /* the caller's (pageable) buffer is complete and released */
+    }
+    if (n_samples) *n_samples = (int64_t)c->fm_samples;
+    if (t_first) *t_first = c->fm_t_first;
+    if (t_last) *t_last = c->fm_t_last;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_flux_mean_set(picles_ctx *c, const double *planes, int64_t n_samples, double t_first, double t_last)
+{
+    if (!c) return -1;
+    if (!c->fm_on) return fail(c, -2, "picles_flux_mean_init first");
+    if (!planes) return fail(c, -2, "picles_flux_mean_set: planes must be given");
+    if (n_samples < 0) return fail(c, -2, "picles_flux_mean_set: n_samples must be >= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc = flux_mean_order(c, c->stream); if (rc) return rc; }
+    HIPCHK(c, hipMemcpyAsync(c->fm_acc, planes, c->fm_bytes, hipMemcpyHostToDevice, c->stream));
+    { int rc = flux_mean_mark(c, c->stream); if (rc) return rc; }
+    HIPCHK(c, hipEventSynchronize(c->fm_ev));              /* the caller's buffer has been read to its last byte */
+    c->fm_samples = (long long)n_samples; c->fm_t_first = t_first; c->fm_t_last = t_last;
+    return 0;
+}
+
+PX_EXPORT int32_t picles_flux_mean_reset(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->fm_on) return fail(c, -2, "picles_flux_mean_init first");
+    HIPCHK(c, hipSetDevice(c->device));
+    return flux_mean_zero(c, c->stream);      /* in stream order behind the updates already issued; no host synchronisation; s goes on */
+}
+
+PX_EXPORT int32_t picles_flux_mean_free(picles_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->fm_on) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());       /* updates in flight read and write the planes about to go */
+    flux_mean_release(c);
     return 0;
 }
 
@@ -4034,6 +4266,9 @@ PX_EXPORT int32_t picles_nest_relocate(picles_ctx *c, picles_ctx *p, int32_t si,
         return fail(c, -5, W + "the child still holds a " + (c->fb ? "feedback" : c->nest ? "nest" : c->bf_n ? "forcing set" : "statistics set") +
                            ": its nodes would keep their indices and lose their places (end the leg first: picles_nest_free, picles_bforce_free, "
                            "picles_stat_free)");
+    if (c->fm_on && c->fm_samples > 0)
+        return fail(c, -2, W + "the child's flux-mean set holds " + std::to_string(c->fm_samples) + " samples, whose cells would mean another place "
+                           "after the move: picles_flux_mean_push or picles_flux_mean_reset first");
     if (c->G.periodic_x || c->G.periodic_y || c->G.tripolar) return fail(c, -5, W + "the child has a periodic axis: only an open box moves");
     if (c->A.m11) return fail(c, -5, W + "the child has a metric set (picles_set_metric): its planes belong to the old position");
     if (c->wind.streamed()) return fail(c, -5, W + "the child runs under a wind stream: its ring holds levels sampled for the old position's lattice window");
@@ -4443,7 +4678,7 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
     if (flags & PICLES_STEP_ATOMIC) return fail(c, -5, "PICLES_STEP_ATOMIC is single-slab only");
     { int rc = probe_room(c, n_steps, "picles_slab_run_steps"); if (rc) return rc; }      /* up front: nothing has changed yet */
     HIPCHK(c, hipSetDevice(c->device));
-    if ((c->probe_n || c->stat_on) && !R->sP) {
+    if ((c->probe_n || c->stat_on || c->fm_on) && !R->sP) {
         HIPCHK(c, hipStreamCreateWithFlags(&R->sP, hipStreamNonBlocking));
         for (hipEvent_t *e : {&R->evPx, &R->evPm, &R->evP[0], &R->evP[1]}) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
@@ -4508,7 +4743,8 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
         if (phases) { HIPCHK(c, hipEventRecord(pe.m1, R->sM)); R->ph_used.push_back(pe); }
         const bool probe = c->probe_n && c->probe_cad.due(c->probe_cad.steps + 1);
         const bool stat = c->stat_on && c->stat_cad.due(c->stat_cad.steps + 1);      /* the statistics update: ordered exactly as a probe */
-        const bool sample = probe || stat;
+        const bool fmean = c->fm_on && c->fm_cad.due(c->fm_cad.steps + 1);        /* the flux-mean update: likewise */
+        const bool sample = probe || stat || fmean;
         if (sample && fused == 0) {      /* what the probe of a fused step waits for: the interior launch and the delivered halo */
             HIPCHK(c, hipEventRecord(R->evPm, R->sM));
             HIPCHK(c, hipEventRecord(R->evPx, R->sE));
@@ -4533,11 +4769,13 @@ PX_EXPORT int32_t picles_slab_run_steps(picles_ctx *c, double dt, int32_t n_step
             HIPCHK(c, hipStreamWaitEvent(R->sP, R->evPx, 0));
             if (probe && (rc = probe_take(c, R->sP))) return rc;
             if (stat && (rc = stat_update(c, R->sP))) return rc;
+            if (fmean && (rc = flux_mean_update(c, R->sP, "picles_slab_run_steps"))) return rc;
             HIPCHK(c, hipEventRecord(R->evP[c->cur], R->sP));
             R->evP_live[c->cur] = true;
         } else if (sample) {
             if (probe && (rc = probe_take(c, R->sM))) return rc;      /* State is in memory: gathered on the stream that ran the scatter */
             if (stat && (rc = stat_update(c, R->sM))) return rc;
+            if (fmean && (rc = flux_mean_update(c, R->sM, "picles_slab_run_steps"))) return rc;
         }
         R->steps++;
     }

@@ -112,6 +112,35 @@ def combine_flux_partials(list_of_partials) -> dict:
     return dict(zip(K.FLUX_PARTIAL, acc))
 
 
+def flux_mean_tile_partials(acc) -> np.ndarray:
+    """the tile partials of a mean (include/picles_hip.h "flux means") from accumulator planes [11, Nxc, nyc] on the host: each plane
+    through the halving tree inside each group of 64 coarse columns, then the four groups of a tile of 256 in ascending order;
+    [nyc * tiles_per_row, 11], index J tiles_per_row + T — the bits k_flux_mean_final writes"""
+    acc = np.asarray(acc, dtype=np.float64)
+    _, nxc, nyc = acc.shape
+    tpr = -(-nxc // 256)
+    v = np.zeros((K.FLUX_NPARTIAL, tpr * 256, nyc))
+    v[:, :nxc] = acc
+    v = v.reshape(K.FLUX_NPARTIAL, tpr, 4, 64, nyc)
+    s = 32
+    while s >= 1:
+        v = v[:, :, :, :s] + v[:, :, :, s:2 * s]
+        s //= 2
+    w = v[:, :, :, 0]
+    t = ((w[:, :, 0] + w[:, :, 1]) + w[:, :, 2]) + w[:, :, 3]              # [11, tpr, nyc]
+    return np.ascontiguousarray(t.transpose(2, 1, 0).reshape(nyc * tpr, K.FLUX_NPARTIAL))
+
+
+def flux_mean_concat(parts) -> dict:
+    """what flux_mean_get returned on every rank, in rank order, as one whole-grid result: the planes row block after row block, the
+    scalars of rank 0 (the ranks step together), and "totals": the eleven sums over all cells — every rank's tile partials combined
+    in rank order as combine_flux_partials does — divided by n_samples (None without a sample)"""
+    n = int(parts[0]["n_samples"])
+    tot = combine_flux_partials([flux_mean_tile_partials(p["acc"]) for p in parts])
+    return dict(acc=np.concatenate([np.asarray(p["acc"]) for p in parts], axis=2), n_samples=n, t_first=parts[0]["t_first"],
+                t_last=parts[0]["t_last"], totals={k: v / n for k, v in tot.items()} if n else None)
+
+
 # ---- run statistics: the plane block of picles_stat_get / picles_stat_set (include/picles_hip.h "run statistics") ----
 STAT_GROUPS = {"peak": K.STAT_PEAK, "mean": K.STAT_MEAN, "exceed": K.STAT_EXCEED}
 STAT_PEAK_PLANES = ("e_peak", "mx_peak", "my_peak", "t_peak")
@@ -662,6 +691,83 @@ class HipModel:
     @property
     def flux_pending(self):
         return self.lib.picles_flux_pending(self.h)
+
+    # ---- flux means (picles_flux_mean_*: the coupling fluxes accumulated behind every step, exported as interval means) ----
+    def flux_mean_init(self, every=1, first=1):
+        """a mean set over the flux set's cells (flux_init first): an update follows every model step s (counted from here) with
+        s >= first and (s - first) % every == 0; a pending fused step stays pending"""
+        self._ck(self.lib.picles_flux_mean_init(self.h, int(every), int(first)), "picles_flux_mean_init")
+
+    def flux_mean_shape(self):
+        """(every, n_planes = 11, bytes of the accumulator planes); no device work"""
+        ev, npl = C.c_int32(), C.c_int32()
+        b = C.c_size_t()
+        if self.lib.picles_flux_mean_shape(self.h, C.byref(ev), C.byref(npl), C.byref(b)) != 0:
+            raise K.PiclesError("picles_flux_mean_shape failed: flux_mean_init first")
+        return ev.value, npl.value, b.value
+
+    def flux_mean_update(self, stream=None):
+        """one update now (callers of the split-phase API, on the stream their step is ordered on)"""
+        self._ck(self.lib.picles_flux_mean_update(self.h, stream), "picles_flux_mean_update")
+
+    def flux_mean_push(self, reset=True):
+        """the mean over the samples held into the next slot of the flux ring (flux_pop serves it); reset: zero behind it"""
+        self._ck(self.lib.picles_flux_mean_push(self.h, 1 if reset else 0), "picles_flux_mean_push")
+
+    def flux_mean_export(self, fields, partials=None, reset=True):
+        """the mean of flux_mean_push written into torch CUDA tensors (picles_flux_mean_export): the arguments of flux_export"""
+        import torch
+        nxc, nyc, nf, npart, _ = self.flux_shape()
+        if not (fields.is_cuda and fields.dtype == torch.float32 and fields.is_contiguous() and fields.numel() == nf * nxc * nyc):
+            raise ValueError(f"flux_mean_export: fields must be a contiguous float32 device tensor of {nf} x {nyc} x {nxc} values")
+        if partials is not None and not (partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()
+                                         and partials.numel() == npart * K.FLUX_NPARTIAL):
+            raise ValueError(f"flux_mean_export: partials must be a contiguous float64 device tensor of {npart} x {K.FLUX_NPARTIAL} values")
+        cur = torch.cuda.current_stream(fields.device)
+        s = cur
+        if not cur.cuda_stream:          # torch's default stream is the null stream: ordered through a side stream (flux_export)
+            s = getattr(self, "_stream_side", None)
+            if s is None:
+                s = self._stream_side = torch.cuda.Stream(fields.device)
+            s.wait_stream(cur)
+        try:
+            self._ck(self.lib.picles_flux_mean_export(self.h, fields.data_ptr(), None if partials is None else C.cast(partials.data_ptr(), K.c_double_p),
+                                                      s.cuda_stream, 1 if reset else 0), "picles_flux_mean_export")
+        finally:
+            if s is not cur:
+                cur.wait_stream(s)
+
+    def flux_mean_get(self):
+        """the raw accumulators: {"acc": float64 [11, Nxc, nyc_loc] (each plane [I + Nxc J] in memory: the nine sums in plane order,
+        n_active, n_bad), "n_samples", "t_first", "t_last"}; waits for the latest operation on them alone"""
+        nxc, nyc, _, _, _ = self.flux_shape()
+        buf = np.empty(K.FLUX_NPARTIAL * nxc * nyc)
+        n, t0, t1 = C.c_int64(), C.c_double(), C.c_double()
+        self._ck(self.lib.picles_flux_mean_get(self.h, K.dptr(buf), C.byref(n), C.byref(t0), C.byref(t1)), "picles_flux_mean_get")
+        return dict(acc=buf.reshape((K.FLUX_NPARTIAL, nyc, nxc)).transpose(0, 2, 1), n_samples=int(n.value), t_first=float(t0.value),
+                    t_last=float(t1.value))
+
+    def flux_mean_scalars(self):
+        """(n_samples, t_first, t_last) of the mean set: host-side values, no device work"""
+        n, t0, t1 = C.c_int64(), C.c_double(), C.c_double()
+        self._ck(self.lib.picles_flux_mean_get(self.h, None, C.byref(n), C.byref(t0), C.byref(t1)), "picles_flux_mean_get")
+        return int(n.value), float(t0.value), float(t1.value)
+
+    def flux_mean_set(self, acc):
+        """upload what flux_mean_get returned: how a picked-up run continues an open interval"""
+        nxc, nyc, _, _, _ = self.flux_shape()
+        a = np.asarray(acc["acc"], dtype=np.float64)
+        if a.shape != (K.FLUX_NPARTIAL, nxc, nyc):
+            raise ValueError(f"flux_mean_set: acc must be {K.FLUX_NPARTIAL} x {nxc} x {nyc}, got {a.shape}")
+        buf = np.ascontiguousarray(a.transpose(0, 2, 1))
+        self._ck(self.lib.picles_flux_mean_set(self.h, K.dptr(buf), int(acc["n_samples"]), float(acc["t_first"]), float(acc["t_last"])),
+                 "picles_flux_mean_set")
+
+    def flux_mean_reset(self):
+        self._ck(self.lib.picles_flux_mean_reset(self.h), "picles_flux_mean_reset")
+
+    def flux_mean_free(self):
+        self._ck(self.lib.picles_flux_mean_free(self.h), "picles_flux_mean_free")
 
     # ---- station probes (picles_probe_*: the State value of chosen nodes behind every step, the fused path kept) ----
     def probe_init(self, nodes, every=1, first=1, capacity=64):

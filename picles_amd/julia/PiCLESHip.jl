@@ -29,7 +29,7 @@ import PiCLES.Operators.TimeSteppers: time_step!, movie_time_step!, time_step!_a
 import PiCLES.Simulations: init_particles!
 
 const libpicles = get(ENV, "PICLES_HIP_LIB", "libpicles_hip.so")
-const PICLES_ABI_VERSION = Int32(19)
+const PICLES_ABI_VERSION = Int32(20)
 
 # ---- C structs (include/picles_hip.h) ----------------------------------------------------
 struct picles_grid
@@ -558,6 +558,64 @@ function flux_export!(model::WaveGrowth2DHIP, fields::Ptr{Float32}, partials::Pt
 end
 
 flux_free!(model::WaveGrowth2DHIP) = (check(model.ctx, ccall((:picles_flux_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_flux_free"); nothing)
+
+"""
+    flux_mean_init!(model; every=1, first=1)
+    flux_mean_shape(model) -> (every, n_planes, bytes)
+    flux_mean_update!(model; stream=C_NULL)
+    flux_mean_push!(model; reset=true)                       # served by flux_pop! / flux_pending
+    flux_mean_export!(model, fields, partials=C_NULL; stream=C_NULL, reset=true)
+    flux_mean_get(model) -> (planes::Array{Float64,3}, n_samples, t_first, t_last)
+    flux_mean_set!(model, planes, n_samples, t_first, t_last)
+    flux_mean_reset!(model); flux_mean_free!(model)
+
+Flux means (`picles_flux_mean_*`; the contract is in include/picles_hip.h, "flux means"): the coupling fluxes accumulated on the
+device behind every model step — a pending fused step stays pending — and exported as the mean over the samples of a coupling
+interval.  The set takes its cells, mask and scales from the flux set (`flux_init!` first).  `flux_mean_get` returns the eleven raw
+fp64 accumulator planes `[Nxc, nyc, 11]`; a picked-up run puts them back with `flux_mean_set!`.
+"""
+flux_mean_init!(model::WaveGrowth2DHIP; every::Integer=1, first::Integer=1) =
+    (check(model.ctx, ccall((:picles_flux_mean_init, libpicles), Int32, (Ptr{Cvoid}, Int32, Int32), model.ctx, every, first), "picles_flux_mean_init"); nothing)
+
+function flux_mean_shape(model::WaveGrowth2DHIP)
+    ev = Ref{Int32}(0); npl = Ref{Int32}(0); nbytes = Ref{Csize_t}(0)
+    ccall((:picles_flux_mean_shape, libpicles), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Csize_t}), model.ctx, ev, npl, nbytes) == 0 ||
+        error("picles_flux_mean_shape failed: flux_mean_init! first")
+    (Int(ev[]), Int(npl[]), Int(nbytes[]))
+end
+
+flux_mean_update!(model::WaveGrowth2DHIP; stream::Ptr{Cvoid}=C_NULL) =
+    (check(model.ctx, ccall((:picles_flux_mean_update, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), model.ctx, stream), "picles_flux_mean_update"); nothing)
+
+flux_mean_push!(model::WaveGrowth2DHIP; reset::Bool=true) =
+    (check(model.ctx, ccall((:picles_flux_mean_push, libpicles), Int32, (Ptr{Cvoid}, Int32), model.ctx, reset ? 1 : 0), "picles_flux_mean_push"); nothing)
+
+function flux_mean_export!(model::WaveGrowth2DHIP, fields::Ptr{Float32}, partials::Ptr{Float64}=Ptr{Float64}(C_NULL); stream::Ptr{Cvoid}=C_NULL,
+                           reset::Bool=true)
+    check(model.ctx, ccall((:picles_flux_mean_export, libpicles), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Int32),
+        model.ctx, fields, partials, stream, reset ? 1 : 0), "picles_flux_mean_export")
+    nothing
+end
+
+function flux_mean_get(model::WaveGrowth2DHIP)
+    nxc, nyc, _, _, _ = flux_shape(model)
+    planes = Array{Float64,3}(undef, nxc, nyc, 11)
+    n = Ref{Int64}(0); t0 = Ref{Float64}(0.0); t1 = Ref{Float64}(0.0)
+    check(model.ctx, ccall((:picles_flux_mean_get, libpicles), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ref{Int64}, Ref{Float64}, Ref{Float64}),
+        model.ctx, planes, n, t0, t1), "picles_flux_mean_get")
+    (planes, n[], t0[], t1[])
+end
+
+function flux_mean_set!(model::WaveGrowth2DHIP, planes::Array{Float64,3}, n_samples::Integer, t_first::Real, t_last::Real)
+    nxc, nyc, _, _, _ = flux_shape(model)
+    size(planes) == (nxc, nyc, 11) || error("flux_mean_set!: planes must be $nxc x $nyc x 11")
+    check(model.ctx, ccall((:picles_flux_mean_set, libpicles), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Float64, Float64),
+        model.ctx, planes, n_samples, Float64(t_first), Float64(t_last)), "picles_flux_mean_set")
+    nothing
+end
+
+flux_mean_reset!(model::WaveGrowth2DHIP) = (check(model.ctx, ccall((:picles_flux_mean_reset, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_flux_mean_reset"); nothing)
+flux_mean_free!(model::WaveGrowth2DHIP) = (check(model.ctx, ccall((:picles_flux_mean_free, libpicles), Int32, (Ptr{Cvoid},), model.ctx), "picles_flux_mean_free"); nothing)
 
 function run_fluxes!(model::WaveGrowth2DHIP, Δt::Float64, n_steps::Integer, sink!; every::Integer=10, coarsen=(4, 4),
                      fields=FLUX_FIELDS, rho_water::Real=1025.0, slots::Integer=3)

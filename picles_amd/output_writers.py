@@ -1,4 +1,4 @@
-"""OutputWriter: what run() (picles_amd/simulations.py) asks of the entries of `sim.output_writers` — Checkpointer, FieldWriter, FluxWriter,
+"""OutputWriter: what run() (picles_amd/simulations.py) asks of the entries of `sim.output_writers` — Checkpointer, FieldWriter, FluxWriter, MeanFluxWriter,
 StationWriter, StatisticsWriter, TrackWriter — and of the one input that is driven the same way, BoundaryForcing (picles_amd/boundary_forcing.py:
 visited first, so that the level pair of the next chunk is in place before anything else looks at the iteration; NestForcing of
 picles_amd/nesting.py takes its place where the levels come from a parent model, and drives that model's writers through the same
@@ -11,10 +11,10 @@ NO_LIMIT = 2**62          # steps_allowed of a writer that ends no chunk
 
 # the visiting order of each phase, by `kind`; a kind a phase does not list has no work in it (and is visited last)
 PHASE_ORDER = {
-    "begin_run": ("boundary_forcing", "fields", "fluxes", "stations", "statistics", "tracks"),
+    "begin_run": ("boundary_forcing", "fields", "fluxes", "flux_means", "stations", "statistics", "tracks"),
     "after_chunk": ("stations", "checkpointer", "tracks"),
-    "at_iteration": ("boundary_forcing", "statistics", "checkpointer", "fields", "fluxes", "tracks"),
-    "finish": ("checkpointer", "fields", "fluxes", "stations", "statistics", "tracks"),
+    "at_iteration": ("boundary_forcing", "statistics", "checkpointer", "fields", "fluxes", "flux_means", "tracks"),
+    "finish": ("checkpointer", "fields", "fluxes", "flux_means", "stations", "statistics", "tracks"),
 }
 
 

@@ -413,6 +413,7 @@ class SlabModel:
         self._steps_done += 1
         self._probe_after_steps(1, split_phase=not self.native and self.ex is not None)
         self._stat_after_steps(1, split_phase=not self.native and self.ex is not None)
+        self._flux_mean_after_steps(1, split_phase=not self.native and self.ex is not None)
         if self.auto_halo_every > 0 and self.world > 1 and self._steps_done % self.auto_halo_every == 0:
             self.grow_halo_if_needed()
 
@@ -437,6 +438,7 @@ class SlabModel:
         self._steps_done += n
         self._probe_after_steps(n, split_phase=False)
         self._stat_after_steps(n, split_phase=False)
+        self._flux_mean_after_steps(n, split_phase=False)
 
     def check_overflow(self):
         """raise if any particle travelled beyond the ghost rows (it was not scattered: the State is incomplete)"""
@@ -582,6 +584,60 @@ class SlabModel:
         parts = [None] * self.world
         dist.all_gather_object(parts, (f, p))
         return (np.concatenate([a for a, _ in parts], axis=2), combine_flux_partials([b for _, b in parts]), t)
+
+    # ---- flux means: every rank accumulates over the coarse cells of its own rows (picles_flux_mean_*) ----
+    def flux_mean_init(self, every=1, first=1):
+        """the same mean set on every rank, over its flux set's cells (flux_init first).  The native ring, picles_run_steps and
+        picles_time_step update by themselves; the Python-driven split-phase loop calls picles_flux_mean_update behind the halo
+        exchange of every due step."""
+        if every < 1 or first < 1:
+            raise ValueError("flux_mean_init: every and first must be >= 1")
+        self.backend.flux_mean_init(every=every, first=first)
+        self._fmean = dict(every=int(every), first=int(first), steps=0)
+
+    def _flux_mean_after_steps(self, n, split_phase):
+        p = getattr(self, "_fmean", None)
+        if p is None:
+            return
+        p["steps"] += n
+        s = p["steps"]
+        if split_phase and s >= p["first"] and (s - p["first"]) % p["every"] == 0:
+            # the step's launches and its delivered halo are ordered on the interior stream (or on the context stream)
+            self.backend.flux_mean_update(self.s_main.cuda_stream if self.use_streams else None)
+
+    def flux_mean_update(self):
+        """one update now on every rank (the seeded state)"""
+        self.sync()
+        self.backend.flux_mean_update()
+
+    def flux_mean_get(self):
+        return self.backend.flux_mean_get()
+
+    def flux_mean_set(self, acc):
+        self.backend.flux_mean_set(acc)
+
+    def flux_mean_reset(self):
+        self.backend.flux_mean_reset()
+
+    def flux_mean_free(self):
+        if getattr(self, "_fmean", None) is not None:
+            self.backend.flux_mean_free()
+        self._fmean = None
+
+    def gather_flux_means(self):
+        """this rank's accumulators and all ranks': {"acc": [11, Nxc, Nyc] concatenated along y in rank order, "n_samples", "t_first",
+        "t_last", "totals": the eleven sums over all cells divided by n_samples (None without a sample)}.  Accumulators are per
+        coarse cell and coarse cells are global (j_begin % cy == 0): the planes are a single context's bit for bit, for any
+        decomposition.  The totals are formed like gather_fluxes': every rank's planes through the tile tree of the partials, then
+        combined in rank order, J ascending."""
+        from .driver import flux_mean_concat
+        part = self.backend.flux_mean_get()
+        parts = [part]
+        if self.world > 1:
+            import torch.distributed as dist
+            parts = [None] * self.world
+            dist.all_gather_object(parts, part)
+        return flux_mean_concat(parts)
 
     # ---- station probes: every rank samples the nodes of its own rows (picles_probe_*) ----
     def probe_init(self, nodes, every=1, first=1, capacity=64):

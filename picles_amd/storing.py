@@ -83,6 +83,7 @@ def hdf5():
         "H5Tset_size": (C.c_int, [_hid, C.c_size_t]),
         "H5Tset_cset": (C.c_int, [_hid, C.c_int]),
         "H5Tclose": (C.c_int, [_hid]),
+        "H5Lexists": (C.c_int, [_hid, C.c_char_p, _hid]),
         "H5Acreate2": (_hid, [_hid, C.c_char_p, _hid, _hid, _hid, _hid]),
         "H5Aopen": (_hid, [_hid, C.c_char_p, _hid]),
         "H5Aget_space": (_hid, [_hid]),
@@ -306,8 +307,9 @@ def read_state_store(path):
     return out
 
 
-def read_h5_group(path, group, f64=(), strings=(), attrs=()):
-    """the named float64 datasets (arrays in the file's row-major shape), string datasets and string attributes of one group"""
+def read_h5_group(path, group, f64=(), strings=(), attrs=(), optional_f64=()):
+    """the named float64 datasets (arrays in the file's row-major shape), string datasets and string attributes of one group;
+    optional_f64: float64 datasets that are read where the group has a link of that name (H5Lexists) and left out where it has none"""
     L = hdf5()
     f = _ok(L.H5Fopen(str(path).encode(), _H5F_ACC_RDONLY, 0), f"H5Fopen({path})")
     g = _ok(L.H5Gopen2(f, group.encode(), 0), f"H5Gopen2({group})")
@@ -319,7 +321,7 @@ def read_h5_group(path, group, f64=(), strings=(), attrs=()):
         L.H5Sget_simple_extent_dims(space, d, None)
         return tuple(int(v) for v in d)
 
-    for name in f64:
+    for name in tuple(f64) + tuple(n for n in optional_f64 if _ok(L.H5Lexists(g, n.encode(), 0), f"H5Lexists({n})") > 0):
         d = _ok(L.H5Dopen2(g, name.encode(), 0), f"H5Dopen2({name})")
         sp = L.H5Dget_space(d)
         a = np.empty(shape_of(sp), dtype=np.float64)
