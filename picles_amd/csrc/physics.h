@@ -747,7 +747,8 @@ PM_HD void rhs3_jvp(const KParams &P, double lne, double cx, double cy, const Wi
  * Δ_β depend on ya = α_p - 0.85 = -2 yh alone: dH/dya = 2p H (1 - H), dΔ/dya = 100 sgn(ya) t (1 - t)/(1 + t)³, and
  * 1/(1 + t)³ = (1 + t)(hp r)² reuses the reciprocal r = 1/(hp (1 + t)²) the primal has (no second one).  TV: ∂f/∂t through the node
  * wind's slope (du, dv) — for a plain particle U² enters F only (α² ∝ U²; it cancels out of S_dir).
- * A particle that is not plain takes rhs3_jvp (rare path of ros23_try, lane by lane).  J row-major: J[3 r + c] = ∂f_r/∂u_c. */
+ * A particle that is not plain takes rhs3_jvp (rare path of ros23_try, lane by lane).  J row-major: J[3 r + c] = ∂f_r/∂u_c.
+ * Conditioning: dH/dya = 2p H (1 - H) takes 1 - H from the rounded H, relative 2^-52 / (1 - H) on the dH part where H_β saturates. */
 template <bool METRIC, bool TV>
 PM_HD double rhs3_jac_plain(const KParams &P, double L, double cx, double cy, const WindD &W, double pc, double du, double dv,
                             double (&J)[9], Vec3 &dT)      /* returns y = 1/|c̄| (the caller's plain test) */
