@@ -67,3 +67,51 @@ def test_tables_in_the_sources_match():
         m = re.search(rf"#define {name} \(?(-?[0-9.eE+-]+)\)?", h)
         assert m and float(m.group(1)) == val, name
         assert repr(val).lstrip("-") in o
+    _every_constant_of_the_explicit_half_matches(h, o)
+
+
+def _every_constant_of_the_explicit_half_matches(h, o):
+    """ALL of them, not four: the 32 Tsit5 literals of physics.h against TSIT5 above, the DP5 macros (written as quotients) against
+    the exact rationals, the PI controller's and the AutoSwitch's macros against OrdinaryDiffEq's defaults — and the same numbers in
+    the oracle, which types them a second time"""
+    import re
+    from fractions import Fraction
+
+    import _explicit_mp as X
+    num = r"-?[0-9]+\.?[0-9]*(?:[eE][+-]?[0-9]+)?"
+    o_floats = {float(x) for x in re.findall(rf"(?<![\w.])({num})(?![\w.])", o)}
+    o_quot = {Fraction(int(a), int(b)) for a, b in re.findall(r"(-?[0-9]+)\.0 / ([0-9]+)\.0", o)}
+
+    def entries(tab):          # {"A21": value, ..., "C2": ..., "E1": ...}, zeros left out (no macro stands for a zero)
+        d = {f"A{i + 1}{j + 1}": x for i, row in enumerate(tab["A"]) for j, x in enumerate(row)}
+        d.update({f"C{i + 1}": x for i, x in enumerate(tab["c"]) if 0 < i < 5})
+        d.update({f"E{i + 1}": x for i, x in enumerate(tab["e"])})
+        return {k: v for k, v in d.items() if v != 0}
+
+    ts = entries(TSIT5)
+    assert len(ts) == 32 and len(re.findall(r"#define TS_[ACE][0-9]", h)) == 32
+    for name, val in ts.items():
+        m = re.search(rf"#define TS_{name} \(?({num})\)?\s", h)
+        assert m and float(m.group(1)) == val, name
+        assert val in o_floats, name
+    dp = entries(X.tableau_exact("dp5"))
+    assert {k: v.numerator / v.denominator for k, v in dp.items()} == entries(DP5)          # the floats above are these rationals, rounded
+    assert len(dp) == 30 and len(re.findall(r"#define DP_[ACE][0-9]", h)) == 30          # a72 = e2 = 0
+    for name, val in dp.items():
+        m = re.search(rf"#define DP_{name} \((-?[0-9]+)\.0 / ([0-9]+)\.0\)", h)
+        assert m and Fraction(int(m.group(1)), int(m.group(2))) == val, name
+        assert val in o_quot or float(val) in o_floats, name
+    macros = dict(PI_BETA1=X.BETA["dp5"][0], PI_BETA2=X.BETA["dp5"][1], PI_BETA1_TSIT=X.BETA["tsit5"][0], PI_BETA2_TSIT=X.BETA["tsit5"][1],
+                  PI_GAMMA=X.GAMMA, PI_QMIN=X.QMIN, PI_QMAX=X.QMAX, PI_QOLDINIT=X.QOLD_INIT, ASW_STABILITY=X.STABILITY)
+    for name, val in macros.items():
+        m = re.search(rf"#define {name} \(?({num})\)?\s", h)
+        assert m and float(m.group(1)) == float(val), name
+        assert float(val) in o_floats, name
+    for src, name in ((h, "PI_LNQOLDINIT"), (o, "CTRL_LNQOLDINIT")):
+        m = re.search(rf"#define {name} \(({num})\)", src)
+        assert m and float(m.group(1)) == np.log(1e-4), name
+    for name, oname in (("PI_BETA1", "CTRL_BETA1"), ("PI_BETA2", "CTRL_BETA2"), ("PI_GAMMA", "CTRL_GAMMA"), ("PI_QMIN", "CTRL_QMIN"),
+                        ("PI_QMAX", "CTRL_QMAX"), ("PI_QOLDINIT", "CTRL_QOLDINIT"), ("ASW_STABILITY", "ASW_STABILITY")):
+        m = re.search(rf"#define {oname} \(?({num})\)?\s", o)
+        assert m and float(m.group(1)) == float(macros[name]), oname
+    assert re.search(r"beta1 = 0\.14, beta2 = 0\.08", o)          # the oracle's Tsit5 pair (po_integrate_auto)
